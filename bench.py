@@ -6,7 +6,8 @@
         bench.py --gpus N --steps K --warmup W
 
 A "step" is one `DDIMSampler.p_sample_ddim`: one CFG-batched SeerUNet forward (B = 2b), CFG combine and the DDIM
-update, on synthetic latents that are already resident in HBM.  Workload = BASELINE config 2 (Sthv2): b=1 (CFG batch 2),
+update, on synthetic latents that are already resident in HBM; step i runs schedule index 49 - (i mod 50), and every 50th step
+starts a new sample from the same x_T.  Workload = BASELINE config 2 (Sthv2): b=1 (CFG batch 2),
 12 frames total (2 conditioning + 10 predicted), 32x32 latent (256^2 pixels), full-width SD-v1-5-shaped SeerUNet
 (1.08 G parameters, closed-form synthetic weights: there is no network for checkpoints), bf16 storage / fp32 accumulate.
 N > 1: the headline `value` is the north star's partition of ONE step over all GPUs (seervideoldm_amd/parallel.py: batch x CFG
@@ -14,9 +15,13 @@ groups first -- no communication -- then frame shards inside a group, with their
 all-gathers over RCCL), "scaling": "strong": the same work, N GPUs.  N GPUs denoising N independent samples (the path's natural
 units, no data-path collective; linear by construction) is timed in the same run and reported as `weak_scaling`.
 
-Rank 0 prints ONE JSON line.  `roofline` prices the dominant kernel class (the MFMA GEMM / implicit-GEMM conv template,
-93 % of the step's FLOPs) from HIP-event timings taken inside this process; `cpu_baseline` times the CPU oracle
-(oracle/seer_oracle.py, a port of the reference algorithm) on the host cores: one warm-up + three timed FULL steps.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line; the extras run only with
+`--full` (their keys are null without it): `roofline` prices the dominant kernel class (the MFMA GEMM / implicit-GEMM conv
+template, 93 % of the step's FLOPs) from HIP-event timings taken inside this process; `cpu_baseline` times the CPU oracle
+(oracle/seer_oracle.py, a port of the reference algorithm) on the host cores: one warm-up + three timed FULL steps;
+`end_to_end` times a whole clip and `train_step` one fine-tuning step.
+`--dump-outputs DIR` writes what the last timed step returned (`x_prev`, `pred_x0` of `p_sample_ddim`) as DIR/<name>.npy in
+float32; the inputs and weights are seeded, so two builds given the same arguments can be compared output for output.
 `python bench.py --gpus N` without a launcher starts its N ranks itself; `--dtype fp16` times the fp16-storage engine (an extra).
 """
 from __future__ import annotations
@@ -73,7 +78,19 @@ def parse():
                          "shipped yaml names (SeerUNet(compute_dtype=torch.float16)), an extra measurement")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="sthv2",
                     help="default = BASELINE.json's metric configuration; the others are extra measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras (N = 1: roofline, end-to-end clip, CPU baseline; fine-tuning step); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (x_prev, pred_x0) as DIR/<name>.npy, float32")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, outputs) -> None:
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(d / f"{name}.npy", t.numpy().astype(np.float32))
 
 
 def build_inputs(device, seed=0):
@@ -298,7 +315,7 @@ def main():
     sd = synth.synth_state_dict(synth.unet_param_shapes(cfg), device=device)
     model.load_state_dict(sd, strict=True)
     sd_cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sd_cpu = {k: v.cpu() for k, v in sd.items()}
     del sd
     model.eval()
@@ -316,11 +333,18 @@ def main():
     sampler.static_step_outputs = True
 
     def step(i, x):
+        return step_outputs(i, x)[0]
+
+    def chain_input(i, x):
+        # the steps walk the schedule from its noisiest timestep down; after its last one the next step starts a new sample from
+        # x_T (feeding a finished latent back in at t = 981 amplifies it cycle after cycle until it overflows)
+        return x_T if i % nidx == 0 else x
+
+    def step_outputs(i, x):
         index = nidx - 1 - (i % nidx)
         ts = sampler._t_table[index].expand(w["b"])
-        x, _ = sampler.p_sample_ddim(model, x, c, ts, index=index, x0_emb=x0_emb, unconditional_guidance_scale=w["scale"],
+        return sampler.p_sample_ddim(model, x, c, ts, index=index, x0_emb=x0_emb, unconditional_guidance_scale=w["scale"],
                                      unconditional_conditioning=uc)
-        return x
 
     def barrier():
         if world > 1:
@@ -328,17 +352,23 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    last_outputs = {}
+
     def timed_steps():
-        """W untimed + exactly K timed steps between barrier + synchronize pairs; MAX over ranks (ms per step)"""
+        """W untimed + exactly K timed steps between barrier + synchronize pairs; MAX over ranks (ms per step).  The last timed
+        step's outputs are kept (host copies, taken after the clock stopped) in `last_outputs` for --dump-outputs."""
         x = x_T
         for i in range(args.warmup):
-            x = step(i, x)
+            x = step(i, chain_input(i, x))
         barrier()
+        pred = None
         t0 = time.perf_counter()
         for i in range(args.steps):
-            x = step(args.warmup + i, x)
+            x, pred = step_outputs(args.warmup + i, chain_input(args.warmup + i, x))
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and pred is not None:
+            last_outputs.update(x_prev=x.float().cpu(), pred_x0=pred.float().cpu())
         if world > 1:
             import torch.distributed as dist
             tt = torch.tensor([dt], device=device, dtype=torch.float64)
@@ -400,9 +430,12 @@ def main():
         model._shard = None
         model._engine = None
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outputs)
+
     # ---- roofline of the dominant kernel class: event-bracketed launches, device kept ahead of the host
     roofline = None
-    if rank == 0 and world == 1:      # (N > 1: every step is collective -- no rank-0-only extra steps)
+    if args.full and rank == 0 and world == 1:      # (N > 1: every step is collective -- no rank-0-only extra steps)
         eng = model._engine
         timed = TimedOps()
         eng.ops = timed
@@ -482,7 +515,7 @@ def main():
 
     # ---- end-to-end clip latency: 50 DDIM steps + frozen VAE decode of the 10 predicted frames
     clip = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from seervideoldm_amd import AutoencoderKL, ddim_sample
         from seervideoldm_amd.vae import ldm_to_diffusers_vae
         vae = AutoencoderKL().to(device)
@@ -534,7 +567,7 @@ def main():
     # ---- extra: one fine-tuning step (BASELINE config 5: b=1 per GPU, 12 frames, 2 conditioning frames).
     # Data parallel for N > 1: one micro-batch per rank and one RCCL all-reduce of the flat fp32 gradient buffers.
     train = None
-    if not args.no_train and args.workload == "sthv2":
+    if args.full and not args.no_train and args.workload == "sthv2":
         # an extra must never cost the headline line: any failure here is reported inside the JSON instead of raised
         # (every rank takes the same path: the collectives below stay matched)
         try:

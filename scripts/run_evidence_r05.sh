@@ -14,9 +14,9 @@ python scripts/pmc_util_summary.py $(ls $O/pmc_util/*/*_counter_collection.csv |
 cp $O/r05_pmc_traffic.json profiles/r05_pmc_traffic.json
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_util
 # 2. the bench line (default command), with the traffic file of THIS build in place
-python bench.py > $O/r05_bench_final.json.log 2> $O/bench.err
+python bench.py --full > $O/r05_bench_final.json.log 2> $O/bench.err
 # 3. the same command under rocprofv3 --kernel-trace --stats
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train > $O/r05_bench_under_rocprof.json.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train > $O/r05_bench_under_rocprof.json.log 2>&1)
 S=$(ls $O/rocprof/*/*_kernel_stats.csv | head -1)
 cp $S $O/r05_rocprof_kernel_stats.csv
 T=$(ls $O/rocprof/*/*_kernel_trace.csv | head -1)
@@ -36,10 +36,10 @@ hipcc --offload-arch=gfx950 -O3 -Wno-unused-value scripts/lab_mfma_lds.cpp -o bu
 python scripts/exp_shard_sizes.py > $O/r05_shard_sizes.log 2>&1
 # 5. the other configurations
 for w in bridge sthv2_512 sthv2_14 bridge_17; do
-  python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-4000 >> $O/r05_bench_other_configs.json.log
+  python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-4000 >> $O/r05_bench_other_configs.json.log
 done
 # 6. the same step under rocprofv3 at config 4 (the 64x64 latent): where the 256 x 320 tile kernel carries the GEMM / conv class
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof4 -- python3 $R/bench.py --workload sthv2_512 --steps 10 --warmup 3 --no-cpu-baseline --no-train > $O/r05_bench_config4_under_rocprof.json.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof4 -- python3 $R/bench.py --full --workload sthv2_512 --steps 10 --warmup 3 --no-cpu-baseline --no-train > $O/r05_bench_config4_under_rocprof.json.log 2>&1)
 S4=$(ls $O/rocprof4/*/*_kernel_stats.csv | head -1)
 python scripts/rocprof_summary.py $S4 63 > $O/r05_rocprof_summary_config4.md 2>&1
 rm -rf $O/rocprof4

@@ -14,9 +14,9 @@ python scripts/pmc_util_summary.py $(ls $O/pmc_util/*/*_counter_collection.csv |
 cp $O/r06_pmc_traffic.json profiles/r06_pmc_traffic.json
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_util
 # 2. the bench line (default command), with the traffic file of THIS build in place
-python bench.py > $O/r06_bench_final.json.log 2> $O/bench.err
+python bench.py --full > $O/r06_bench_final.json.log 2> $O/bench.err
 # 3. the same command under rocprofv3 --kernel-trace --stats
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-train > $O/r06_bench_under_rocprof.json.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-train > $O/r06_bench_under_rocprof.json.log 2>&1)
 S=$(ls $O/rocprof/*/*_kernel_stats.csv | head -1)
 cp $S $O/r06_rocprof_kernel_stats.csv
 T=$(ls $O/rocprof/*/*_kernel_trace.csv | head -1)
@@ -35,13 +35,13 @@ python scripts/lab_rowchain.py > $O/r06_lab_rowchain.log 2>&1
 python scripts/lab_ff_pre.py > $O/r06_lab_ff_pre.log 2>&1
 python scripts/exp_fixed_vs_variable.py > $O/r06_fixed_vs_variable.md 2>&1
 # 4c. the fp16-storage engine (the mixed_precision every shipped yaml names): the same bench line, an extra measurement
-python bench.py --dtype fp16 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-6000 > $O/r06_bench_fp16.json.log
+python bench.py --full --dtype fp16 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-6000 > $O/r06_bench_fp16.json.log
 # 5. the other configurations
 for w in bridge sthv2_512 sthv2_14 bridge_17; do
-  python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-4000 >> $O/r06_bench_other_configs.json.log
+  python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline --no-train 2>/dev/null | cut -c1-4000 >> $O/r06_bench_other_configs.json.log
 done
 # 6. the same step under rocprofv3 at config 4 (the 64x64 latent): where the 256 x 320 tile kernel carries the GEMM / conv class
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof4 -- python3 $R/bench.py --workload sthv2_512 --steps 10 --warmup 3 --no-cpu-baseline --no-train > $O/r06_bench_config4_under_rocprof.json.log 2>&1)
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof4 -- python3 $R/bench.py --full --workload sthv2_512 --steps 10 --warmup 3 --no-cpu-baseline --no-train > $O/r06_bench_config4_under_rocprof.json.log 2>&1)
 S4=$(ls $O/rocprof4/*/*_kernel_stats.csv | head -1)
 python scripts/rocprof_summary.py $S4 63 > $O/r06_rocprof_summary_config4.md 2>&1
 rm -rf $O/rocprof4

@@ -1,6 +1,6 @@
-"""The contract of `python bench.py` at N = 1 (the command the driver runs): ONE JSON line with the metric, the whole-job value, the
-`roofline` object of the dominant kernel class and the `cpu_baseline` object -- checked on a short run (few steps, small CPU budget;
-the numbers are not asserted, their consistency is)."""
+"""The contract of `python bench.py` at N = 1 (the command the driver runs): ONE JSON line with the metric and the whole-job value;
+with `--full` also the `roofline` object of the dominant kernel class and the `cpu_baseline` object -- checked on short runs (few
+steps, small CPU budget; the numbers are not asserted, their consistency is)."""
 import json
 import subprocess
 import sys
@@ -13,7 +13,7 @@ ROOT = Path(__file__).resolve().parents[1]
 
 
 def test_single_gpu_bench_line_contract():
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--no-train", "--cpu-budget-s", "3"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-train", "--cpu-budget-s", "3"],
                        capture_output=True, text=True, timeout=900, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -35,3 +35,28 @@ def test_single_gpu_bench_line_contract():
     assert ("traffic" in rf) and (rf["traffic"] is None and "traffic_note" in rf or rf["traffic"] > rf["algorithmic_bytes_per_launch"] * 0.5)
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "steps/s" and cb["cores"] >= 1 and 0 < cb["value"] < d["value"] and cb["sample"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline only (the extras' keys are null);
+    --dump-outputs writes the last timed step's x_prev / pred_x0 as float32 .npy files, and the same arguments give the same arrays (to reduction order)"""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(out)], capture_output=True, text=True, timeout=900, cwd=str(ROOT))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["dtype"] == "bf16" and d["unit"] == "steps/s"
+        assert d["higher_is_better"] is True and abs(d["value"] * d["ms_per_step"] - 1e3) < 1.0
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["end_to_end"] is None and d["train_step"] is None
+        got = {n: np.load(out / f"{n}.npy") for n in ("x_prev", "pred_x0")}
+        for a in got.values():
+            assert a.dtype == np.float32 and a.shape == (1, 4, 10, 32, 32) and np.isfinite(a).all()
+        dumps.append(got)
+    for n in dumps[0]:          # same seeded inputs and weights: the same result up to the order of floating-point reductions
+        a, b = dumps[0][n].astype(np.float64), dumps[1][n].astype(np.float64)
+        assert np.linalg.norm(a - b) <= 1e-3 * np.linalg.norm(a), n
