@@ -497,6 +497,32 @@ int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
                            float scale, const float* coef, int32_t* step, const float* x, const float* noise, float* x_prev,
                            float* pred_x0, void* stream);
 
+/* CFG combine + PLMS update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:199-236; eta = 0, so no noise term), fp32.
+ * e is the CFG-combined eps of this evaluation as in seer_cfg_ddim_step (frames >= cond_f only); h1, h2, h3 are earlier e,
+ * newest first, each [b, C, F_pred, HW].  e' by `order`:
+ *   0: e                                   the first step's provisional DDIM update (plms.py:221)
+ *   1: (h1 + e)/2                          the first step's final update: h1 = its first evaluation, e = the second (:223)
+ *   2: (3e - h1)/2    3: (23e - 16h1 + 5h2)/12    4: (55e - 59h1 + 37h2 - 9h3)/24      (:226-232)
+ * then x0 = (x - sqrt(1-a_t) e')/sqrt(a_t), x' = sqrt(a_prev) x0 + sqrt(1-a_prev-sigma^2) e' from coef row `index`.
+ * Order k reads h1 for k >= 1, h2 for k >= 3, h3 for k == 4 and no other history pointer (NULL is allowed there; a slot that is
+ * not read may hold anything, NaN included).  e_out (NULL: not written) receives e -- not e' (plms.py:160) -- for every order but
+ * 1.  x may alias x_prev, and e_out may alias h1, h2 or h3: every thread reads its element before it writes it. */
+int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                       float scale, const float* coef, int32_t index, int32_t order, const float* x, const float* h1,
+                       const float* h2, const float* h3, float* x_prev, float* pred_x0, float* e_out, void* stream);
+
+/* The same update for a step captured whole in one hipGraph (seer_ddim_step_begin -> UNet -> this kernel): index = step[1], then
+ * step[0] = index - 1, as seer_cfg_ddim_step_dev.  The history is a ring of three slots, ring fp32 [3][b*C*F_pred*HW].
+ * ring_state int32[4] = (valid, newest) for even indices, then (valid, newest) for odd ones: a step reads the pair of its own
+ * index's parity -- valid in 0..3 earlier e, h1 = slot newest, h2 = slot (newest+2)%3, h3 = slot (newest+1)%3 -- runs order 0
+ * for valid = 0 and order valid+1 otherwise, stores e into slot s = (newest+1)%3 (the oldest slot once all three are valid), and
+ * one thread writes (min(valid+1, 3), s) into the pair of parity (index-1).  No kernel reads and writes the same word, so replays
+ * walk the schedule and the ring with no host-written scalars; the host writes step[0] and the pair of the first index to start
+ * a chain.  A pair outside those ranges is read as (0, 2).  x may alias x_prev. */
+int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                           float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state, const float* x,
+                           float* x_prev, float* pred_x0, void* stream);
+
 /* decoded image post-process of ddim_sample (utils/ddim_sampling_utils.py:41): clamp((x+1)/2, 0, 1) in place */
 int seer_clamp01(float* x, int64_t n, void* stream);
 

@@ -7,7 +7,8 @@ Importing the package never touches the GPU; the HIP library is loaded on first 
 """
 from .ddim import DDIMSampler, ddim_sample  # noqa: F401
 from .fstext import FSTextTransformer  # noqa: F401
+from .plms import PLMSSampler  # noqa: F401
 from .unet import SeerUNet  # noqa: F401
 from .vae import AutoencoderKL  # noqa: F401
 
-__all__ = ["SeerUNet", "DDIMSampler", "ddim_sample", "AutoencoderKL", "FSTextTransformer"]
+__all__ = ["SeerUNet", "DDIMSampler", "PLMSSampler", "ddim_sample", "AutoencoderKL", "FSTextTransformer"]

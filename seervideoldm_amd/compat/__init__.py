@@ -17,6 +17,8 @@ presented as namespace packages over the directories found on `sys.path`.
 runs the script with the aliases installed (`sys.argv`, `sys.path[0]` and `__main__` as `python script.py` sets them).
 `install(vae=True)` (or `SEER_COMPAT_VAE=1` with the runner) also replaces `diffusers.AutoencoderKL` by the product's VAE
 when `diffusers` is importable; without it the reference keeps its fp32 torch VAE for `vae.decode` / `vae.encode`.
+`SEER_COMPAT_SAMPLER=plms` (read by `install()`) makes the scripts sample with `PLMSSampler` under the name `DDIMSampler`: the
+yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluations).
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import importlib.machinery
 import os
 import sys
 import types
+from typing import Optional
 
 ALIASES = {
     "seer.models.unet_3d_condition": "seervideoldm_amd.compat._unet_3d_condition",
@@ -48,6 +51,9 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
             mod = types.ModuleType(spec.name, src.__doc__)
             mod.__dict__.update({k: v for k, v in src.__dict__.items() if not k.startswith("__")})
             mod.__all__ = list(getattr(src, "__all__", []))
+            if spec.name == "ldm.models.diffusion.ddim_video" and _sampler == "plms":
+                from seervideoldm_amd.plms import PLMSSampler
+                mod.DDIMSampler = PLMSSampler
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -65,9 +71,14 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
 
 _finder = _AliasFinder()
+_sampler = None
 
 
-def install(vae: bool = False) -> None:
+def install(vae: bool = False, sampler: Optional[str] = None) -> None:
+    """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
+    `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler; anything else keeps DDIMSampler"""
+    global _sampler
+    _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
     if _finder not in sys.meta_path:
         sys.meta_path.insert(0, _finder)
     for name in list(ALIASES) + _PARENTS:      # modules imported before install() (the reference's own) give way

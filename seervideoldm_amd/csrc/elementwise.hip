@@ -1,5 +1,5 @@
 // Small / boundary kernels of the Seer hot path on gfx950: rotary embedding, timestep embedding, small-M linear,
-// conv_in / conv_out (layout change fused), casts, CFG + DDIM update.
+// conv_in / conv_out (layout change fused), casts, CFG + DDIM / PLMS update.
 #include "seer_common.h"
 #include <atomic>
 
@@ -384,6 +384,86 @@ __global__ void cfg_ddim_dev_kernel(const float* __restrict__ eps, int cfg, int 
     if (pred_x0) pred_x0[i] = x0;
 }
 
+// ---- CFG + PLMS update (ldm/models/diffusion/plms.py:199-236, eta = 0; fp32, one thread per latent element) -----------------
+// e = the CFG-combined eps of this evaluation; h1, h2, h3 = earlier e, newest first.  e' by order:
+//   0: e (the first step's provisional DDIM update)   1: (h1 + e)/2 (the first step's final update: h1 = first evaluation, e = second)
+//   2: (3e - h1)/2   3: (23e - 16h1 + 5h2)/12   4: (55e - 59h1 + 37h2 - 9h3)/24
+// then the DDIM update with e' from coefficient row `index`.  A history term the order does not use is never read (stale slots may
+// hold NaN, and 0 * NaN is NaN).  e_out (may alias a history slot: every thread reads its element before it writes it) receives e,
+// not e' (plms.py:160), for every order but 1, whose e is the second evaluation that plms.py does not keep.
+__device__ __forceinline__ float cfg_eps_at(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW,
+                                            float scale, int64_t i) {
+    const int Fp = Ft - cond_f;
+    const int hw = (int)(i % HW);
+    const int f = (int)((i / HW) % Fp);
+    const int c = (int)((i / ((int64_t)HW * Fp)) % C);
+    const int bi = (int)(i / ((int64_t)HW * Fp * C));
+    const int64_t eoff = (((int64_t)bi * C + c) * Ft + (f + cond_f)) * HW + hw;
+    if (!cfg) return eps[eoff];
+    const float eu = eps[eoff];
+    const float ec = eps[eoff + (int64_t)b * C * Ft * HW];
+    return eu + scale * (ec - eu);
+}
+
+__device__ __forceinline__ void plms_update(float e, int order, const float* h1, const float* h2, const float* h3, int64_t i,
+                                            const float* __restrict__ coef, int index, const float* x, float* x_prev,
+                                            float* __restrict__ pred_x0, float* e_out) {
+    float ep;
+    switch (order) {
+        case 0: ep = e; break;
+        case 1: ep = (h1[i] + e) / 2.f; break;
+        case 2: ep = (3.f * e - h1[i]) / 2.f; break;
+        case 3: ep = (23.f * e - 16.f * h1[i] + 5.f * h2[i]) / 12.f; break;
+        default: ep = (55.f * e - 59.f * h1[i] + 37.f * h2[i] - 9.f * h3[i]) / 24.f; break;
+    }
+    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], sigma = coef[4 * index + 2], s1m = coef[4 * index + 3];
+    const float xv = x[i];
+    const float x0 = (xv - s1m * ep) / sqrtf(a_t);
+    const float dir = sqrtf(1.f - a_prev - sigma * sigma) * ep;
+    x_prev[i] = sqrtf(a_prev) * x0 + dir;
+    if (pred_x0) pred_x0[i] = x0;
+    if (e_out && order != 1) e_out[i] = e;
+}
+
+__global__ void cfg_plms_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
+                                const float* __restrict__ coef, int index, int order, const float* x, const float* h1,
+                                const float* h2, const float* h3, float* x_prev, float* __restrict__ pred_x0, float* e_out) {
+    const int64_t n = (int64_t)b * C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    plms_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), order, h1, h2, h3, i, coef, index, x, x_prev, pred_x0,
+                e_out);
+}
+
+// The captured form: the index is step[1] (seer_ddim_step_begin copied it there) and the history is a 3-slot ring of [n] fp32
+// slots.  ring_state int32[4] holds (valid, newest) twice, by parity of the index: a step reads pair (index & 1) and one thread
+// writes pair ((index - 1) & 1) = (min(valid + 1, 3), slot) with slot = (newest + 1) % 3, the slot this step stores e into (the
+// oldest one once all three are valid); it also writes step[0] = index - 1.  No kernel reads and writes the same word.
+// valid = 0 is a plain DDIM step (order 0), valid = k > 0 is order k + 1.
+__global__ void cfg_plms_dev_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
+                                    const float* __restrict__ coef, int* __restrict__ step, float* ring,
+                                    int* __restrict__ ring_state, const float* x, float* x_prev, float* __restrict__ pred_x0) {
+    const int64_t n = (int64_t)b * C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int index = step[1];
+    const int* rs = ring_state + 2 * (index & 1);
+    int valid = rs[0], newest = rs[1];
+    if (valid < 0 || valid > 3 || newest < 0 || newest > 2) valid = 0, newest = 2;     // never index outside the ring
+    const int slot = newest == 2 ? 0 : newest + 1;
+    if (i == 0) {
+        step[0] = index - 1;
+        int* ws = ring_state + 2 * ((index - 1) & 1);
+        ws[0] = valid < 3 ? valid + 1 : 3;
+        ws[1] = slot;
+    }
+    if (i >= n) return;
+    const float* h1 = ring + (int64_t)newest * n;
+    const float* h2 = ring + (int64_t)(newest == 0 ? 2 : newest - 1) * n;
+    const float* h3 = ring + (int64_t)slot * n;
+    plms_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), valid == 0 ? 0 : valid + 1, h1, h2, h3, i, coef, index,
+                x, x_prev, pred_x0, ring + (int64_t)slot * n);
+}
+
 // pointwise channel mix on NCHW fp32 (VAE post_quant_conv, 4 -> 4): y[n,co,p] = sum_ci W[co,ci] x[n,ci,p] + b[co]
 __global__ void conv1x1_nchw_kernel(const float* __restrict__ x, int N, int Cin, int Cout, int HW,
                                     const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ y) {
@@ -626,6 +706,33 @@ extern "C" int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, 
     return SEER_OK;
 }
 
+extern "C" int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                  int32_t HW, float scale, const float* coef, int32_t index, int32_t order, const float* x,
+                                  const float* h1, const float* h2, const float* h3, float* x_prev, float* pred_x0, float* e_out,
+                                  void* stream) {
+    if (!eps || !coef || !x || !x_prev || b <= 0 || C <= 0 || F_total <= cond_f || cond_f < 0 || HW <= 0 || index < 0 ||
+        order < 0 || order > 4 || (order >= 1 && !h1) || (order >= 3 && !h2) || (order >= 4 && !h3))
+        return SEER_EINVAL;
+    const int64_t n = (int64_t)b * C * (F_total - cond_f) * HW;
+    hipLaunchKernelGGL(cfg_plms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, cfg, b, C, F_total,
+                       cond_f, HW, scale, coef, index, order, x, h1, h2, h3, x_prev, pred_x0, e_out);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                      int32_t HW, float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state,
+                                      const float* x, float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !coef || !step || !ring || !ring_state || !x || !x_prev || b <= 0 || C <= 0 || F_total <= cond_f || cond_f < 0 ||
+        HW <= 0)
+        return SEER_EINVAL;
+    const int64_t n = (int64_t)b * C * (F_total - cond_f) * HW;
+    hipLaunchKernelGGL(cfg_plms_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, cfg, b, C, F_total,
+                       cond_f, HW, scale, coef, step, ring, ring_state, x, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
 extern "C" int seer_conv1x1_nchw_f32(const float* x, int32_t N, int32_t Cin, int32_t Cout, int32_t HW, const float* Wt,
                                      const float* bias, float* y, void* stream) {
     if (!x || !Wt || !y || N <= 0 || Cin <= 0 || Cout <= 0 || HW <= 0) return SEER_EINVAL;
@@ -653,7 +760,7 @@ extern "C" int seer_gaussian_sample(const float* moments, int32_t N, int32_t C, 
     return SEER_OK;
 }
 
-extern "C" int seer_abi_version(void) { return 24; }
+extern "C" int seer_abi_version(void) { return 25; }
 extern "C" const char* seer_build_arch(void) { return "gfx950"; }
 extern "C" const char* seer_strerror(int code) {
     switch (code) {

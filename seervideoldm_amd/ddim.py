@@ -148,8 +148,6 @@ class DDIMSampler(object):
         """ddim_video.py:183-238."""
         if use_original_steps or noise_dropout > 0. or repeat_noise:
             raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
-        b = x.shape[0]
-        cond_f = 0
         x = x.to(torch.float32).contiguous()
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         sigma = float(self.ddim_sigmas[index])
@@ -162,6 +160,21 @@ class DDIMSampler(object):
             done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale)
             if done is not None:
                 return done
+        eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        noise = None
+        if sigma != 0. or self.consume_rng_when_deterministic:
+            noise = torch.randn(x.shape, device=x.device) * temperature
+            if sigma != 0.:
+                noise = _from_rank0(unet, noise)
+        x_prev, pred_x0 = ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale,
+                                            cond_f=cond_f, noise=noise if sigma != 0. else None)
+        return x_prev, pred_x0
+
+    def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale):
+        """the model call of p_sample_ddim (ddim_video.py:187-207): x0_emb in front of x along frames, batched CFG when uc has c's
+        frame count, two calls otherwise.  Returns (eps [2b or b, C, cond_f + F, h, w], cfg, cond_f): the CFG combine and the
+        slicing off of the conditioning frames are the update kernel's."""
+        cond_f = 0
         x_cat = x
         if x0_emb is not None:
             cond_f = x0_emb.shape[2]
@@ -183,15 +196,7 @@ class DDIMSampler(object):
             e_c = unet(x_cat, t, c, cond_frame=cond_frames)
             eps = torch.cat([e_uc, e_c])
             cfg = True
-        noise = None
-        if sigma != 0. or self.consume_rng_when_deterministic:
-            noise = torch.randn(x.shape, device=x.device) * temperature
-            if sigma != 0.:
-                noise = _from_rank0(unet, noise)
-        x_prev, pred_x0 = ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale,
-                                            cond_f=cond_f, noise=noise if sigma != 0. else None)
-        return x_prev, pred_x0
-
+        return eps, cfg, cond_f
 
     # ---- the captured step -----------------------------------------------------------------------------------------
     def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale):
@@ -199,6 +204,38 @@ class DDIMSampler(object):
         no torch kernel between two UNet evaluations except the reference's per-step RNG draw, no host-written scalars -- the
         schedule index lives in device memory and the captured step counts it down itself.  Returns None when this step cannot
         take the path (sharded model, capture refused): the caller then runs the launches one by one."""
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale)
+        if G is None:
+            return None
+        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
+            G["x"].copy_(x)
+        if G["expect"] != index:
+            G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
+        return self._replay_step(G, x, index)
+
+    def _replay_step(self, G, x, index):
+        if self.consume_rng_when_deterministic:
+            torch.randn(x.shape, device=x.device)   # ddim_video.py:234 draws every step, also at sigma = 0: keep the RNG stream
+        G["graph"].replay()
+        G["expect"] = index - 1
+        if self.static_step_outputs:
+            return G["x"], G["pred"]
+        return G["x"].clone(), G["pred"].clone()
+
+    # what a subclass changes in the captured step: the first word of its graph-cache key, the static buffers beyond the DDIM
+    # step's, and the step's last kernel
+    _GRAPH_KIND = "step"
+
+    def _graph_buffers(self, x):
+        return {}
+
+    def _graph_update(self, G, eps, cfg, scale, cond_f):
+        ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], cfg=cfg, scale=scale, cond_f=cond_f, x_prev=G["x"],
+                              pred_x0=G["pred"])
+
+    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale):
+        """the captured step of this shape / CFG / scale (captured on first use) with its read-by-address inputs refreshed; None
+        when the step cannot be captured"""
         from .unet import SeerUNet
         if not isinstance(unet, SeerUNet) or unet._shard is not None or unet._ops_backend is not ops \
                 or unet.config.center_input_sample or getattr(self, "_step_graph_broken", False):
@@ -226,7 +263,7 @@ class DDIMSampler(object):
             return None
         ctx, L = eng._context(context)          # new prompt: the static context / K|V buffers are refreshed in place
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
-        key = ("step", (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape))
+        key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape))
         G = eng.graph_get(key)
         if G is None:
             G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L)
@@ -249,17 +286,7 @@ class DDIMSampler(object):
             G["ttab"][:n].copy_(self._t_table)
             G["sched_key"], G["sched_ref"] = ksch, (self.ddim_coef, self._t_table)
             G["expect"] = None
-        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
-            G["x"].copy_(x)
-        if G["expect"] != index:
-            G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
-        if self.consume_rng_when_deterministic:
-            torch.randn(x.shape, device=x.device)   # ddim_video.py:234 draws every step, also at sigma = 0: keep the RNG stream
-        G["graph"].replay()
-        G["expect"] = index - 1
-        if self.static_step_outputs:
-            return G["x"], G["pred"]
-        return G["x"].clone(), G["pred"].clone()
+        return G
 
     def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L):
         dev = x.device
@@ -272,7 +299,7 @@ class DDIMSampler(object):
                  t=torch.empty((reps * b,), device=dev, dtype=torch.long), step=torch.zeros((2,), device=dev, dtype=torch.int32),
                  coef=torch.zeros((nsched, 4), device=dev, dtype=torch.float32),
                  ttab=torch.zeros((nsched,), device=dev, dtype=torch.long), sched_key=None, sched_ref=(None, None), x0_ref=None,
-                 expect=None)
+                 expect=None, **self._graph_buffers(x))
         G["coef"][:, 0] = 1.0                        # a_t = 1 in the unused rows: the warm-up below must stay finite
         G["x"].copy_(x)
         if x0_emb is not None:
@@ -281,8 +308,7 @@ class DDIMSampler(object):
         def body():
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
-            ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], cfg=cfg, scale=scale, cond_f=f1, x_prev=G["x"],
-                                  pred_x0=G["pred"])
+            self._graph_update(G, eps, cfg, scale, f1)
         try:
             body()                                   # warm-up: K|V / rotary caches, allocations
             torch.cuda.synchronize()

@@ -950,6 +950,59 @@ def cfg_ddim_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, st
                                              _p(noise), _p(x_prev), _p(pred_x0), _stream()), "seer_cfg_ddim_step_dev")
 
 
+def cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, order: int, *, cfg: bool, scale: float,
+                  cond_f: int, history=(), x_prev: Optional[torch.Tensor] = None, pred_x0: Optional[torch.Tensor] = None,
+                  e_out: Optional[torch.Tensor] = None, want_pred_x0=True, want_e=True):
+    """eps [2b or b, C, F_total, h, w] fp32 ; x [b, C, F_pred, h, w] fp32 ; history = earlier e, newest first (order 1, 2: one,
+    3: two, 4: three) -> (x_prev, pred_x0, e).  e is this evaluation's CFG-combined eps (None for order 1, which keeps none);
+    x_prev may be x and e_out a history tensor (include/seer_hip.h, seer_cfg_plms_step)."""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
+    assert eps.is_contiguous() and x.is_contiguous()
+    b, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
+    order = int(order)
+    need = (0, 1, 1, 2, 3)[order] if 0 <= order <= 4 else None
+    assert need is not None, f"order {order}: 0..4"
+    history = list(history)
+    assert need <= len(history) <= 3, f"order {order} needs {need} earlier eps (at most 3), got {len(history)}"
+    for hh in history:
+        _req(hh, torch.float32, "history")
+        assert hh.is_contiguous() and hh.shape == x.shape
+    # every history tensor given is passed on: the kernel reads only those its order uses
+    hp = [_p(hh) for hh in history] + [None] * (3 - len(history))
+    x_prev = torch.empty_like(x) if x_prev is None else x_prev
+    pred = (torch.empty_like(x) if want_pred_x0 else None) if pred_x0 is None else pred_x0
+    e = (torch.empty_like(x) if want_e and order != 1 else None) if e_out is None else e_out
+    for name, tt in (("x_prev", x_prev), ("pred_x0", pred), ("e_out", e)):
+        if tt is not None:
+            _req(tt, torch.float32, name)
+            assert tt.is_contiguous() and tt.shape == x.shape
+    check(_lib.load().seer_cfg_plms_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), int(index), order,
+                                         _p(x), hp[0], hp[1], hp[2], _p(x_prev), _p(pred), _p(e), _stream()), "seer_cfg_plms_step")
+    return x_prev, pred, (None if order == 1 else e)
+
+
+def cfg_plms_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, ring: torch.Tensor,
+                      ring_state: torch.Tensor, *, cfg: bool, scale: float, cond_f: int, x_prev: torch.Tensor,
+                      pred_x0: Optional[torch.Tensor]) -> None:
+    """last kernel of a captured PLMS step: cfg_plms_step with index = step[1] and the order / history taken from the 3-slot ring
+    (ring [3, *x.shape], ring_state int32[4]: (valid, newest) per index parity); step[0] = index - 1; x_prev may be x"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    _req(ring, torch.float32, "ring"); _req(ring_state, torch.int32, "ring_state")
+    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
+    assert ring.is_contiguous() and tuple(ring.shape) == (3, *x.shape) and ring_state.numel() >= 4 and step.numel() >= 2
+    if pred_x0 is not None:
+        _req(pred_x0, torch.float32, "pred_x0")
+        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
+    b, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
+    check(_lib.load().seer_cfg_plms_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), _p(step),
+                                             _p(ring), _p(ring_state), _p(x), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_cfg_plms_step_dev")
+
+
 def clamp01_(x: torch.Tensor) -> torch.Tensor:
     _req(x, torch.float32, "x")
     assert x.is_contiguous()

@@ -1,0 +1,194 @@
+"""PLMSSampler -- pseudo linear multistep sampling (ldm/models/diffusion/plms.py, the PNDM paper's PLMS) on the Seer model call.
+
+The update is the reference's p_sample_plms: the first step evaluates twice (a provisional DDIM step to t_next, then the mean of
+the two eps: improved Euler), every later step once, combining its eps with the last one, two or three earlier ones by the
+Adams-Bashforth weights.  The model call is Seer's (ddim_video.py:187-207, DDIMSampler._model_output): x0_emb in front of the
+latent along frames, batched or unbatched CFG by uc's frame count, cond_frame.  The reference's PLMSSampler drives a 4-D
+`model.apply_model` and cannot run a SeerUNet.
+
+Same constructor, `sample(...)` keywords and return values as DDIMSampler, so ddim_sample, pipeline.generate_clips and
+pipeline.evaluate_batch take either sampler.  The schedule IS DDIMSampler.make_schedule (same tables, same 'uniform' stride).
+
+Kernels: CFG combine + PLMS combination + DDIM update are one fused HIP kernel (seer_cfg_plms_step; include/seer_hip.h).  With
+`unet.use_graph` on an unsharded SeerUNet every step after the first is ONE hipGraph replay -- seer_ddim_step_begin, the UNet,
+seer_cfg_plms_step_dev -- captured once per shape / CFG / scale key by DDIMSampler's capture machinery; the eps history is a
+3-slot ring in the graph's static buffers and the kernel walks it itself, so a chain of replays needs no host-written scalar.
+The first step (two evaluations) runs launch by launch: a second captured graph would hold a second full set of step
+activations in the engine's small graph cache for one step per sample.
+
+The reference draws noise_like(x.shape) in every get_x_prev_and_pred_x0 call, also at sigma = 0 -- twice on the first step, once
+on every later one (plms.py:212); those draws are kept (consume_rng_when_deterministic) so a seeded run leaves the device RNG
+stream where the reference leaves it.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .ddim import DDIMSampler, _from_rank0
+
+
+class PLMSSampler(DDIMSampler):
+    _GRAPH_KIND = "plms"
+
+    def make_schedule(self, ddim_num_steps, *args, ddim_eta=0., **kwargs):
+        """DDIMSampler.make_schedule; PLMS is deterministic only (plms.py:25-26)"""
+        if ddim_eta != 0:
+            raise ValueError("ddim_eta must be 0 for PLMS")
+        super().make_schedule(ddim_num_steps, *args, ddim_eta=ddim_eta, **kwargs)
+
+    @torch.no_grad()
+    def sample(self, unet, S, batch_size, shape, x0_emb=None, conditioning=None, callback=None, normals_sequence=None,
+               img_callback=None, eta=0., mask=None, x0=None, cond_frames=0, temperature=1., noise_dropout=0.,
+               score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
+               unconditional_guidance_scale=1., unconditional_conditioning=None, null_cond_prob=None, is_3d=False,
+               **kwargs):
+        if conditioning is not None and not isinstance(conditioning, dict):
+            if conditioning.shape[0] != batch_size:
+                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        if is_3d:
+            C, Fr, H, W = shape
+            size = (batch_size, C, Fr, H, W)
+        else:
+            raise NotImplementedError("the Seer hot path is 5-D (is_3d=True, ddim_sampling_utils.py:36)")
+        if noise_dropout > 0.:
+            raise NotImplementedError("noise_dropout: only the deterministic PLMS path is built")
+        return self.plms_sampling(unet, conditioning, size, x0_emb=x0_emb, is_3d=is_3d, callback=callback,
+                                  img_callback=img_callback, cond_frames=cond_frames, temperature=temperature, x_T=x_T,
+                                  log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning)
+
+    @torch.no_grad()
+    def plms_sampling(self, unet, cond, shape, is_3d=True, x0_emb=None, cond_frames=0, x_T=None, callback=None,
+                      img_callback=None, log_every_t=100, temperature=1., unconditional_guidance_scale=1.,
+                      unconditional_conditioning=None, **kwargs):
+        """plms.py:114-170 over the Seer model call"""
+        device = self.device
+        b = shape[0]
+        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
+        # a clip sharded over several ranks (parallel.attach): every rank runs the same update on rank 0's inputs
+        img = _from_rank0(unet, img)
+        if x0_emb is not None:
+            x0_emb = _from_rank0(unet, x0_emb.to(device))
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        total_steps = self.ddim_timesteps.shape[0]
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
+        graph = (getattr(unet, "use_graph", False) and img.is_cuda
+                 and (uc is None or scale == 1. or uc.shape[2] == cond.shape[2]))
+        from .unet import SeerUNet
+        # the first step of a captured chain runs its two evaluations launch by launch, not as a UNet graph of their own
+        first_eager = graph and isinstance(unet, SeerUNet) and unet._shard is None
+        old_eps = []
+        chained = False
+        static_before, self.static_step_outputs = self.static_step_outputs, True
+        try:
+            for i in range(total_steps):
+                index = total_steps - i - 1
+                out = None
+                if graph and i > 0:
+                    plain = uc is None or scale == 1.
+                    out = self._plms_graph_step(unet, img, cond, None if plain else uc, index, x0_emb,
+                                                0 if plain else cond_frames, scale, old_eps, restart=not chained)
+                chained = out is not None
+                if out is None:
+                    if i == 0 and first_eager:
+                        unet.use_graph = False
+                    try:
+                        # t_next = time_range[min(i + 1, n - 1)] (plms.py:145)
+                        out = self.p_sample_plms(unet, img, cond, self._t_table[index].expand(b), index, x0_emb=x0_emb,
+                                                 cond_frames=cond_frames, temperature=temperature,
+                                                 unconditional_guidance_scale=scale, unconditional_conditioning=uc,
+                                                 old_eps=old_eps, t_next=self._t_table[max(index - 1, 0)].expand(b))
+                    finally:
+                        if i == 0 and first_eager:
+                            unet.use_graph = True
+                img, pred_x0, e_t = out
+                old_eps.append(e_t)
+                if len(old_eps) >= 4:
+                    old_eps.pop(0)
+                if callback:
+                    callback(i)
+                if img_callback:
+                    img_callback(pred_x0.clone(), i)
+                if index % log_every_t == 0 or index == total_steps - 1:
+                    intermediates["x_inter"].append(img.clone())
+                    intermediates["pred_x0"].append(pred_x0.clone())
+        finally:
+            self.static_step_outputs = static_before
+        return img.clone(), intermediates
+
+    @torch.no_grad()
+    def p_sample_plms(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
+                      use_original_steps=False, quantize_denoised=False, temperature=1., noise_dropout=0.,
+                      score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
+                      unconditional_conditioning=None, old_eps=None, t_next=None):
+        """plms.py:172-236 -> (x_prev, pred_x0, e_t); e_t is this step's (first) CFG-combined eps, the one old_eps keeps.
+        Launch by launch (seer_cfg_plms_step)."""
+        if use_original_steps or noise_dropout > 0. or repeat_noise or quantize_denoised or score_corrector is not None:
+            raise NotImplementedError("only the deterministic PLMS path over the DDIM subsequence is built")
+        x = x.to(torch.float32).contiguous()
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        old_eps = [] if old_eps is None else old_eps
+        history = [e.to(torch.float32).contiguous() for e in reversed(old_eps[-3:])]       # newest first
+        eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        kw = dict(cfg=cfg, scale=scale, cond_f=cond_f)
+        if not history:
+            # pseudo improved Euler: a provisional DDIM step to t_next, a second evaluation there, the mean of the two eps
+            if t_next is None:
+                raise ValueError("the first PLMS step (old_eps empty) needs t_next")
+            self._consume_rng(x)
+            x_prov, _, e_t = ops.cfg_plms_step(eps.float().contiguous(), x, self.ddim_coef, index, 0, want_pred_x0=False, **kw)
+            eps2, _, _ = self._model_output(unet, x_prov, c, t_next, x0_emb, cond_frames, uc, scale)
+            self._consume_rng(x)
+            x_prev, pred_x0, _ = ops.cfg_plms_step(eps2.float().contiguous(), x, self.ddim_coef, index, 1, history=[e_t], **kw)
+        else:
+            self._consume_rng(x)
+            x_prev, pred_x0, e_t = ops.cfg_plms_step(eps.float().contiguous(), x, self.ddim_coef, index, len(history) + 1,
+                                                     history=history, **kw)
+        return x_prev, pred_x0, e_t
+
+    def _consume_rng(self, x):
+        if self.consume_rng_when_deterministic:
+            torch.randn(x.shape, device=x.device)    # plms.py:212 draws in every update, also at sigma = 0
+
+    def p_sample_ddim(self, *args, **kwargs):
+        raise NotImplementedError("PLMSSampler steps with p_sample_plms")
+
+    def ddim_sampling(self, *args, **kwargs):
+        raise NotImplementedError("PLMSSampler samples with plms_sampling")
+
+    # ---- the captured step: DDIMSampler's graph with a 3-slot eps ring and seer_cfg_plms_step_dev as its last kernel --------
+    def _graph_buffers(self, x):
+        return dict(ring=torch.zeros((3, *x.shape), device=x.device, dtype=torch.float32),
+                    ring_state=torch.zeros((4,), device=x.device, dtype=torch.int32), ring_host=None)
+
+    def _graph_update(self, G, eps, cfg, scale, cond_f):
+        ops.cfg_plms_step_dev(eps, G["x"], G["coef"], G["step"], G["ring"], G["ring_state"], cfg=cfg, scale=scale, cond_f=cond_f,
+                              x_prev=G["x"], pred_x0=G["pred"])
+
+    def _plms_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, old_eps, restart):
+        """one later PLMS step as a single replay; `restart` (or a chain the graph did not run last) seeds the ring from old_eps and
+        writes the step index and the ring state of that index: the only host writes of a chain.  Returns None when the step
+        cannot be captured."""
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale)
+        if G is None:
+            return None
+        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
+            G["x"].copy_(x)
+        if restart or G["expect"] != index or G["ring_host"] is None:
+            hist = list(reversed(old_eps[-3:]))                         # newest first -> slots 0, 2, 1
+            if hist:
+                src = torch.stack([e.to(torch.float32) for e in hist])   # a copy: old_eps may be views of this very ring
+                for k in range(len(hist)):
+                    G["ring"][(3 - k) % 3].copy_(src[k])
+            G["step"][:1].fill_(int(index))
+            p = 2 * (int(index) & 1)
+            G["ring_state"][p:p + 2].copy_(torch.tensor([len(hist), 0], dtype=torch.int32))
+            G["ring_host"] = (len(hist), 0)
+        valid, newest = G["ring_host"]
+        slot = (newest + 1) % 3
+        x_prev, pred_x0 = self._replay_step(G, x, index)
+        G["ring_host"] = (min(valid + 1, 3), slot)
+        e_t = G["ring"][slot]
+        return x_prev, pred_x0, (e_t if self.static_step_outputs else e_t.clone())
