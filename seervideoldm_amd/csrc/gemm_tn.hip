@@ -10,7 +10,6 @@
 #include "seer_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace {
@@ -261,17 +260,12 @@ extern "C" int seer_gemm_tn_f32(const void* A, int32_t lda, const void* B, int32
 namespace {
 
 // rows of contraction one workgroup of a grouped launch takes (the group fills the chip by its number of problems, so a problem is
-// split only to bound the longest workgroup, not to make workgroups)
-int tn_group_rows() {
-    static const int rows = [] {
-        const char* e = getenv("SEER_TN_GROUP_ROWS");
-        const int v = e ? atoi(e) : 0;
-        return v >= TM ? (v + TM - 1) / TM * TM : 16384;
-    }();
-    return rows;
+// split only to bound the longest workgroup, not to make workgroups): seer_tn_item::group_rows rounded up to the tile height,
+// 0 (or less than a tile) = 16384
+int tn_group_splits(const seer_tn_item& it) {
+    const int rows = it.group_rows >= TM ? (it.group_rows + TM - 1) / TM * TM : 16384;
+    return (it.M + rows - 1) / rows;
 }
-
-int tn_group_splits(int M) { return (M + tn_group_rows() - 1) / tn_group_rows(); }
 
 bool tn_item_ok(const seer_tn_item& it) {
     if (!it.A || !it.B || !it.C || it.M <= 0 || it.N <= 0 || it.K <= 0) return false;
@@ -287,7 +281,7 @@ extern "C" int64_t seer_gemm_tn_grouped_workspace_bytes(const seer_tn_item* item
     int64_t floats = 0;
     for (int i = 0; i < n_items; ++i) {
         if (!tn_item_ok(items[i])) return SEER_EINVAL;
-        const int s = tn_group_splits(items[i].M);
+        const int s = tn_group_splits(items[i]);
         if (s > 1) floats += (int64_t)s * ((int64_t)items[i].N * items[i].K + items[i].N);
     }
     return floats * (int64_t)sizeof(float);
@@ -304,7 +298,7 @@ extern "C" int seer_gemm_tn_grouped_f32(const seer_tn_item* items, int32_t n_ite
     std::vector<int> order(n_items);
     for (int i = 0; i < n_items; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        const int sa = tn_group_splits(items[a].M), sb = tn_group_splits(items[b].M);
+        const int sa = tn_group_splits(items[a]), sb = tn_group_splits(items[b]);
         return (items[a].M + sa - 1) / sa > (items[b].M + sb - 1) / sb;
     });
     float* ws = reinterpret_cast<float*>(workspace);
@@ -317,7 +311,7 @@ extern "C" int seer_gemm_tn_grouped_f32(const seer_tn_item* items, int32_t n_ite
         for (int j = 0; j < n; ++j) {
             const seer_tn_item& it = items[order[base + j]];
             TnProb& q = g.p[j];
-            int s = tn_group_splits(it.M);
+            int s = tn_group_splits(it);
             q.m_chunk = ((it.M + s - 1) / s + TM - 1) / TM * TM;
             s = (it.M + q.m_chunk - 1) / q.m_chunk;
             const int64_t slice = (int64_t)it.N * it.K + it.N;
@@ -338,7 +332,7 @@ extern "C" int seer_gemm_tn_grouped_f32(const seer_tn_item* items, int32_t n_ite
                 r.count4 = it.colsum ? slice / 4 : r.nk4;
                 r.blk0 = blk;
                 blk += (int)((r.count4 + 255) / 256);
-                ws += (int64_t)tn_group_splits(it.M) * slice;        // the layout seer_gemm_tn_grouped_workspace_bytes sized
+                ws += (int64_t)tn_group_splits(it) * slice;        // the layout seer_gemm_tn_grouped_workspace_bytes sized
             } else {
                 q.dst = it.C;
                 q.cdst = it.colsum;

@@ -68,7 +68,7 @@ class FrameShard:
 
     @property
     def exact_stats(self) -> bool:
-        """does every GroupNorm of this engine need exact integer statistics (unet._Engine._gn)?  Only frame shards exchange
+        """does every GroupNorm of this engine need exact integer statistics (groupnorm.groupnorm)?  Only frame shards exchange
         anything: with batch groups alone (a CFG half per rank, P == 1) the engine keeps the single-process forms -- no extra
         pass over the activations, nothing to add up across ranks.  The one-rank references of the bit-identity tests ask for the
         sharded arithmetic explicitly."""

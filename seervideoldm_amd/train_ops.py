@@ -7,6 +7,7 @@ path.  The matrix products of the backward pass are plain ops.gemm / ops.conv3x3
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Sequence, Optional, Tuple
 
 import torch
@@ -69,6 +70,17 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None
     return out
 
 
+def tn_items(problems):
+    """the host table of seer_gemm_tn_grouped_f32 for `problems` (checked by the caller: gemm_tn_grouped).  SEER_TN_GROUP_ROWS=<rows>
+    (A/B runs): the contraction rows one workgroup takes, in every item's group_rows; unset = 0 = the library's 16384"""
+    group_rows = int(os.environ.get("SEER_TN_GROUP_ROWS") or 0)
+    items = (_lib.TnItem * len(problems))()
+    for it, (a, b, out, colsum) in zip(items, problems):
+        it.A, it.B, it.C, it.colsum = a.data_ptr(), b.data_ptr(), out.data_ptr(), None if colsum is None else colsum.data_ptr()
+        it.lda, it.ldb, it.M, it.N, it.K, it.group_rows = a.stride(0), b.stride(0), a.shape[0], a.shape[1], b.shape[1], group_rows
+    return items
+
+
 def gemm_tn_grouped(problems) -> None:
     """problems: [(a [M, N], b [M, K], out [N, K] fp32, colsum [N] fp32 or None), ...] -- out_i = a_i^T @ b_i (and colsum_i = the column
     sums of a_i) for all of them in ONE launch (+ one for the K slices of the long ones): the deferred weight gradients of a backward
@@ -76,18 +88,14 @@ def gemm_tn_grouped(problems) -> None:
     if not problems:
         return
     lib = _lib.load()
-    items = (_lib.TnItem * len(problems))()
-    for it, (a, b, out, colsum) in zip(items, problems):
+    for a, b, out, colsum in problems:
         _req(a, bf16, "a"); _req(b, bf16, "b"); _req(out, torch.float32, "out")
         assert a.dim() == 2 and b.dim() == 2 and a.shape[0] == b.shape[0] and a.stride(1) == 1 and b.stride(1) == 1
-        M, N = a.shape
-        K = b.shape[1]
-        assert out.shape == (N, K) and out.is_contiguous()
+        assert out.shape == (a.shape[1], b.shape[1]) and out.is_contiguous()
         if colsum is not None:
             _req(colsum, torch.float32, "colsum")
-            assert colsum.is_contiguous() and colsum.numel() == N
-        it.A, it.B, it.C, it.colsum = _p(a), _p(b), _p(out), _p(colsum)
-        it.lda, it.ldb, it.M, it.N, it.K = a.stride(0), b.stride(0), M, N, K
+            assert colsum.is_contiguous() and colsum.numel() == a.shape[1]
+    items = tn_items(problems)
     nbytes = lib.seer_gemm_tn_grouped_workspace_bytes(items, len(problems))
     if nbytes < 0:
         check(int(nbytes), "seer_gemm_tn_grouped_workspace_bytes")

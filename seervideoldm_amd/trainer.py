@@ -28,7 +28,8 @@ import torch
 from . import ops as hip_ops
 from . import train_ops as hip_train_ops
 from .fstext import FSTextTransformer
-from .unet import MAX_RATIO, MAX_WIN_SIZE, MIN_WIN_SIZE, SeerUNet, _Engine
+from .groupnorm import groupnorm
+from .unet import MAX_RATIO, MAX_WIN_SIZE, MIN_WIN_SIZE, SeerUNet, _Engine, fx_arena
 from .weights import geglu_row_order
 
 bf16 = torch.bfloat16
@@ -174,6 +175,10 @@ class SeerTrainer:
         # where the walk reaches it)
         self._dw_deferred = os.environ.get("SEER_DW_GROUPED", "1") != "0" and hasattr(tops, "gemm_tn_grouped")
         self._dw: List[Tuple] = []
+        # GroupNorm statistics accumulated in fixed point by the producers: the engine's switch (unet.gn_fx / SEER_GN_FX=0: per-tile sums)
+        self.gn_fx = self.eng.gn_fx and hasattr(ops, "FxArena")
+        self._fx = self._fx_arena = None        # the step's ops.FxArena (unet.fx_arena)
+        self._fx_retired: List[object] = []
         self._cf: Optional[List[Tuple]] = [] if self._dw_deferred and hasattr(tops, "colfinal_grouped") else None   # d gamma / d beta slabs of the LayerNorms, as the weight gradients
 
     # ================================================================================================ helpers
@@ -229,33 +234,16 @@ class SeerTrainer:
 
     def _cb(self, B):
         """`colsum_batch` of a launch whose output feeds a GroupNorm: accumulate into the step's arena when there is one"""
-        return (B, self._fx) if getattr(self, "_fx", None) is not None else B
+        return (B, self._fx) if self._fx is not None else B
 
     def _gn_fwd(self, x1, x2, B, rows_pb, name, eps, silu):
-        ops, w = self.ops, self.w
-        stats = torch.empty((B, self.eng.G, 2), device=x1.device, dtype=f32)
-        # as in the inference engine (unet._Engine._gn): the column sums the producing GEMM / conv left next to its output, when
-        # every source has them -- no statistics pass over the activations
-        cs1 = getattr(x1, "colsums", None)
-        cs2 = getattr(x2, "colsums", None) if x2 is not None else None
+        ops, w, G = self.ops, self.w, self.eng.G
+        stats = torch.empty((B, G, 2), device=x1.device, dtype=f32)
+        # the forms of the inference engine (groupnorm.groupnorm), except the one-launch per-tile one: the backward reads (sum, sumsq)
+        y, _ = groupnorm(ops, x1, x2, B, G, rows_pb, eps, w[name + ".weight"], w[name + ".bias"], silu, stats=stats,
+                         want_stats=True, fused=False)
         C = x1.shape[1] + (0 if x2 is None else x2.shape[1])
-        count = rows_pb * (C // self.eng.G)
-        FX = getattr(ops, "ColSumsFx", ())
-        if isinstance(cs1, FX) and (x2 is None or isinstance(cs2, FX)):
-            # accumulated fixed-point sums (unet._Engine._gn): one launch normalises and leaves the statistics for the backward
-            y = ops.groupnorm_apply_fx(x1, x2, cs1, cs2, B, self.eng.G, count, eps, w[name + ".weight"], w[name + ".bias"], silu,
-                                       stats_out=stats)
-            if y is not None:
-                return y, (x1, x2, B, stats, count, name, eps, silu)
-            ops.groupnorm_stats_from_fx(cs1, cs2, B, self.eng.G, stats)
-        elif isinstance(cs1, FX) or isinstance(cs2, FX):
-            ops.groupnorm_stats(x1, x2, B, self.eng.G, stats)
-        elif cs1 is not None and (x2 is None or cs2 is not None):
-            ops.groupnorm_stats_from_colsums(cs1, cs2, B, self.eng.G, stats)
-        else:
-            ops.groupnorm_stats(x1, x2, B, self.eng.G, stats)
-        y = ops.groupnorm_apply(x1, x2, B, self.eng.G, stats, count, eps, w[name + ".weight"], w[name + ".bias"], silu)
-        return y, (x1, x2, B, stats, count, name, eps, silu)
+        return y, (x1, x2, B, stats, rows_pb * (C // G), name, eps, silu)
 
     def _gn_bwd(self, saved, dy, dres1=None, dres2=None):
         x1, x2, B, stats, count, name, eps, silu = saved
@@ -510,16 +498,9 @@ class SeerTrainer:
         self._temb = ops.linear_smallm(emb, w["temb_all.w"], w["temb_all.b"], silu_in=True)
         tape: List[Tuple] = []
         self._fx = None
-        if getattr(self, "gn_fx", os.environ.get("SEER_GN_FX", "1") != "0") and hasattr(ops, "FxArena"):
-            need = (eng.n_groupnorms() + 16) * B * 4 * max(boc) * 2
-            if getattr(self, "_fx_arena", None) is None or self._fx_arena.buf.numel() < need:
-                assert not (sample.is_cuda and torch.cuda.is_current_stream_capturing()), \
-                    "the accumulator arena must exist before a graph capture"
-                if getattr(self, "_fx_arena", None) is not None:
-                    self._fx_retired = getattr(self, "_fx_retired", []) + [self._fx_arena]     # captured steps keep theirs by address
-                self._fx_arena = ops.FxArena(sample.device, need)
-            self._fx_arena.reset()
-            self._fx = self._fx_arena
+        if self.gn_fx:
+            self._fx = self._fx_arena = fx_arena(ops, sample, (eng.n_groupnorms() + 16) * B * 4 * max(boc) * 2,
+                                                 self._fx_arena, self._fx_retired)
         x = ops.conv_in(sample, w["conv_in.weight"], w["conv_in.bias"])
         skips = [x]
         geo = (B, Fr, H, W)

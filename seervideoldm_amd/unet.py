@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import ops as hip_ops
 from . import synth
+from .groupnorm import groupnorm, groupnorm_statistics
 from .weights import geglu_row_order, pack_conv1x1, pack_conv3x3, pack_conv3x3_up_phases
 
 bf16 = torch.bfloat16
@@ -221,6 +222,26 @@ FX_MAX_ROWS = 100_000        # rows at the finest level up to which the LayerNor
 FX_MAX_ROWS_PB = int(os.environ.get("SEER_FX_MAX_ROWS_PB", "4096"))        # rows per batch element up to which a GroupNorm's statistics are accumulated in fixed point (_Engine._cb)
 
 
+def _switch(model, attr: str, env: Optional[str] = None) -> bool:
+    """an engine switch: the model's attribute if it is set, else the environment variable if the switch has one ("0" = off), else on"""
+    on = getattr(model, attr, None)
+    return bool(on) if on is not None else (env is None or os.environ.get(env, "1") != "0")
+
+
+def fx_arena(ops, sample, need: int, arena, retired: list):
+    """the ops.FxArena of one evaluation, zeroed: `arena` where it holds `need` int64 elements, else a new one -- the old one joins
+    `retired` (captured steps of smaller shapes keep adding into theirs by address).  reset() = one fill over what the last
+    evaluation took."""
+    if arena is None or arena.buf.numel() < need:
+        assert not (sample.is_cuda and torch.cuda.is_current_stream_capturing()), \
+            "the accumulator arena must exist before a graph capture"
+        if arena is not None:
+            retired.append(arena)
+        arena = ops.FxArena(sample.device, need)
+    arena.reset()
+    return arena
+
+
 class _Engine:
     """packed weights + the kernel schedule of one SeerUNet forward."""
 
@@ -237,36 +258,32 @@ class _Engine:
         self.heads = self.cfg.attention_head_dim
         self.G = self.cfg.norm_num_groups
         self.eps = self.cfg.norm_eps
-        # GroupNorm statistics from the producers' column sums (ops.ColSums) instead of a pass over the activations, in every
-        # engine (single-process and sharded: a shard all-reduces the same (sum, sumsq) either way).  `model.gn_colsums = False`
-        # before prepare() keeps the two-stage reduction everywhere (A/B runs, tests).
-        self.gn_colsums = bool(getattr(model, "gn_colsums", True))
-        # statistics from column sums INSIDE the apply launch (model.gn_fused = False / SEER_GN_FUSED=0: the two-launch form, A/B runs)
-        self.gn_fused = bool(getattr(model, "gn_fused", os.environ.get("SEER_GN_FUSED", "1") != "0"))
-        # ... and, single-process engines: the producers ACCUMULATE the sums per batch element in fixed point (ops.ColSumsFx) and the
-        # apply launch reads them directly -- no finalize launch either (model.gn_fx = False / SEER_GN_FX=0: the forms above)
-        self.gn_fx = bool(getattr(model, "gn_fx", os.environ.get("SEER_GN_FX", "1") != "0"))
+        # The switches, resolved here and nowhere else (_switch: the model's attribute if set, else the environment variable, else
+        # on), each with what it needs.  A/B runs and the tests run the older forms through them.
+        # gn_colsums, gn_fused, gn_fx: GroupNorm statistics from the column sums the producers leave (per tile; derived inside the
+        #   apply launch; accumulated in fixed point by the producers) instead of a pass over the activations: groupnorm.py
+        # ln_fold:    LayerNorm folded into the consuming GEMM: the producers of the residual stream leave per-row (sum, sum of
+        #   squares) next to it (ops.RowStats), the q|k|v / to_q / ff.net.0 GEMMs normalise in their epilogue -- no LayerNorm launch
+        #   (fold_ln=False: the trainer's engine -- its weights move, it runs its own forward)
+        # ff_fold:    ff.net.2 and proj_out as one two-source GEMM (off: two launches; see _pack)
+        # ff_fused:   ... and, at 320 channels, the whole feed-forward with it as ONE launch
+        # rowchain:   the row-local chains in front of the attention launches at 320 channels -- GroupNorm -> proj_in -> norm1 ->
+        #   q|k|v, and attn1.to_out + residual -> norm2 -> attn2.to_q -- as ONE launch each (ops.rowchain, csrc/rowchain.hip)
+        # ff_pre:     ... and the block's last to_out + residual as a prologue of the fused feed-forward
+        self.gn_colsums = _switch(model, "gn_colsums")
+        self.gn_fused = _switch(model, "gn_fused", "SEER_GN_FUSED")
+        self.gn_fx = _switch(model, "gn_fx", "SEER_GN_FX")
+        self.ln_fold = bool(fold_ln) and _switch(model, "ln_fold", "SEER_LN_FOLD") and hasattr(self.ops, "fold_layernorm")
+        self.ff_fold = _switch(model, "ff_fold", "SEER_FF_FOLD")
+        self.ff_fused = self.ff_fold and _switch(model, "ff_fused", "SEER_FF_FUSED")
+        self.rowchain = _switch(model, "rowchain", "SEER_ROWCHAIN") and hasattr(self.ops, "rowchain")
+        self.ff_pre = self.rowchain and self.ff_fused and _switch(model, "ff_pre", "SEER_FF_PRE")
         self._fx_arena = None
         self._fx_retired: List[object] = []
         self._fx = None
-        # LayerNorm folded into the consuming GEMM: the producers of the residual stream leave per-row (sum, sum of squares) next
-        # to it (ops.RowStats), the q|k|v / to_q / ff.net.0 GEMMs normalise in their epilogue -- no LayerNorm launch
-        # (model.ln_fold = False / SEER_LN_FOLD=0: the layernorm kernel everywhere)
-        self.ln_fold = bool(fold_ln) and bool(getattr(model, "ln_fold", os.environ.get("SEER_LN_FOLD", "1") != "0")) and \
-            hasattr(self.ops, "fold_layernorm")       # (fold_ln=False: the trainer's engine -- its weights move, it runs its own forward)
         self.ln_folded = 0
         self._ln_on = False
-        # ff.net.2 and proj_out as one two-source GEMM (model.ff_fold = False / SEER_FF_FOLD=0: two launches; see _pack)
-        self.ff_fold = bool(getattr(model, "ff_fold", os.environ.get("SEER_FF_FOLD", "1") != "0"))
-        # ... and, at 320 channels, the whole feed-forward with it as ONE launch (model.ff_fused = False / SEER_FF_FUSED=0: off)
-        self.ff_fused = self.ff_fold and bool(getattr(model, "ff_fused", os.environ.get("SEER_FF_FUSED", "1") != "0"))
-        # ... and the row-local chains in front of the attention launches at 320 channels -- GroupNorm -> proj_in -> norm1 -> q|k|v, and
-        # attn1.to_out + residual -> norm2 -> attn2.to_q -- as ONE launch each (ops.rowchain, csrc/rowchain.hip;
-        # model.rowchain = False / SEER_ROWCHAIN=0: the separate launches)
-        self.rowchain = bool(getattr(model, "rowchain", os.environ.get("SEER_ROWCHAIN", "1") != "0")) and hasattr(self.ops, "rowchain")
         self.rowchains = 0
-        # ... and the block's last to_out + residual as a prologue of the fused feed-forward (SEER_FF_PRE=0: its own launch)
-        self.ff_pre = self.rowchain and self.ff_fused and os.environ.get("SEER_FF_PRE", "1") != "0"
         self._ffpre_bias: Dict[str, str] = {}
         self.gn_from_colsums = 0
         self.w: Dict[str, torch.Tensor] = {}
@@ -413,61 +430,13 @@ class _Engine:
 
     # ---- building blocks --------------------------------------------------------------------------------------
     def _gn(self, x1, x2, B, rows_pb, name, eps, silu):
-        """GroupNorm over (C/G, F, H, W): stats (+ cross-shard reduction) then apply."""
-        ops = self.ops
-        stats = self._stats_arena[self._stats_i]
+        """GroupNorm over (C/G, F, H, W); which of its forms runs, and the cross-shard reduction: groupnorm.groupnorm"""
         self._stats_i += 1
-        # statistics from the column sums the producing GEMM / conv left next to its output (ops.ColSums) when every source
-        # has them: no pass over the activations; otherwise the two-stage reduction over x1 | x2
-        cs1 = getattr(x1, "colsums", None)
-        cs2 = getattr(x2, "colsums", None) if x2 is not None else None
-        C = x1.shape[1] + (0 if x2 is None else x2.shape[1])
-        FX = getattr(ops, "ColSumsFx", ())
-        if self.shard is not None and self.shard.exact_stats and self._fx is not None and hasattr(ops, "groupnorm_stats_fx"):
-            # frame shards (P > 1; batch groups alone exchange nothing and keep the forms below): EVERY GroupNorm normalises with exact integer statistics -- a source whose producer left no
-            # accumulated sums (conv_in's output, tensors above the producers' row limit) gets them from one pass over its rows;
-            # the sums stay with the tensor (a skip connection feeds a second GroupNorm with the totals already exchanged)
-            if not isinstance(cs1, FX):
-                cs1 = x1.colsums = ops.groupnorm_stats_fx(x1, B, self._fx)
-            if x2 is not None and not isinstance(cs2, FX):
-                cs2 = x2.colsums = ops.groupnorm_stats_fx(x2, B, self._fx)
-        exchanged = False
-        if isinstance(cs1, FX) or isinstance(cs2, FX):
-            if isinstance(cs1, FX) and (x2 is None or isinstance(cs2, FX)):
-                count = rows_pb * (C // self.G)
-                if self.shard is not None:
-                    # frame shards: the integer sums of all shards are added in place (exact: the statistics are the unsharded ones)
-                    count = self.shard.reduce_fx((cs1, cs2), count, sync=self.sync_point)
-                    exchanged = True
-                y = ops.groupnorm_apply_fx(x1, x2, cs1, cs2, B, self.G, count, eps,
-                                           self.w[name + ".weight"], self.w[name + ".bias"], silu)
-                self.gn_from_colsums += 1
-                if y is not None:
-                    return y
-                ops.groupnorm_stats_from_fx(cs1, cs2, B, self.G, stats)
-            else:
-                ops.groupnorm_stats(x1, x2, B, self.G, stats)
-        elif self.gn_colsums and cs1 is not None and (x2 is None or cs2 is not None):
-            if self.shard is None and self.gn_fused:
-                # one launch: every apply block re-derives the statistics of its own groups from the column sums (no frame
-                # shards: a sharded run all-reduces the statistics between the two steps)
-                y = ops.groupnorm_apply_from_colsums(x1, x2, cs1, cs2, B, self.G, rows_pb * (C // self.G), eps,
-                                                     self.w[name + ".weight"], self.w[name + ".bias"], silu)
-                if y is not None:
-                    self.gn_from_colsums += 1
-                    return y
-            ops.groupnorm_stats_from_colsums(cs1, cs2, B, self.G, stats)
-            self.gn_from_colsums += 1
-        else:
-            ops.groupnorm_stats(x1, x2, B, self.G, stats)
-        count = rows_pb * (C // self.G)
-        if self.shard is not None:
-            if exchanged:           # the statistics above came from sums that already hold every shard's share
-                count = count / self.shard.local_frames * self.shard.total_frames
-            else:
-                count = self.shard.reduce_gn_stats(stats, count, sync=self.sync_point)
-        return ops.groupnorm_apply(x1, x2, B, self.G, stats, count, eps, self.w[name + ".weight"],
-                                   self.w[name + ".bias"], silu)
+        y, from_colsums = groupnorm(self.ops, x1, x2, B, self.G, rows_pb, eps, self.w[name + ".weight"], self.w[name + ".bias"], silu,
+                                    stats=self._stats_arena[self._stats_i - 1], use_colsums=self.gn_colsums, fused=self.gn_fused,
+                                    shard=self.shard, sync=self.sync_point, arena=self._fx)
+        self.gn_from_colsums += from_colsums
+        return y
 
     def _cb(self, B, rows_pb, for_chain=False):
         """`colsum_batch` of a launch whose output (rows_pb rows per batch element) feeds a GroupNorm: (B, arena) = accumulate in
@@ -479,58 +448,37 @@ class _Engine:
             return 0
         return (B, self._fx) if (self._fx is not None and (rows_pb <= FX_MAX_ROWS_PB or for_chain)) else B
 
-    def _chain_next(self, C, B, rows_pb):
-        """will a transformer's GroupNorm -> proj_in -> norm1 -> q|k|v over [B * rows_pb, C] run as one launch (ops.rowchain)?  Its
-        producer then ACCUMULATES the column sums whatever the tensor's size (_cb(for_chain=True)): the chain reads them directly and
-        the statistics launch in front of it goes too (the apply launch that made the accumulated form lose at the 32x32 level is
-        not run at all there)"""
+    def _chain_ok(self, C, B, rows_pb):
+        """will a transformer's GroupNorm -> proj_in -> norm1 -> q|k|v over [B * rows_pb, C] run as one launch (ops.rowchain)?  Asked
+        by the consumer (_rc_in) and by the PRODUCER of its input, which then accumulates the column sums whatever the tensor's size
+        (_cb(for_chain=True)): the chain reads them directly and the statistics launch in front of it goes too (the apply launch
+        that made the accumulated form lose at the 32x32 level is not run at all there).  Frame shards exchange the statistics
+        between the two steps and keep the separate launches (batch groups alone run the single-process forms)."""
         ops = self.ops
-        return bool(self.rowchain and (self.shard is None or not self.shard.exact_stats) and self._fx is not None and
-                    C == getattr(ops, "ROWCHAIN_C", -1) and
+        return bool(self.rowchain and (self.shard is None or not self.shard.exact_stats) and C == ops.ROWCHAIN_C and
                     rows_pb >= ops.ROWCHAIN_ROWS and ops.rowchain_pays(B * rows_pb))
-
-    def _gn_stats(self, x, B, rows_pb):
-        """(statistics, count) of the GroupNorm over x alone, for a launch that applies the normalisation itself (ops.rowchain): the
-        producer's accumulated fixed-point sums as they are, else stats [B, G, 2] from its per-tile column sums or from a pass over x.
-        None: a frame-sharded engine -- the caller keeps the separate launches (batch groups alone run the single-process forms)."""
-        ops = self.ops
-        cs = getattr(x, "colsums", None)
-        if self.shard is not None and self.shard.exact_stats:      # frame shards exchange the statistics between the two steps
-            return None
-        if isinstance(cs, getattr(ops, "ColSumsFx", ())):
-            self.gn_from_colsums += 1
-            return cs, rows_pb * (x.shape[1] // self.G)         # the producer's accumulated sums: read by the chain itself
-        stats = self._stats_arena[self._stats_i]
-        self._stats_i += 1
-        if self.gn_colsums and cs is not None:
-            ops.groupnorm_stats_from_colsums(cs, None, B, self.G, stats)
-            self.gn_from_colsums += 1
-        else:
-            ops.groupnorm_stats(x, None, B, self.G, stats)
-        return stats, rows_pb * (x.shape[1] // self.G)
 
     def _rc_in(self, p, tb, x, B, rows_pb, rotary, qs):
         """GroupNorm -> proj_in -> norm1 -> q|k|v of transformer `p` as one launch: (h, qkv), or None when this block / shape keeps
         the separate launches"""
         ops, w = self.ops, self.w
-        if not self.rowchain or (p + ".rc.proj_in") not in w or rows_pb < ops.ROWCHAIN_ROWS or not ops.rowchain_pays(x.shape[0]):
+        if not self._chain_ok(x.shape[1], B, rows_pb) or (p + ".rc.proj_in") not in w:
             return None
-        i0 = self._stats_i
-        st = self._gn_stats(x, B, rows_pb)
-        if st is None:
-            return None
+        st, count, from_colsums = groupnorm_statistics(ops, x, B, self.G, rows_pb, stats=self._stats_arena[self._stats_i],
+                                                       use_colsums=self.gn_colsums)
         r = ops.rowchain(x, w[p + ".rc.proj_in"], b1=w[p + ".proj_in.bias"],
-                         gn=(st[0], st[1], 1e-6, w[p + ".norm.weight"], w[p + ".norm.bias"], rows_pb, self.G),
+                         gn=(st, count, 1e-6, w[p + ".norm.weight"], w[p + ".norm.bias"], rows_pb, self.G),
                          ln=(w[tb + ".norm1.weight"], w[tb + ".norm1.bias"], 1e-5), w2f=w[tb + ".rc.qkv"], col_scale=(qs, 1), rotary=rotary)
         if r is None:
-            self._stats_i = i0
             return None
+        self._stats_i += 1
+        self.gn_from_colsums += from_colsums
         self.rowchains += 1
         return r
 
     def _resnet(self, p, x, skip, geo, feeds_transformer=False):
         """ResnetBlock3D (resnet.py:174-208); `skip` is the channel-concat partner of unet_3d_blocks.py:596,712.  feeds_transformer:
-        the output's only GroupNorm is the next transformer's (see _chain_next)."""
+        the output's only GroupNorm is the next transformer's (see _chain_ok)."""
         ops, w = self.ops, self.w
         B, Fr, H, W = geo
         rows_pb = Fr * H * W
@@ -546,7 +494,7 @@ class _Engine:
         else:
             assert skip is None
             sc = x
-        if feeds_transformer and self._chain_next(w[p + ".conv2.weight"].shape[0], B, rows_pb):
+        if feeds_transformer and self._chain_ok(w[p + ".conv2.weight"].shape[0], B, rows_pb):
             cb = self._cb(B, rows_pb, for_chain=True)
         return ops.conv3x3(h, w[p + ".conv2.weight"], B * Fr, H, W, bias=w[p + ".conv2.bias"], residual=sc, colsum_batch=cb)
 
@@ -642,7 +590,7 @@ class _Engine:
             self._attn_list.append(self._cross_scores(q, kv[:, :C], B, Fr, H, W, heads, d, L))
         ops.attention(q, kv[:, :C], kv[:, C:], a, batch=B * Fr, heads=heads, head_dim=d, Sq=HW, Sk=L, q_prescaled=True)
         # (the output's only GroupNorm is the temporal transformer's: accumulated sums when that one runs as a chain)
-        cb = self._cb(B, Fr * HW, for_chain=self._chain_next(C, B, Fr * HW))
+        cb = self._cb(B, Fr * HW, for_chain=self._chain_ok(C, B, Fr * HW))
         if self._ff_pre(p, tb, h):
             return self._ff_proj_out(p, tb, h, x, cb, a=a)      # attn2.to_out + residual inside the fused feed-forward launch
         # (the fused feed-forward normalises its rows itself: no row statistics asked of their producer)
@@ -752,15 +700,9 @@ class _Engine:
         self._ln_on = self.ln_fold and small
         if (fx_gn or self._ln_on) and hasattr(ops, "FxArena"):
             # fixed-point accumulators of the evaluation: a [reps, B, 2, C] slot per colsum producer, a [rows, 2] slot per producer
-            # of LayerNorm rows; reset() = one fill over what the last evaluation took
+            # of LayerNorm rows
             need = (self.n_groupnorms() + 16) * B * 4 * max(boc) * 2 + 5 * 16 * B * Fr * H * W * 2
-            if self._fx_arena is None or self._fx_arena.buf.numel() < need:
-                assert not (sample.is_cuda and torch.cuda.is_current_stream_capturing()), \
-                    "the accumulator arena must exist before a graph capture"
-                if self._fx_arena is not None:
-                    self._fx_retired.append(self._fx_arena)     # captured steps of smaller shapes keep adding into theirs by address
-                self._fx_arena = ops.FxArena(sample.device, need)
-            self._fx_arena.reset()
+            self._fx_arena = fx_arena(ops, sample, need, self._fx_arena, self._fx_retired)
             self._fx = self._fx_arena if fx_gn else None
         emb = ops.timestep_embedding(t, boc[0], self.cfg.flip_sin_to_cos, self.cfg.freq_shift)
         emb = ops.linear_smallm(emb, w["time_embedding.linear_1.weight"], w["time_embedding.linear_1.bias"], silu_out=True)

@@ -27,6 +27,7 @@ import torch
 import torch.nn as nn
 
 from . import ops as hip_ops
+from .groupnorm import groupnorm
 from .unet import _build_tree, _Config
 from .weights import pack_conv1x1, pack_conv3x3
 
@@ -252,12 +253,10 @@ class AutoencoderKL(nn.Module):
 
     # ---- shared blocks ----------------------------------------------------------------------------------------------
     def _gn(self, x, N, rows, name, silu):
-        ops = hip_ops
         G = self.config.norm_num_groups
         stats = torch.empty((N, G, 2), device=x.device, dtype=torch.float32)
-        ops.groupnorm_stats(x, None, N, G, stats)
-        return ops.groupnorm_apply(x, None, N, G, stats, rows * (x.shape[1] // G), 1e-6, self._w[name + ".weight"],
-                                   self._w[name + ".bias"], silu)
+        # (no producer here leaves column sums: the pass over the activations + apply)
+        return groupnorm(hip_ops, x, None, N, G, rows, 1e-6, self._w[name + ".weight"], self._w[name + ".bias"], silu, stats=stats)[0]
 
     def _res(self, p, x, N, H, W):
         ops, w = hip_ops, self._w

@@ -177,3 +177,20 @@ def test_deferred_weight_gradients_are_final_at_the_hook_and_equal_the_immediate
     tr0.forward_backward(x, noise, t, text, cond)
     assert torch.equal(tr0.pu.g, tr.pu.g) and torch.equal(tr0.pf.g, tr.pf.g)
     assert len(calls) == 2
+
+
+def test_grouped_weight_gradient_items_carry_the_slice_length(monkeypatch):
+    """train_ops.tn_items: the host table of seer_gemm_tn_grouped_f32.  The library reads no environment variable: SEER_TN_GROUP_ROWS
+    travels in every item's group_rows, 0 (= the built-in 16384) when it is unset"""
+    from seervideoldm_amd import train_ops
+    a, b = torch.zeros((24, 16), dtype=torch.bfloat16), torch.zeros((24, 8), dtype=torch.bfloat16)
+    out, cs = torch.zeros((16, 8)), torch.zeros((16,))
+    probs = [(a, b, out, cs), (a[:, :8], b, out[:8], None)]
+    monkeypatch.delenv("SEER_TN_GROUP_ROWS", raising=False)
+    items = train_ops.tn_items(probs)
+    assert [it.group_rows for it in items] == [0, 0]
+    assert (items[0].A, items[0].B, items[0].C, items[0].colsum) == (a.data_ptr(), b.data_ptr(), out.data_ptr(), cs.data_ptr())
+    assert (items[0].lda, items[0].ldb, items[0].M, items[0].N, items[0].K) == (16, 8, 24, 16, 8)
+    assert (items[1].lda, items[1].N, items[1].colsum) == (16, 8, None)
+    monkeypatch.setenv("SEER_TN_GROUP_ROWS", "2048")
+    assert [it.group_rows for it in train_ops.tn_items(probs)] == [2048, 2048]
