@@ -28,8 +28,10 @@ extern "C" {
 #define SEER_ENOSYS (-38)   /* shape class not built (e.g. head dim) */
 #define SEER_ELAUNCH (-5)   /* hipLaunchKernel reported an error */
 
-/* storage type of 16-bit activations for the *_dt entry points: bf16 everywhere on the UNet path, IEEE half on the VAE path (the
- * reference decodes in fp32: inference_img.py:118) */
+/* storage type of 16-bit tensors: bf16 by default on the UNet path, IEEE half on the VAE path (the reference decodes in fp32:
+ * inference_img.py:118) and in the UNet engine under fp16 autocast.  Every entry point with a `dtype` argument runs the same kernel
+ * on either storage type -- wherever its comment says bf16, read "the storage type `dtype`" -- and returns SEER_EINVAL for any other
+ * code (ahead of any SEER_ENOSYS shape refusal). */
 #define SEER_DT_BF16 0
 #define SEER_DT_F16 1
 
@@ -300,7 +302,7 @@ int seer_rotary_inplace(void* x, int64_t rows, int32_t ld, int32_t col0_q, int32
  * ALL shards (so mean = sum/count). */
 int64_t seer_groupnorm_workspace_floats(int32_t C, int32_t batch, int64_t rows_per_batch, int32_t groups);
 int seer_groupnorm_stats(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                         int64_t rows_per_batch, int32_t groups, float* stats, float* workspace, void* stream);
+                         int64_t rows_per_batch, int32_t groups, float* stats, float* workspace, int32_t dtype, void* stream);
 /* The same stats[b][g][2] from the column sums the producers of x1 / x2 left behind (seer_gemm_desc::colsum) -- no pass over
  * the activations.  Source i: C_i channels, partial rows [phases_i][tiles_i][C_i][2]; the tiles of a phase cover the batch
  * elements in order, tiles_i / batch each (tiles_i % batch == 0).  One wave per (b, g) adds its channels' partials in a fixed
@@ -310,22 +312,22 @@ int seer_groupnorm_stats_from_colsums(const float* cs1, int32_t C1, int32_t phas
                                       float* stats, void* stream);
 int seer_groupnorm_apply(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
                          int64_t rows_per_batch, int32_t groups, const float* stats, double count, float eps,
-                         const float* gamma, const float* beta, int32_t silu, void* y, void* stream);
+                         const float* gamma, const float* beta, int32_t silu, void* y, int32_t dtype, void* stream);
 /* seer_groupnorm_stats_from_colsums + seer_groupnorm_apply in ONE launch: every block re-derives the statistics of the groups it
- * normalises from the producers' column sums (same arguments as the two calls; bf16 activations).  Single-process runs only: a
+ * normalises from the producers' column sums (same arguments as the two calls).  Single-process runs only: a
  * frame-sharded run has to all-reduce the statistics between the two steps and keeps the two calls.  SEER_ENOSYS when the
  * channel layout does not slice into whole groups of 64..128 channels (the caller then makes the two calls). */
 int seer_groupnorm_apply_from_colsums(const void* x1, int32_t C1, const void* x2, int32_t C2, const float* cs1, int32_t phases1,
                                       int32_t tiles1, const float* cs2, int32_t phases2, int32_t tiles2, int32_t batch,
                                       int64_t rows_per_batch, int32_t groups, double count, float eps, const float* gamma,
-                                      const float* beta, int32_t silu, void* y, void* stream);
+                                      const float* beta, int32_t silu, void* y, int32_t dtype, void* stream);
 /* GroupNorm apply whose statistics are the fixed-point column sums the producers ACCUMULATED (seer_gemm_desc::colsum_fx):
  * fx1 [reps1][batch][2][C1], fx2 [reps2][batch][2][C2] int64 (NULL with C2 = 0).  One launch per GroupNorm; every block converts the sums of
  * the groups it normalises (double precision) and streams its rows.  stats_out (or NULL): receives (sum, sum of squares) per
  * (batch element, group) as fp32 [batch][groups][2], what seer_groupnorm_bwd takes.  SEER_ENOSYS as above. */
 int seer_groupnorm_apply_fx(const void* x1, int32_t C1, const void* x2, int32_t C2, const int64_t* fx1, int32_t reps1,
                             const int64_t* fx2, int32_t reps2, int32_t batch, int64_t rows_per_batch, int32_t groups, double count, float eps, const float* gamma,
-                            const float* beta, int32_t silu, void* y, float* stats_out, void* stream);
+                            const float* beta, int32_t silu, void* y, float* stats_out, int32_t dtype, void* stream);
 /* The same accumulated sums from the ACTIVATIONS: fx [batch][2][C] int64 (one replica; ADDED to: zero it first) receives
  * sum_r round(x[r][c] * 2^20) and sum_r round(x[r][c]^2 * 2^20) over the rows of each batch element.  Every element is rounded on
  * its own, so the totals are exact integer sums: independent of the order of the additions and -- frame shards -- of which rank
@@ -333,16 +335,6 @@ int seer_groupnorm_apply_fx(const void* x1, int32_t C1, const void* x2, int32_t 
  * for GroupNorm sources without accumulated producer sums (resnet.py:179,197, attention.py:133 normalise over all frames). */
 int seer_groupnorm_stats_fx(const void* x, int32_t C, int32_t batch, int64_t rows_per_batch, int64_t* fx, int32_t dtype,
                             void* stream);
-/* seer_groupnorm_apply_from_colsums / seer_groupnorm_apply_fx with the storage type of x1 / x2 / y chosen by `dtype` (SEER_DT_*):
- * the UNet engine on fp16 storage */
-int seer_groupnorm_apply_from_colsums_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, const float* cs1, int32_t phases1,
-                                         int32_t tiles1, const float* cs2, int32_t phases2, int32_t tiles2, int32_t batch,
-                                         int64_t rows_per_batch, int32_t groups, double count, float eps, const float* gamma,
-                                         const float* beta, int32_t silu, void* y, int32_t dtype, void* stream);
-int seer_groupnorm_apply_fx_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, const int64_t* fx1, int32_t reps1,
-                               const int64_t* fx2, int32_t reps2, int32_t batch, int64_t rows_per_batch, int32_t groups, double count,
-                               float eps, const float* gamma, const float* beta, int32_t silu, void* y, float* stats_out, int32_t dtype,
-                               void* stream);
 /* The feed-forward of a transformer block at the 320-channel level and the transformer's proj_out, ONE launch (csrc/ff_fused.hip):
  *     y = x + [Wp | Wp W2] [h | g] + bcat,   g = GEGLU(LayerNorm(h; gamma, beta, eps) W1^T + b1)
  * i.e. norm3 -> ff.net.0 -> ff.net.2 + residual -> proj_out + residual (seer/models/attention.py:231-248, 308-327, 742-747,
@@ -352,16 +344,16 @@ int seer_groupnorm_apply_fx_dt(const void* x1, int32_t C1, const void* x2, int32
  * b1 [2560] fp32 in the same interleaved order; bcat [320] fp32 = Wp b2 + bp.  colsum_fx (or NULL): [fx_reps][M / fx_rows][2][320]
  * int64, ADDED to, the fixed-point column sums of y as seer_gemm_desc::colsum_fx (fx_rows = rows per batch element, a multiple of
  * 16 and at least 96: a tile may straddle two batch elements).  colsum_tiles (or NULL; M a multiple of 96): [M / 96][320][2] fp32,
- * WRITTEN, (sum, sum of squares) of the stored values per 96-row tile as seer_gemm_desc::colsum.  All pointers 16-byte aligned.  SEER_EINVAL otherwise. */
-int seer_ff_fused_c320(const void* h, int32_t ldh, const void* x, int32_t ldx, void* y, int32_t ldy, int64_t M,
-                       const float* gamma, const float* beta, float eps, const void* w1f, const float* b1, const void* wcf,
-                       const float* bcat, int64_t* colsum_fx, int64_t fx_rows, int32_t fx_reps, float* colsum_tiles, void* stream);
-/* ... with h, x, y and the two packed weight matrices in the storage type `dtype` (SEER_DT_*; the pack entry points move 16-bit
- * words and serve both) */
-int seer_ff_fused_c320_dt(const void* h, int32_t ldh, const void* x, int32_t ldx, void* y, int32_t ldy, int64_t M,
-                          const float* gamma, const float* beta, float eps, const void* w1f, const float* b1, const void* wcf,
-                          const float* bcat, int64_t* colsum_fx, int64_t fx_rows, int32_t fx_reps, float* colsum_tiles, int32_t dtype,
-                          void* stream);
+ * WRITTEN, (sum, sum of squares) of the stored values per 96-row tile as seer_gemm_desc::colsum.  All pointers 16-byte aligned.  SEER_EINVAL otherwise.
+ * The optional prologue: with a != NULL the rows the launch reads as h are  h + a Wo^T + bo  -- the attention's to_out projection and its
+ * residual (seer/models/attention.py:237-240, 316-322), computed in the tile and stored nowhere (this launch is their only reader).
+ * a [M][320] (row stride lda), wof = Wo [320][320] in the fragment order of seer_rowchain_pack, bo [320] fp32; a == NULL: no prologue
+ * (lda, wof, bo ignored).  h, x, y, a and the packed weight matrices are in the storage type `dtype` (the pack entry points move
+ * 16-bit words and serve both). */
+int seer_ff_fused_c320(const void* a, int32_t lda, const void* wof, const float* bo, const void* h, int32_t ldh, const void* x,
+                       int32_t ldx, void* y, int32_t ldy, int64_t M, const float* gamma, const float* beta, float eps,
+                       const void* w1f, const float* b1, const void* wcf, const float* bcat, int64_t* colsum_fx, int64_t fx_rows,
+                       int32_t fx_reps, float* colsum_tiles, int32_t dtype, void* stream);
 /* The row-local chains in front of the attention launches of a transformer block at the 320-channel level, ONE launch (csrc/rowchain.hip):
  *     h   = [GroupNorm(inp)] W1^T + b1 [+ res]                         (stored when h != NULL)
  *     out = LayerNorm(h; ln_gamma, ln_beta, ln_eps) [W2_0 | ... ]^T     n2 = 1..3 thirds of 320 columns (skipped when w2f == NULL)
@@ -391,41 +383,20 @@ int seer_rowchain_c320(const seer_rowchain_desc* desc /* host */, void* stream);
 /* n_mats 320 x 320 matrices -- rows 320 t .. 320 t + 319 of W [n_mats * 320][ld], 16-bit elements -- into the kernel's fragment order:
  * out[t][K step 5][wave 4][k32 2][column fragment 5][lane 64][8], element W[320 t + 80 w + 16 j + (lane & 15)][64 s + 32 k32 + 8 (lane >> 4) + e] */
 int seer_rowchain_pack(const void* W, int32_t ld, int32_t n_mats, void* out, void* stream);
-/* ... with a prologue: the rows the launch reads as h are  h + a Wo^T + bo  -- the attention's to_out projection and its residual
- * (seer/models/attention.py:237-240, 316-322), computed in the tile and stored nowhere (this launch is their only reader).  a [M][320]
- * (row stride lda), wof = Wo [320][320] in the fragment order of seer_rowchain_pack, bo [320] fp32; a == NULL: no prologue. */
-int seer_ff_fused_c320_pre(const void* a, int32_t lda, const void* wof, const float* bo, const void* h, int32_t ldh, const void* x,
-                           int32_t ldx, void* y, int32_t ldy, int64_t M, const float* gamma, const float* beta, float eps,
-                           const void* w1f, const float* b1, const void* wcf, const float* bcat, int64_t* colsum_fx, int64_t fx_rows,
-                           int32_t fx_reps, float* colsum_tiles, int32_t dtype, void* stream);
 /* w1 [2560][320] bf16 -> out (same size): [chunk 20][wave 4][K step 5][k32 2][value | gate][lane 64][8 bf16], element
  * w1[128 c + 32 w + 16 f + (lane & 15)][64 ks + 32 k32 + 8 (lane >> 4) + e]: every fragment load of the kernel is one contiguous KiB */
 int seer_ff_fused_pack_w1(const void* w1, void* out, void* stream);
 /* wcat [320][1600] bf16 -> out (same size): [K step 25][wave 4][k32 2][column fragment 5][lane 64][8 bf16], element
  * wcat[80 w + 16 j + (lane & 15)][64 s + 32 k32 + 8 (lane >> 4) + e] */
 int seer_ff_fused_pack_wcat(const void* wcat, void* out, void* stream);
-/* the same two with the storage type of x1 / x2 / y chosen by `dtype` (SEER_DT_*): the VAE's nn.GroupNorm(32, eps 1e-6)
- * (ldm/modules/diffusionmodules/model.py:38-40) on fp16 activations */
-int seer_groupnorm_stats_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                            int64_t rows_per_batch, int32_t groups, float* stats, float* workspace, int32_t dtype, void* stream);
-int seer_groupnorm_apply_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                            int64_t rows_per_batch, int32_t groups, const float* stats, double count, float eps,
-                            const float* gamma, const float* beta, int32_t silu, void* y, int32_t dtype, void* stream);
-
 /* nn.LayerNorm(C) per token row (attention.py:198-200,275-277), eps 1e-5; bf16 in/out, fp32 statistics. */
 int seer_layernorm(const void* x, int64_t rows, int32_t C, int32_t ldx, const float* gamma, const float* beta,
-                   float eps, void* y, int32_t ldy, void* stream);
-/* ... with x and y in the storage type `dtype` (SEER_DT_*) */
-int seer_layernorm_dt(const void* x, int64_t rows, int32_t C, int32_t ldx, const float* gamma, const float* beta,
-                      float eps, void* y, int32_t ldy, int32_t dtype, void* stream);
+                   float eps, void* y, int32_t ldy, int32_t dtype, void* stream);
 
 /* y = softmax(scale * x) over rows of a [rows, n] matrix, x bf16 or fp32, y bf16 (VAE mid attention,
  * ldm/modules/diffusionmodules/model.py:186-197) */
 int seer_softmax_rows(const void* x, int32_t x_is_f32, int64_t rows, int32_t n, int32_t ld, float scale, void* y,
-                      int32_t ldy, void* stream);
-/* ... with 16-bit x and y in the storage type `dtype` (SEER_DT_*) */
-int seer_softmax_rows_dt(const void* x, int32_t x_is_f32, int64_t rows, int32_t n, int32_t ld, float scale, void* y,
-                         int32_t ldy, int32_t dtype, void* stream);
+                      int32_t ldy, int32_t dtype, void* stream);
 
 /* ---- small / boundary kernels ----------------------------------------------------------- */
 /* diffusers Timesteps(320, flip_sin_to_cos, freq_shift) (unet_3d_condition.py:97,307): out[b] = [cos | sin](t*f_i)
@@ -436,25 +407,18 @@ int seer_timestep_embedding(const int64_t* t, int32_t B, int32_t dim, int32_t fl
 /* small-M linear: y[b, n] = act( sum_k f(x[b,k]) * W[n,k] + bias[n] ), f = SiLU if silu_in.  x fp32 [B,K], W bf16 [N][K],
  * y fp32.  Used for time_embedding (unet_3d_condition.py:308) and all 22 time_emb_proj at once (resnet.py:192). */
 int seer_linear_smallm(const float* x, int32_t B, int32_t K, const void* W, const float* bias, int32_t N,
-                       int32_t silu_in, int32_t silu_out, float* y, void* stream);
-/* ... with W in the storage type `dtype` (SEER_DT_*) */
-int seer_linear_smallm_dt(const float* x, int32_t B, int32_t K, const void* W, const float* bias, int32_t N,
-                          int32_t silu_in, int32_t silu_out, float* y, int32_t dtype, void* stream);
+                       int32_t silu_in, int32_t silu_out, float* y, int32_t dtype, void* stream);
 
 /* conv_in: InflatedConv3d(4->C0, 3x3, pad 1) reading the reference layout [B, Cin, F, H, W] fp32 and writing
- * channels-last bf16 [B*F, H*W, C0] (unet_3d_condition.py:94,311).  W fp32 repacked to [3][3][Cin][C0]. */
+ * channels-last bf16 [B*F, H*W, C0] (unet_3d_condition.py:94,311; the VAE's conv_in, ldm/modules/diffusionmodules/model.py:487-491).
+ * W fp32 repacked to [3][3][Cin][C0]. */
 int seer_conv_in(const float* x, int32_t B, int32_t Cin, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                 const float* bias, int32_t Cout, void* y, void* stream);
+                 const float* bias, int32_t Cout, void* y, int32_t dtype, void* stream);
 /* conv_out: InflatedConv3d(C0->Cout(4), 3x3, pad 1) reading channels-last bf16 and writing [B, Cout, F, H, W] fp32
- * (unet_3d_condition.py:205,370).  W fp32 [Cout][3][3][C0]. */
+ * (unet_3d_condition.py:205,370; the VAE's conv_out, model.py:556-568).  W fp32 [Cout][3][3][C0].  Cout 3 or 4 for SEER_DT_BF16,
+ * 3 for SEER_DT_F16 (SEER_ENOSYS otherwise). */
 int seer_conv_out(const void* x, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                  const float* bias, int32_t Cout, float* y, void* stream);
-/* the VAE's conv_in / conv_out (ldm/modules/diffusionmodules/model.py:487-491,556-568) with the channels-last side stored
- * as `dtype` (SEER_DT_*); conv_out: Cout = 3 for SEER_DT_F16 */
-int seer_conv_in_dt(const float* x, int32_t B, int32_t Cin, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                    const float* bias, int32_t Cout, void* y, int32_t dtype, void* stream);
-int seer_conv_out_dt(const void* x, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                     const float* bias, int32_t Cout, float* y, int32_t dtype, void* stream);
+                  const float* bias, int32_t Cout, float* y, int32_t dtype, void* stream);
 
 /* pointwise channel mix on NCHW fp32: the VAE's post_quant_conv (1x1, 4->4; ldm/models/autoencoder.py:330-333).
  * W fp32 [Cout][Cin]. */
@@ -462,9 +426,7 @@ int seer_conv1x1_nchw_f32(const float* x, int32_t N, int32_t Cin, int32_t Cout, 
                           const float* bias, float* y, void* stream);
 
 /* layout / dtype conversion: fp32 [rows, C] -> bf16 (context, weights) */
-int seer_cast_f32_bf16(const float* x, int64_t n, void* y, void* stream);
-/* ... to the 16-bit storage type `dtype` (SEER_DT_*) */
-int seer_cast_f32_dt(const float* x, int64_t n, void* y, int32_t dtype, void* stream);
+int seer_cast_f32(const float* x, int64_t n, void* y, int32_t dtype, void* stream);
 /* NHWC bf16 -> NCHW fp32 and back (VAE boundary) */
 int seer_nchw_f32_to_nhwc_bf16(const float* x, int32_t N, int32_t C, int32_t HW, void* y, void* stream);
 int seer_nhwc_bf16_to_nchw_f32(const void* x, int32_t N, int32_t C, int32_t HW, float* y, void* stream);

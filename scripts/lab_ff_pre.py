@@ -1,4 +1,4 @@
-"""the fused feed-forward with the attention's to_out + residual as its prologue (seer_ff_fused_c320_pre) against the two launches it
+"""the fused feed-forward with the attention's to_out + residual as its prologue (seer_ff_fused_c320 with a != NULL) against the two launches it
 replaces, back to back inside a replayed hipGraph, at 24 576 rows.
 
     python scripts/lab_ff_pre.py > profiles/r06_lab_ff_pre.log

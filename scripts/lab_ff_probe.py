@@ -28,6 +28,9 @@ w1f, wcf = ops.ff_fused_pack(w1, wcat)
 flop = 2.0 * M * Cc * 2 * inner + 2.0 * M * (Cc + inner) * Cc
 NAMES = {1: "W1 stream", 2: "[Wp|WpW2] stream", 4: "MFMAs", 8: "GELU", 16: "fragment reads"}
 masks = [int(a) for a in sys.argv[1:]] or [0]
+vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+# a, lda, wof, bo (no prologue: NULL), h .. colsum_tiles, dtype (SEER_DT_BF16 = 0), stream
+FF_ARGTYPES = [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, C.c_float, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]
 out = ROOT / "gpurun_out" / "ffprobe"
 out.mkdir(parents=True, exist_ok=True)
 for mask in masks:
@@ -37,13 +40,12 @@ for mask in masks:
                     str(ROOT / "seervideoldm_amd" / "csrc" / "ff_fused.hip"), "-o", str(so)], check=True)
     lib = C.CDLL(str(so))
     fn = lib.seer_ff_fused_c320
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    fn.argtypes = [vp, i32, vp, i32, vp, i32, i64, vp, vp, C.c_float, vp, vp, vp, vp, vp, i64, i32, vp, vp]
+    fn.argtypes = FF_ARGTYPES
     st = torch.cuda.current_stream().cuda_stream
 
     def call():
-        rc = fn(h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
-                b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, st)
+        rc = fn(None, 0, None, None, h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
+                b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, 0, st)
         assert rc == 0, rc
     for _ in range(5):
         call()
@@ -65,10 +67,10 @@ subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", 
                 str(ROOT / "seervideoldm_amd" / "csrc" / "ff_fused.hip"), "-o", str(so)], check=True)
 lib = C.CDLL(str(so))
 fn = lib.seer_ff_fused_c320
-fn.argtypes = [vp, i32, vp, i32, vp, i32, i64, vp, vp, C.c_float, vp, vp, vp, vp, vp, i64, i32, vp, vp]
+fn.argtypes = FF_ARGTYPES
 for _ in range(3):
-    assert fn(h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
-              b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, st) == 0
+    assert fn(None, 0, None, None, h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
+              b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, 0, st) == 0
     torch.cuda.synchronize()
 buf = (C.c_longlong * (2 * 4 * 256))()
 assert lib.seer_lab_ff_stamps(buf) == 0

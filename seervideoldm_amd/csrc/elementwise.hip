@@ -548,70 +548,47 @@ int ensure_lds(K kernel, size_t bytes, std::atomic<bool>* done) {      // settin
 }
 
 extern "C" int seer_linear_smallm(const float* x, int32_t B, int32_t K, const void* W, const float* bias, int32_t N,
-                                  int32_t silu_in, int32_t silu_out, float* y, void* stream) {
-    return seer_linear_smallm_dt(x, B, K, W, bias, N, silu_in, silu_out, y, SEER_DT_BF16, stream);
-}
-extern "C" int seer_linear_smallm_dt(const float* x, int32_t B, int32_t K, const void* W, const float* bias, int32_t N,
-                                     int32_t silu_in, int32_t silu_out, float* y, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
+                                  int32_t silu_in, int32_t silu_out, float* y, int32_t dtype, void* stream) {
     if (!x || !W || !y || B <= 0 || B > 8 || K <= 0 || K % 8 || N <= 0) return SEER_EINVAL;
     const size_t lds = (size_t)B * K * sizeof(float);
-    const bf16* Wb = reinterpret_cast<const bf16*>(W);
     static std::atomic<bool> done[4] = {{false}, {false}, {false}, {false}};
-#define SEER_LSM(MB, R, H, GRID, FLAG)                                                                                              \
-    do {                                                                                                                            \
-        const int rc = ensure_lds(linear_smallm_kernel<MB, R, H>, lds, &done[FLAG]);                                                \
+    // the batch class is the outer choice, the storage type the inner one; FLAG: the first of the class's two `done` flags
+#define SEER_LSM(MB, R, GRID, FLAG)                                                                                                 \
+    seer_dispatch_dtype(dtype, [&](auto f16) {                                                                                      \
+        constexpr bool F16 = decltype(f16)::value;                                                                                  \
+        const int rc = ensure_lds(linear_smallm_kernel<MB, R, F16>, lds, &done[FLAG + !F16]);                                       \
         if (rc != SEER_OK) return rc;                                                                                               \
-        hipLaunchKernelGGL((linear_smallm_kernel<MB, R, H>), dim3(GRID), dim3(256), lds, S(stream), x, B, K, Wb, bias, N, silu_in,   \
-                           silu_out, y);                                                                                            \
-    } while (0)
-    if (B <= 2) {
-        if (dtype == SEER_DT_F16) SEER_LSM(2, 4, true, (N + 15) / 16, 0);
-        else SEER_LSM(2, 4, false, (N + 15) / 16, 1);
-    } else {
-        if (dtype == SEER_DT_F16) SEER_LSM(8, 2, true, (N + 7) / 8, 2);
-        else SEER_LSM(8, 2, false, (N + 7) / 8, 3);
-    }
+        hipLaunchKernelGGL((linear_smallm_kernel<MB, R, F16>), dim3(GRID), dim3(256), lds, S(stream), x, B, K,                      \
+                           reinterpret_cast<const bf16*>(W), bias, N, silu_in, silu_out, y);                                        \
+        SEER_LAUNCH_CHECK();                                                                                                        \
+        return SEER_OK;                                                                                                             \
+    })
+    if (B <= 2) return SEER_LSM(2, 4, (N + 15) / 16, 0);
+    return SEER_LSM(8, 2, (N + 7) / 8, 2);
 #undef SEER_LSM
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
 }
 
-extern "C" int seer_conv_in_dt(const float* x, int32_t B, int32_t Cin, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                               const float* bias, int32_t Cout, void* y, int32_t dtype, void* stream);
 extern "C" int seer_conv_in(const float* x, int32_t B, int32_t Cin, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                            const float* bias, int32_t Cout, void* y, void* stream) {
-    return seer_conv_in_dt(x, B, Cin, F, H, W_, Wt, bias, Cout, y, SEER_DT_BF16, stream);
-}
-extern "C" int seer_conv_in_dt(const float* x, int32_t B, int32_t Cin, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                               const float* bias, int32_t Cout, void* y, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    if (!x || !Wt || !y || B <= 0 || Cin <= 0 || F <= 0 || H <= 0 || W_ <= 0 || Cout <= 0 || Cout % 8 || Cout > 2048)
-        return SEER_EINVAL;
-    const int ppb = 32;
-    const size_t lds = ((size_t)9 * Cin * Cout + (size_t)ppb * 9 * Cin) * sizeof(float);
-    static std::atomic<bool> done{false}, done16{false};
-    const int rc = dtype == SEER_DT_F16 ? ensure_lds(conv_in_kernel<true>, lds, &done16) : ensure_lds(conv_in_kernel<false>, lds, &done);
-    if (rc != SEER_OK) return rc;
-    const int64_t npix = (int64_t)B * F * H * W_;
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL(conv_in_kernel<true>, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), lds, S(stream), x, B, Cin, F, H, W_,
-                           Wt, bias, Cout, reinterpret_cast<bf16*>(y), ppb);
-    else
-        hipLaunchKernelGGL(conv_in_kernel<false>, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), lds, S(stream), x, B, Cin, F, H, W_,
-                           Wt, bias, Cout, reinterpret_cast<bf16*>(y), ppb);
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+                            const float* bias, int32_t Cout, void* y, int32_t dtype, void* stream) {
+    static std::atomic<bool> done[2] = {{false}, {false}};
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        if (!x || !Wt || !y || B <= 0 || Cin <= 0 || F <= 0 || H <= 0 || W_ <= 0 || Cout <= 0 || Cout % 8 || Cout > 2048)
+            return SEER_EINVAL;
+        const int ppb = 32;
+        const size_t lds = ((size_t)9 * Cin * Cout + (size_t)ppb * 9 * Cin) * sizeof(float);
+        const int rc = ensure_lds(conv_in_kernel<F16>, lds, &done[F16]);
+        if (rc != SEER_OK) return rc;
+        const int64_t npix = (int64_t)B * F * H * W_;
+        hipLaunchKernelGGL(conv_in_kernel<F16>, dim3((unsigned)((npix + ppb - 1) / ppb)), dim3(256), lds, S(stream), x, B, Cin, F, H,
+                           W_, Wt, bias, Cout, reinterpret_cast<bf16*>(y), ppb);
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
-extern "C" int seer_conv_out_dt(const void* x, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                                const float* bias, int32_t Cout, float* y, int32_t dtype, void* stream);
 extern "C" int seer_conv_out(const void* x, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                             const float* bias, int32_t Cout, float* y, void* stream) {
-    return seer_conv_out_dt(x, B, C0, F, H, W_, Wt, bias, Cout, y, SEER_DT_BF16, stream);
-}
-extern "C" int seer_conv_out_dt(const void* x, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
-                                const float* bias, int32_t Cout, float* y, int32_t dtype, void* stream) {
+                             const float* bias, int32_t Cout, float* y, int32_t dtype, void* stream) {
     if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
     if (!x || !Wt || !y || B <= 0 || C0 <= 0 || C0 % 8 || F <= 0 || H <= 0 || W_ <= 0) return SEER_EINVAL;
     const int64_t npix = (int64_t)B * F * H * W_;
@@ -642,17 +619,15 @@ extern "C" int seer_conv_out_dt(const void* x, int32_t B, int32_t C0, int32_t F,
     return SEER_OK;
 }
 
-extern "C" int seer_cast_f32_bf16(const float* x, int64_t n, void* y, void* stream) { return seer_cast_f32_dt(x, n, y, SEER_DT_BF16, stream); }
-extern "C" int seer_cast_f32_dt(const float* x, int64_t n, void* y, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    if (!x || !y || n <= 0) return SEER_EINVAL;
-    const int64_t nt = (n + 3) / 4;
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL(cast_f32_bf16_kernel<true>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, S(stream), x, n, reinterpret_cast<bf16*>(y));
-    else
-        hipLaunchKernelGGL(cast_f32_bf16_kernel<false>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, S(stream), x, n, reinterpret_cast<bf16*>(y));
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+extern "C" int seer_cast_f32(const float* x, int64_t n, void* y, int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        if (!x || !y || n <= 0) return SEER_EINVAL;
+        const int64_t nt = (n + 3) / 4;
+        hipLaunchKernelGGL(cast_f32_bf16_kernel<decltype(f16)::value>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, S(stream), x, n,
+                           reinterpret_cast<bf16*>(y));
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 extern "C" int seer_nchw_f32_to_nhwc_bf16(const float* x, int32_t N, int32_t C, int32_t HW, void* y, void* stream) {
@@ -760,7 +735,7 @@ extern "C" int seer_gaussian_sample(const float* moments, int32_t N, int32_t C, 
     return SEER_OK;
 }
 
-extern "C" int seer_abi_version(void) { return 25; }
+extern "C" int seer_abi_version(void) { return 26; }
 extern "C" const char* seer_build_arch(void) { return "gfx950"; }
 extern "C" const char* seer_strerror(int code) {
     switch (code) {

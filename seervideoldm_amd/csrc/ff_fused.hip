@@ -74,7 +74,7 @@ struct FfArgs {
     int64_t* colsum_fx;                     // [reps][M / fx_rows][2][FF_C] fixed-point column sums (seer_gemm_desc::colsum_fx) or NULL
     int fx_rows, fx_reps;                   // rows per batch element (a multiple of 16, at least 96), replicas
     float* colsum_tiles;                    // [M / 96][FF_C][2] fp32 per-tile column sums (seer_gemm_desc::colsum) or NULL
-    // optional prologue (seer_ff_fused_c320_pre): the rows of `h` are h = h + a Wo^T + bo first -- the attention's to_out projection and
+    // optional prologue (a != NULL): the rows of `h` are h = h + a Wo^T + bo first -- the attention's to_out projection and
     // its residual (attention.py:316-322, 237-240), whose output nobody but this launch reads
     const bf16* a; int lda; const unsigned char* wof; const float* bo;
 };
@@ -621,27 +621,13 @@ extern "C" int seer_ff_fused_pack_wcat(const void* wcat, void* out, void* stream
     return SEER_OK;
 }
 
-extern "C" int seer_ff_fused_c320(const void* h, int32_t ldh, const void* x, int32_t ldx, void* y, int32_t ldy, int64_t M,
-                                  const float* gamma, const float* beta, float eps, const void* w1f, const float* b1, const void* wcf,
-                                  const float* bcat, int64_t* colsum_fx, int64_t fx_rows, int32_t fx_reps, float* colsum_tiles,
-                                  void* stream) {
-    return seer_ff_fused_c320_dt(h, ldh, x, ldx, y, ldy, M, gamma, beta, eps, w1f, b1, wcf, bcat, colsum_fx, fx_rows, fx_reps, colsum_tiles,
-                                 SEER_DT_BF16, stream);
-}
-extern "C" int seer_ff_fused_c320_dt(const void* h, int32_t ldh, const void* x, int32_t ldx, void* y, int32_t ldy, int64_t M,
-                                     const float* gamma, const float* beta, float eps, const void* w1f, const float* b1, const void* wcf,
-                                     const float* bcat, int64_t* colsum_fx, int64_t fx_rows, int32_t fx_reps, float* colsum_tiles,
-                                     int32_t dtype, void* stream) {
-    return seer_ff_fused_c320_pre(nullptr, 0, nullptr, nullptr, h, ldh, x, ldx, y, ldy, M, gamma, beta, eps, w1f, b1, wcf, bcat, colsum_fx, fx_rows,
-                                  fx_reps, colsum_tiles, dtype, stream);
-}
-extern "C" int seer_ff_fused_c320_pre(const void* a_in, int32_t lda, const void* wof, const float* bo, const void* h, int32_t ldh, const void* x,
-                                      int32_t ldx, void* y, int32_t ldy, int64_t M, const float* gamma, const float* beta, float eps,
-                                      const void* w1f, const float* b1, const void* wcf, const float* bcat, int64_t* colsum_fx, int64_t fx_rows,
-                                      int32_t fx_reps, float* colsum_tiles, int32_t dtype, void* stream) {
+extern "C" int seer_ff_fused_c320(const void* a_in, int32_t lda, const void* wof, const float* bo, const void* h, int32_t ldh, const void* x,
+                                  int32_t ldx, void* y, int32_t ldy, int64_t M, const float* gamma, const float* beta, float eps,
+                                  const void* w1f, const float* b1, const void* wcf, const float* bcat, int64_t* colsum_fx, int64_t fx_rows,
+                                  int32_t fx_reps, float* colsum_tiles, int32_t dtype, void* stream) {
     if (a_in && (!wof || !bo || lda % 8 || lda < FF_C || ldh % 4 ||
                  ((reinterpret_cast<uintptr_t>(a_in) | reinterpret_cast<uintptr_t>(wof) | reinterpret_cast<uintptr_t>(bo)) & 15))) return SEER_EINVAL;
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
+    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;      // before the attribute calls below touch the runtime
     if (!h || !x || !y || !gamma || !beta || !w1f || !b1 || !wcf || !bcat) return SEER_EINVAL;
     if (M <= 0 || M >= ((int64_t)1 << 31) - FF_BM || ldh % 8 || ldx % 8 || ldy % 8 || ldh < FF_C || ldx < FF_C || ldy < FF_C) return SEER_EINVAL;
     if ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w1f) |
@@ -663,14 +649,11 @@ extern "C" int seer_ff_fused_c320_pre(const void* a_in, int32_t lda, const void*
     a.colsum_fx = colsum_fx; a.fx_rows = (int)fx_rows; a.fx_reps = fx_reps; a.colsum_tiles = colsum_tiles;
     a.a = reinterpret_cast<const bf16*>(a_in); a.lda = lda; a.wof = reinterpret_cast<const unsigned char*>(wof); a.bo = bo;
     const dim3 grid((unsigned)((M + FF_BM - 1) / FF_BM));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (a_in) {
-        if (dtype == SEER_DT_F16) hipLaunchKernelGGL((seer_ff_fused_c320_kernel<true, true>), grid, dim3(256), FF_LDS, st, a);
-        else hipLaunchKernelGGL((seer_ff_fused_c320_kernel<false, true>), grid, dim3(256), FF_LDS, st, a);
-    } else {
-        if (dtype == SEER_DT_F16) hipLaunchKernelGGL((seer_ff_fused_c320_kernel<true, false>), grid, dim3(256), FF_LDS, st, a);
-        else hipLaunchKernelGGL((seer_ff_fused_c320_kernel<false, false>), grid, dim3(256), FF_LDS, st, a);
-    }
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        auto kernel = a_in ? seer_ff_fused_c320_kernel<F16, true> : seer_ff_fused_c320_kernel<F16, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), FF_LDS, reinterpret_cast<hipStream_t>(stream), a);
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }

@@ -571,37 +571,27 @@ extern "C" int64_t seer_groupnorm_workspace_floats(int32_t C, int32_t batch, int
     return (int64_t)batch * g.nblk * groups * 2;
 }
 
-extern "C" int seer_groupnorm_stats_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                                       int64_t rows_per_batch, int32_t groups, float* stats, float* workspace,
-                                       int32_t dtype, void* stream);
 extern "C" int seer_groupnorm_stats(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
                                     int64_t rows_per_batch, int32_t groups, float* stats, float* workspace,
-                                    void* stream) {
-    return seer_groupnorm_stats_dt(x1, C1, x2, C2, batch, rows_per_batch, groups, stats, workspace, SEER_DT_BF16, stream);
-}
-extern "C" int seer_groupnorm_stats_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                                       int64_t rows_per_batch, int32_t groups, float* stats, float* workspace,
-                                       int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    GnGeom g;
-    if (!x1 || !stats || !workspace || batch <= 0 || rows_per_batch <= 0) return SEER_EINVAL;
-    if (!x2) C2 = 0;
-    if (!gn_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_EINVAL;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int cpp = g.ncols < 256 ? g.ncols : 256;
-    const size_t lds = (size_t)(256 / cpp) * g.ncols * 4 * sizeof(float);
-    dim3 grid((unsigned)g.nblk, batch);
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL(gn_stats_kernel<true>, grid, dim3(256), lds, st, reinterpret_cast<const bf16*>(x1),
+                                    int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        GnGeom g;
+        if (!x1 || !stats || !workspace || batch <= 0 || rows_per_batch <= 0) return SEER_EINVAL;
+        if (!x2) C2 = 0;
+        if (!gn_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_EINVAL;
+        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+        const int cpp = g.ncols < 256 ? g.ncols : 256;
+        const size_t lds = (size_t)(256 / cpp) * g.ncols * 4 * sizeof(float);
+        dim3 grid((unsigned)g.nblk, batch);
+        hipLaunchKernelGGL(gn_stats_kernel<F16>, grid, dim3(256), lds, st, reinterpret_cast<const bf16*>(x1),
                            reinterpret_cast<const bf16*>(x2), g, rows_per_batch, groups, workspace);
-    else
-        hipLaunchKernelGGL(gn_stats_kernel<false>, grid, dim3(256), lds, st, reinterpret_cast<const bf16*>(x1),
-                           reinterpret_cast<const bf16*>(x2), g, rows_per_batch, groups, workspace);
-    SEER_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((batch * groups * 2 + 3) / 4)), dim3(256), 0, st, workspace, g.nblk, groups,
-                       batch, stats);
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+        SEER_LAUNCH_CHECK();
+        hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((batch * groups * 2 + 3) / 4)), dim3(256), 0, st, workspace, g.nblk,
+                           groups, batch, stats);
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 extern "C" int seer_groupnorm_stats_from_colsums(const float* cs1, int32_t C1, int32_t phases1, int32_t tiles1,
@@ -618,110 +608,75 @@ extern "C" int seer_groupnorm_stats_from_colsums(const float* cs1, int32_t C1, i
     return SEER_OK;
 }
 
-extern "C" int seer_groupnorm_apply_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                                       int64_t rows_per_batch, int32_t groups, const float* stats, double count,
-                                       float eps, const float* gamma, const float* beta, int32_t silu, void* y,
-                                       int32_t dtype, void* stream);
 extern "C" int seer_groupnorm_apply(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
                                     int64_t rows_per_batch, int32_t groups, const float* stats, double count,
                                     float eps, const float* gamma, const float* beta, int32_t silu, void* y,
-                                    void* stream) {
-    return seer_groupnorm_apply_dt(x1, C1, x2, C2, batch, rows_per_batch, groups, stats, count, eps, gamma, beta, silu, y,
-                                   SEER_DT_BF16, stream);
-}
-extern "C" int seer_groupnorm_apply_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, int32_t batch,
-                                       int64_t rows_per_batch, int32_t groups, const float* stats, double count,
-                                       float eps, const float* gamma, const float* beta, int32_t silu, void* y,
-                                       int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    GnGeom g;
-    if (!x1 || !stats || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
-    if (!x2) C2 = 0;
-    if (!gn_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_EINVAL;
-    dim3 grid((unsigned)g.nblk, batch);
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL(gn_apply_kernel<true>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                                    int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        GnGeom g;
+        if (!x1 || !stats || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
+        if (!x2) C2 = 0;
+        if (!gn_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_EINVAL;
+        dim3 grid((unsigned)g.nblk, batch);
+        hipLaunchKernelGGL(gn_apply_kernel<F16>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                            reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), g, rows_per_batch, groups,
                            stats, (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y));
-    else
-        hipLaunchKernelGGL(gn_apply_kernel<false>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), g, rows_per_batch, groups,
-                           stats, (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y));
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 extern "C" int seer_groupnorm_apply_from_colsums(const void* x1, int32_t C1, const void* x2, int32_t C2, const float* cs1,
                                                  int32_t phases1, int32_t tiles1, const float* cs2, int32_t phases2,
                                                  int32_t tiles2, int32_t batch, int64_t rows_per_batch, int32_t groups,
                                                  double count, float eps, const float* gamma, const float* beta,
-                                                 int32_t silu, void* y, void* stream) {
-    return seer_groupnorm_apply_from_colsums_dt(x1, C1, x2, C2, cs1, phases1, tiles1, cs2, phases2, tiles2, batch, rows_per_batch, groups,
-                                                count, eps, gamma, beta, silu, y, SEER_DT_BF16, stream);
-}
-extern "C" int seer_groupnorm_apply_from_colsums_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, const float* cs1,
-                                                    int32_t phases1, int32_t tiles1, const float* cs2, int32_t phases2,
-                                                    int32_t tiles2, int32_t batch, int64_t rows_per_batch, int32_t groups,
-                                                    double count, float eps, const float* gamma, const float* beta,
-                                                    int32_t silu, void* y, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    if (!x1 || !cs1 || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
-    if (phases1 <= 0 || tiles1 <= 0 || tiles1 % batch) return SEER_EINVAL;
-    if (!x2) C2 = 0;
-    if (C2 > 0 && (!cs2 || phases2 <= 0 || tiles2 <= 0 || tiles2 % batch)) return SEER_EINVAL;
-    GnCsGeom g;
-    if (!gn_cs_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_ENOSYS;
-    // Where the one-launch form wins (profiles/r04_gn_fused.log, inside a hipGraph): few partials per batch element and a small
-    // tensor -- the 16x16 level down.  At the 32x32 level every one of ~512 blocks re-reads 82 KB of partials (42 MB per launch)
-    // and the two launches are faster (11.3 vs 13.3 us); the caller keeps them there.
-    {
-        const int64_t parts = (int64_t)phases1 * (tiles1 / batch) > (C2 ? (int64_t)phases2 * (tiles2 / batch) : 0)
-                                  ? (int64_t)phases1 * (tiles1 / batch) : (int64_t)phases2 * (tiles2 / batch);
-        if (parts > 32 || rows_per_batch * (int64_t)(C1 + C2) > (int64_t)4200000) return SEER_ENOSYS;
-    }
-    const GnColsumSrc s1{cs1, C1, phases1, tiles1}, s2{cs2, C2, C2 ? phases2 : 0, C2 ? tiles2 : 0};
-    dim3 grid((unsigned)(g.nslice * g.nrowblk), batch);
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL((gn_apply_cs_kernel<false, true>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                                                 int32_t silu, void* y, int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        if (!x1 || !cs1 || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
+        if (phases1 <= 0 || tiles1 <= 0 || tiles1 % batch) return SEER_EINVAL;
+        if (!x2) C2 = 0;
+        if (C2 > 0 && (!cs2 || phases2 <= 0 || tiles2 <= 0 || tiles2 % batch)) return SEER_EINVAL;
+        GnCsGeom g;
+        if (!gn_cs_geom(C1, C2, groups, batch, rows_per_batch, &g)) return SEER_ENOSYS;
+        // Where the one-launch form wins (profiles/r04_gn_fused.log, inside a hipGraph): few partials per batch element and a small
+        // tensor -- the 16x16 level down.  At the 32x32 level every one of ~512 blocks re-reads 82 KB of partials (42 MB per launch)
+        // and the two launches are faster (11.3 vs 13.3 us); the caller keeps them there.
+        {
+            const int64_t parts = (int64_t)phases1 * (tiles1 / batch) > (C2 ? (int64_t)phases2 * (tiles2 / batch) : 0)
+                                      ? (int64_t)phases1 * (tiles1 / batch) : (int64_t)phases2 * (tiles2 / batch);
+            if (parts > 32 || rows_per_batch * (int64_t)(C1 + C2) > (int64_t)4200000) return SEER_ENOSYS;
+        }
+        const GnColsumSrc s1{cs1, C1, phases1, tiles1}, s2{cs2, C2, C2 ? phases2 : 0, C2 ? tiles2 : 0};
+        dim3 grid((unsigned)(g.nslice * g.nrowblk), batch);
+        hipLaunchKernelGGL((gn_apply_cs_kernel<false, F16>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                            reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), s1, s2, g, batch, rows_per_batch,
                            (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y), (float*)nullptr);
-    else
-        hipLaunchKernelGGL((gn_apply_cs_kernel<false, false>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), s1, s2, g, batch, rows_per_batch,
-                           (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y), (float*)nullptr);
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 extern "C" int seer_groupnorm_apply_fx(const void* x1, int32_t C1, const void* x2, int32_t C2, const int64_t* fx1, int32_t reps1,
                                        const int64_t* fx2, int32_t reps2, int32_t batch, int64_t rows_per_batch, int32_t groups,
                                        double count, float eps, const float* gamma, const float* beta, int32_t silu, void* y,
-                                       float* stats_out, void* stream) {
-    return seer_groupnorm_apply_fx_dt(x1, C1, x2, C2, fx1, reps1, fx2, reps2, batch, rows_per_batch, groups, count, eps, gamma, beta, silu,
-                                      y, stats_out, SEER_DT_BF16, stream);
-}
-extern "C" int seer_groupnorm_apply_fx_dt(const void* x1, int32_t C1, const void* x2, int32_t C2, const int64_t* fx1, int32_t reps1,
-                                          const int64_t* fx2, int32_t reps2, int32_t batch, int64_t rows_per_batch, int32_t groups,
-                                          double count, float eps, const float* gamma, const float* beta, int32_t silu, void* y,
-                                          float* stats_out, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    if (!x1 || !fx1 || reps1 < 1 || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
-    if (!x2) C2 = 0;
-    if (C2 > 0 && (!fx2 || reps2 < 1)) return SEER_EINVAL;
-    GnCsGeom g;
-    if (!gn_cs_geom(C1, C2, groups, batch, rows_per_batch, &g, SEER_GN_FX_BLOCKS)) return SEER_ENOSYS;
-    const GnColsumSrc s1{reinterpret_cast<const float*>(fx1), C1, reps1, batch}, s2{reinterpret_cast<const float*>(fx2), C2, C2 ? reps2 : 0, batch};
-    dim3 grid((unsigned)(g.nslice * g.nrowblk), batch);
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL((gn_apply_cs_kernel<true, true>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                                       float* stats_out, int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        if (!x1 || !fx1 || reps1 < 1 || !gamma || !beta || !y || batch <= 0 || rows_per_batch <= 0 || count <= 0) return SEER_EINVAL;
+        if (!x2) C2 = 0;
+        if (C2 > 0 && (!fx2 || reps2 < 1)) return SEER_EINVAL;
+        GnCsGeom g;
+        if (!gn_cs_geom(C1, C2, groups, batch, rows_per_batch, &g, SEER_GN_FX_BLOCKS)) return SEER_ENOSYS;
+        const GnColsumSrc s1{reinterpret_cast<const float*>(fx1), C1, reps1, batch}, s2{reinterpret_cast<const float*>(fx2), C2, C2 ? reps2 : 0, batch};
+        dim3 grid((unsigned)(g.nslice * g.nrowblk), batch);
+        hipLaunchKernelGGL((gn_apply_cs_kernel<true, F16>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                            reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), s1, s2, g, batch, rows_per_batch,
                            (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y), stats_out);
-    else
-        hipLaunchKernelGGL((gn_apply_cs_kernel<true, false>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                           reinterpret_cast<const bf16*>(x1), reinterpret_cast<const bf16*>(x2), s1, s2, g, batch, rows_per_batch,
-                           (float)(1.0 / count), eps, gamma, beta, silu, reinterpret_cast<bf16*>(y), stats_out);
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 // (sum, sum of squares) per (batch element, column) in the 64-bit fixed point of seer_gemm_desc::colsum_fx, from the activations:
@@ -777,79 +732,56 @@ __global__ void __launch_bounds__(256) gn_stats_fx_kernel(const bf16* __restrict
 
 extern "C" int seer_groupnorm_stats_fx(const void* x, int32_t C, int32_t batch, int64_t rows_per_batch, int64_t* fx, int32_t dtype,
                                        void* stream) {
-    if (!x || !fx || C <= 0 || C % 8 || batch <= 0 || rows_per_batch <= 0) return SEER_EINVAL;
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    // ~2 blocks per CU at least, at most 64 adds per address
-    int rpb = 256;
-    while (rpb > 16 && (int64_t)batch * ((rows_per_batch + rpb - 1) / rpb) * ((C / 8 + 63) / 64) < 512) rpb >>= 1;
-    while ((rows_per_batch + rpb - 1) / rpb > 64) rpb <<= 1;
-    dim3 grid((unsigned)((C / 8 + 63) / 64), (unsigned)((rows_per_batch + rpb - 1) / rpb), (unsigned)batch);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (dtype == SEER_DT_F16)
-        hipLaunchKernelGGL(gn_stats_fx_kernel<true>, grid, dim3(256), 0, st, reinterpret_cast<const bf16*>(x), C, rows_per_batch, rpb,
-                           reinterpret_cast<long long*>(fx));
-    else
-        hipLaunchKernelGGL(gn_stats_fx_kernel<false>, grid, dim3(256), 0, st, reinterpret_cast<const bf16*>(x), C, rows_per_batch, rpb,
-                           reinterpret_cast<long long*>(fx));
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        if (!x || !fx || C <= 0 || C % 8 || batch <= 0 || rows_per_batch <= 0) return SEER_EINVAL;
+        // ~2 blocks per CU at least, at most 64 adds per address
+        int rpb = 256;
+        while (rpb > 16 && (int64_t)batch * ((rows_per_batch + rpb - 1) / rpb) * ((C / 8 + 63) / 64) < 512) rpb >>= 1;
+        while ((rows_per_batch + rpb - 1) / rpb > 64) rpb <<= 1;
+        dim3 grid((unsigned)((C / 8 + 63) / 64), (unsigned)((rows_per_batch + rpb - 1) / rpb), (unsigned)batch);
+        hipLaunchKernelGGL(gn_stats_fx_kernel<F16>, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                           reinterpret_cast<const bf16*>(x), C, rows_per_batch, rpb, reinterpret_cast<long long*>(fx));
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
 extern "C" int seer_layernorm(const void* x, int64_t rows, int32_t C, int32_t ldx, const float* gamma,
-                              const float* beta, float eps, void* y, int32_t ldy, void* stream) {
-    return seer_layernorm_dt(x, rows, C, ldx, gamma, beta, eps, y, ldy, SEER_DT_BF16, stream);
-}
-extern "C" int seer_layernorm_dt(const void* x, int64_t rows, int32_t C, int32_t ldx, const float* gamma,
-                                 const float* beta, float eps, void* y, int32_t ldy, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
-    if (!x || !y || !gamma || !beta || rows <= 0 || C <= 0 || C % 8 || ldx % 8 || ldy % 8) return SEER_EINVAL;
-    if (C > 64 * 8 * 3) return SEER_ENOSYS;
-    int64_t blocks = (rows + 3) / 4;
-    if (blocks > 4096) blocks = 4096;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bf16* xb = reinterpret_cast<const bf16*>(x);
-    bf16* yb = reinterpret_cast<bf16*>(y);
-#define SEER_LN_LAUNCH(MC, H) hipLaunchKernelGGL((layernorm_kernel<MC, H>), dim3((unsigned)blocks), dim3(256), 0, st, xb, rows, C, ldx, gamma, beta, eps, yb, ldy)
-    if (dtype == SEER_DT_F16) {
-        if (C <= 512) SEER_LN_LAUNCH(1, true);
-        else if (C <= 1024) SEER_LN_LAUNCH(2, true);
-        else SEER_LN_LAUNCH(3, true);
-    } else {
-        if (C <= 512) SEER_LN_LAUNCH(1, false);
-        else if (C <= 1024) SEER_LN_LAUNCH(2, false);
-        else SEER_LN_LAUNCH(3, false);
-    }
-#undef SEER_LN_LAUNCH
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+                              const float* beta, float eps, void* y, int32_t ldy, int32_t dtype, void* stream) {
+    return seer_dispatch_dtype(dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        if (!x || !y || !gamma || !beta || rows <= 0 || C <= 0 || C % 8 || ldx % 8 || ldy % 8) return SEER_EINVAL;
+        if (C > 64 * 8 * 3) return SEER_ENOSYS;
+        int64_t blocks = (rows + 3) / 4;
+        if (blocks > 4096) blocks = 4096;
+        auto kernel = layernorm_kernel<1, F16>;              // 512 columns per pass over the row's registers
+        if (C > 512) kernel = layernorm_kernel<2, F16>;
+        if (C > 1024) kernel = layernorm_kernel<3, F16>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                           reinterpret_cast<const bf16*>(x), rows, C, ldx, gamma, beta, eps, reinterpret_cast<bf16*>(y), ldy);
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }
 
-extern "C" int seer_softmax_rows_dt(const void* x, int32_t x_is_f32, int64_t rows, int32_t n, int32_t ld, float scale,
-                                    void* y, int32_t ldy, int32_t dtype, void* stream);
 extern "C" int seer_softmax_rows(const void* x, int32_t x_is_f32, int64_t rows, int32_t n, int32_t ld, float scale,
-                                 void* y, int32_t ldy, void* stream) {
-    return seer_softmax_rows_dt(x, x_is_f32, rows, n, ld, scale, y, ldy, SEER_DT_BF16, stream);
-}
-extern "C" int seer_softmax_rows_dt(const void* x, int32_t x_is_f32, int64_t rows, int32_t n, int32_t ld, float scale,
-                                    void* y, int32_t ldy, int32_t dtype, void* stream) {
-    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;
+                                 void* y, int32_t ldy, int32_t dtype, void* stream) {
+    if (dtype != SEER_DT_BF16 && dtype != SEER_DT_F16) return SEER_EINVAL;      // ahead of the SEER_ENOSYS below
     if (!x || !y || rows <= 0 || n <= 0 || n % 8 || ld % 8 || ldy % 8) return SEER_EINVAL;
     if (n > 64 * 8 * 8) return SEER_ENOSYS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    bf16* yb = reinterpret_cast<bf16*>(y);
-    dim3 grid((unsigned)((rows + 3) / 4));
+    // the size class is the outer choice, the storage type the inner one
 #define SEER_SM(MC)                                                                                                   \
-    do {                                                                                                              \
-        if (dtype == SEER_DT_F16) {                                                                                   \
-            if (x_is_f32) hipLaunchKernelGGL((softmax_rows_kernel<MC, true, true>), grid, dim3(256), 0, st, x, rows, n, ld, scale, yb, ldy); \
-            else hipLaunchKernelGGL((softmax_rows_kernel<MC, false, true>), grid, dim3(256), 0, st, x, rows, n, ld, scale, yb, ldy);         \
-        } else if (x_is_f32) hipLaunchKernelGGL((softmax_rows_kernel<MC, true>), grid, dim3(256), 0, st, x, rows, n, ld, scale, yb, ldy); \
-        else hipLaunchKernelGGL((softmax_rows_kernel<MC, false>), grid, dim3(256), 0, st, x, rows, n, ld, scale, yb, ldy);         \
-    } while (0)
-    if (n <= 1024) SEER_SM(2);
-    else if (n <= 2048) SEER_SM(4);
-    else SEER_SM(8);
+    seer_dispatch_dtype(dtype, [&](auto f16) {                                                                        \
+        constexpr bool F16 = decltype(f16)::value;                                                                    \
+        auto kernel = x_is_f32 ? softmax_rows_kernel<MC, true, F16> : softmax_rows_kernel<MC, false, F16>;            \
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, rows, n, \
+                           ld, scale, reinterpret_cast<bf16*>(y), ldy);                                               \
+        SEER_LAUNCH_CHECK();                                                                                          \
+        return SEER_OK;                                                                                               \
+    })
+    if (n <= 1024) return SEER_SM(2);
+    if (n <= 2048) return SEER_SM(4);
+    return SEER_SM(8);
 #undef SEER_SM
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
 }

@@ -414,7 +414,7 @@ extern "C" int seer_rowchain_pack(const void* W, int32_t ld, int32_t n_mats, voi
 
 extern "C" int seer_rowchain_c320(const seer_rowchain_desc* d, void* stream) {
     if (!d || !d->inp || !d->w1f || d->M <= 0 || d->M >= (1ll << 31) - RC_BM) return SEER_EINVAL;
-    if (d->dtype != SEER_DT_BF16 && d->dtype != SEER_DT_F16) return SEER_EINVAL;
+    if (d->dtype != SEER_DT_BF16 && d->dtype != SEER_DT_F16) return SEER_EINVAL;     // ahead of the SEER_ENOSYS below
     if (d->ld_in % 8 || d->ld_in < RC_C) return SEER_EINVAL;
     if (!d->h && !d->w2f) return SEER_EINVAL;
     if (d->h && (d->ldh % 8 || d->ldh < RC_C)) return SEER_EINVAL;
@@ -460,14 +460,11 @@ extern "C" int seer_rowchain_c320(const seer_rowchain_desc* d, void* stream) {
     a.M = (int)d->M;
     const dim3 grid((unsigned)((d->M + RC_BM - 1) / RC_BM));
     const bool full = d->M % RC_BM == 0 && d->h != nullptr;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d->dtype == SEER_DT_F16) {
-        if (full) hipLaunchKernelGGL((seer_rowchain_c320_kernel<true, true>), grid, dim3(256), RC_LDS, st, a);
-        else hipLaunchKernelGGL((seer_rowchain_c320_kernel<true, false>), grid, dim3(256), RC_LDS, st, a);
-    } else {
-        if (full) hipLaunchKernelGGL((seer_rowchain_c320_kernel<false, true>), grid, dim3(256), RC_LDS, st, a);
-        else hipLaunchKernelGGL((seer_rowchain_c320_kernel<false, false>), grid, dim3(256), RC_LDS, st, a);
-    }
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+    return seer_dispatch_dtype(d->dtype, [&](auto f16) {
+        constexpr bool F16 = decltype(f16)::value;
+        auto kernel = full ? seer_rowchain_c320_kernel<F16, true> : seer_rowchain_c320_kernel<F16, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), RC_LDS, reinterpret_cast<hipStream_t>(stream), a);
+        SEER_LAUNCH_CHECK();
+        return SEER_OK;
+    });
 }

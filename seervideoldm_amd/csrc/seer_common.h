@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "seer_hip.h"
 
 typedef __bf16 bf16;
@@ -42,7 +43,7 @@ __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
     return v;
 }
 
-// the same for IEEE half storage (the VAE path, SEER_EPI_F16 / the *_dt entry points with dtype = SEER_DT_F16).  Scalar
+// the same for IEEE half storage (the VAE path, SEER_EPI_F16 / the entry points with dtype = SEER_DT_F16).  Scalar
 // conversions on the two 16-bit halves of a dword: the ext_vector_type(2) _Float16 form of these loops compiled to code that
 // read element 0 twice (ROCm 7.2; scripts/dbg_gn.py: y[.., 2] == y[.., 0])
 __device__ __forceinline__ float half_bits_to_f32(unsigned int b) {
@@ -231,6 +232,16 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The one bf16 / fp16 fork of the host code: a runtime SEER_DT_* becomes a compile-time bool.  `launch` is a generic lambda that
+// takes std::true_type (IEEE half) or std::false_type (bf16), uses its ::value as the kernels' F16 template argument and returns a
+// SEER_* code; any other dtype is SEER_EINVAL and `launch` does not run.
+template <typename Launch>
+inline int seer_dispatch_dtype(int32_t dtype, Launch&& launch) {
+    if (dtype == SEER_DT_F16) return launch(std::true_type{});
+    if (dtype == SEER_DT_BF16) return launch(std::false_type{});
+    return SEER_EINVAL;
 }
 
 #define SEER_LAUNCH_CHECK()                                   \

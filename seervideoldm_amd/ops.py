@@ -486,7 +486,7 @@ def groupnorm_stats(x1: torch.Tensor, x2: Optional[torch.Tensor], batch: int, gr
     if nws < 0:
         check(int(nws), "seer_groupnorm_workspace_floats")
     ws = torch.empty((nws,), device=x1.device, dtype=torch.float32)
-    check(lib.seer_groupnorm_stats_dt(_p(x1), x1.shape[1], _p(x2), C2, batch, rows, groups, _p(stats), _p(ws), dt,
+    check(lib.seer_groupnorm_stats(_p(x1), x1.shape[1], _p(x2), C2, batch, rows, groups, _p(stats), _p(ws), dt,
                                    _stream()), "seer_groupnorm_stats")
     return stats
 
@@ -512,9 +512,9 @@ def groupnorm_apply(x1: torch.Tensor, x2: Optional[torch.Tensor], batch: int, gr
         out = torch.empty((x1.shape[0], Ct), device=x1.device, dtype=x1.dtype)
     _req16(out, "out", x1)
     _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta")
-    check(_lib.load().seer_groupnorm_apply_dt(_p(x1), x1.shape[1], _p(x2), C2, batch, rows, groups, _p(stats),
-                                              float(count), float(eps), _p(gamma), _p(beta), int(silu), _p(out), dt,
-                                              _stream()), "seer_groupnorm_apply")
+    check(_lib.load().seer_groupnorm_apply(_p(x1), x1.shape[1], _p(x2), C2, batch, rows, groups, _p(stats),
+                                           float(count), float(eps), _p(gamma), _p(beta), int(silu), _p(out), dt,
+                                           _stream()), "seer_groupnorm_apply")
     return out
 
 
@@ -531,7 +531,7 @@ def groupnorm_apply_from_colsums(x1: torch.Tensor, x2: Optional[torch.Tensor], c
     if out is None:
         out = torch.empty((x1.shape[0], x1.shape[1] + C2), device=x1.device, dtype=x1.dtype)
     _req(gamma, torch.float32, "gamma"); _req(beta, torch.float32, "beta")
-    rc = _lib.load().seer_groupnorm_apply_from_colsums_dt(
+    rc = _lib.load().seer_groupnorm_apply_from_colsums(
         _p(x1), x1.shape[1], _p(x2), C2, _p(cs1.buf), cs1.phases, cs1.tiles, _p(cs2.buf) if cs2 is not None else None,
         cs2.phases if cs2 is not None else 0, cs2.tiles if cs2 is not None else 0, batch, rows, groups, float(count), float(eps),
         _p(gamma), _p(beta), int(silu), _p(out), dt, _stream())
@@ -559,10 +559,10 @@ def groupnorm_apply_fx(x1: torch.Tensor, x2: Optional[torch.Tensor], fx1: ColSum
     if stats_out is not None:
         _req(stats_out, torch.float32, "stats_out")
         assert stats_out.shape == (batch, groups, 2) and stats_out.is_contiguous()
-    rc = _lib.load().seer_groupnorm_apply_fx_dt(_p(x1), x1.shape[1], _p(x2), C2, _p(fx1.buf), fx1.reps,
-                                                _p(fx2.buf) if x2 is not None else None, fx2.reps if x2 is not None else 0, batch, rows,
-                                                groups, float(count), float(eps), _p(gamma), _p(beta), int(silu), _p(out),
-                                                _p(stats_out), dt, _stream())
+    rc = _lib.load().seer_groupnorm_apply_fx(_p(x1), x1.shape[1], _p(x2), C2, _p(fx1.buf), fx1.reps,
+                                             _p(fx2.buf) if x2 is not None else None, fx2.reps if x2 is not None else 0, batch, rows,
+                                             groups, float(count), float(eps), _p(gamma), _p(beta), int(silu), _p(out),
+                                             _p(stats_out), dt, _stream())
     if rc == _lib.SEER_ENOSYS:
         return None
     check(rc, "seer_groupnorm_apply_fx")
@@ -597,8 +597,8 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     if out is None:
         out = torch.empty((x.shape[0], x.shape[1]), device=x.device, dtype=x.dtype)
     _req16(out, "out", x)
-    check(_lib.load().seer_layernorm_dt(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(gamma), _p(beta), float(eps),
-                                        _p(out), out.stride(0), dt, _stream()), "seer_layernorm")
+    check(_lib.load().seer_layernorm(_p(x), x.shape[0], x.shape[1], x.stride(0), _p(gamma), _p(beta), float(eps),
+                                     _p(out), out.stride(0), dt, _stream()), "seer_layernorm")
     return out
 
 
@@ -652,7 +652,7 @@ def ff_fused(h: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: torch.
     ff_fused_pack; b1 in the interleaved GEGLU row order, bcat = Wp b2 + bp.  colsum_batch as in gemm(): (B, arena) -> out.colsums =
     the ColSumsFx of y, B -> the per-tile ColSums (96-row tiles; only where no tile straddles two batch elements).
     pre = (a, wof, bo): the rows the launch reads as h are h + a Wo^T + bo -- the attention's to_out projection and its residual, in
-    the same launch (seer_ff_fused_c320_pre; wof = rowchain_pack(Wo)); h itself is not written.  Returns None (nothing launched) when
+    the same launch (wof = rowchain_pack(Wo)); h itself is not written.  Returns None (nothing launched) when
     the shape is not the kernel's: C = 320."""
     M, Cc = h.shape
     if Cc != FF_FUSED_C or M == 0:
@@ -680,10 +680,10 @@ def ff_fused(h: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, beta: torch.
         _req16(a, "pre a", h); _req16(wof, "pre wof", h); _req(bo, torch.float32, "pre bo")
         assert a.shape == h.shape and a.stride(1) == 1 and wof.numel() == Cc * Cc and wof.is_contiguous() and bo.numel() == Cc
         pa, lda, pw, pb = _p(a), a.stride(0), _p(wof), _p(bo)
-    check(_lib.load().seer_ff_fused_c320_pre(pa, lda, pw, pb, _p(h), h.stride(0), _p(x), x.stride(0), _p(out), out.stride(0), M, _p(gamma),
-                                             _p(beta), float(eps), _p(w1f), _p(b1), _p(wcf), _p(bcat),
-                                             fx.data_ptr() if fx is not None else None, fx_rows, fx.shape[0] if fx is not None else 0,
-                                             _p(tiles) if tiles is not None else None, dt, _stream()), "seer_ff_fused_c320")
+    check(_lib.load().seer_ff_fused_c320(pa, lda, pw, pb, _p(h), h.stride(0), _p(x), x.stride(0), _p(out), out.stride(0), M, _p(gamma),
+                                         _p(beta), float(eps), _p(w1f), _p(b1), _p(wcf), _p(bcat),
+                                         fx.data_ptr() if fx is not None else None, fx_rows, fx.shape[0] if fx is not None else 0,
+                                         _p(tiles) if tiles is not None else None, dt, _stream()), "seer_ff_fused_c320")
     out.colsums = cs
     out.rowstats = None
     return out
@@ -795,8 +795,8 @@ def softmax_rows(x: torch.Tensor, scale: float, out: Optional[torch.Tensor] = No
     ldy = out.reshape(-1, out.shape[-1]).stride(0)        # `out` may be wider than x (zero-padded contraction of the next GEMM)
     dt = _req16(out, "out", None if x.dtype == torch.float32 else x)
     assert out.shape[-1] >= x2.shape[1] and out.numel() // out.shape[-1] == x2.shape[0]
-    check(_lib.load().seer_softmax_rows_dt(_p(x2), int(x.dtype == torch.float32), x2.shape[0], x2.shape[1], x2.stride(0),
-                                           float(scale), _p(out), ldy, dt, _stream()), "seer_softmax_rows")
+    check(_lib.load().seer_softmax_rows(_p(x2), int(x.dtype == torch.float32), x2.shape[0], x2.shape[1], x2.stride(0),
+                                        float(scale), _p(out), ldy, dt, _stream()), "seer_softmax_rows")
     return out
 
 
@@ -830,8 +830,8 @@ def linear_smallm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
     B, K = x.shape
     N = w.shape[0]
     y = torch.empty((B, N), device=x.device, dtype=torch.float32)
-    check(_lib.load().seer_linear_smallm_dt(_p(x), B, K, _p(w), _p(bias), N, int(silu_in), int(silu_out), _p(y), dt,
-                                            _stream()), "seer_linear_smallm")
+    check(_lib.load().seer_linear_smallm(_p(x), B, K, _p(w), _p(bias), N, int(silu_in), int(silu_out), _p(y), dt,
+                                         _stream()), "seer_linear_smallm")
     return y
 
 
@@ -843,7 +843,7 @@ def conv_in(x: torch.Tensor, w_khwc: torch.Tensor, bias: torch.Tensor, dtype=bf1
     Cout = w_khwc.shape[-1]
     y = torch.empty((B * F * H * W, Cout), device=x.device, dtype=dtype)
     dt = _req16(y, "y")
-    check(_lib.load().seer_conv_in_dt(_p(x), B, Cin, F, H, W, _p(w_khwc), _p(bias), Cout, _p(y), dt, _stream()),
+    check(_lib.load().seer_conv_in(_p(x), B, Cin, F, H, W, _p(w_khwc), _p(bias), Cout, _p(y), dt, _stream()),
           "seer_conv_in")
     return y
 
@@ -874,7 +874,7 @@ def conv_out(x: torch.Tensor, w_ohwc: torch.Tensor, bias: torch.Tensor, B: int, 
         _launch_gemm(d, x.device, "seer_gemm_bf16(conv_out)")
         return y
     _req(w_ohwc, torch.float32, "w")
-    check(_lib.load().seer_conv_out_dt(_p(x), B, x.shape[1], F, H, W, _p(w_ohwc), _p(bias), Cout, _p(y), dt, _stream()),
+    check(_lib.load().seer_conv_out(_p(x), B, x.shape[1], F, H, W, _p(w_ohwc), _p(bias), Cout, _p(y), dt, _stream()),
           "seer_conv_out")
     return y
 
@@ -884,7 +884,7 @@ def cast_bf16(x: torch.Tensor, dtype=bf16) -> torch.Tensor:
     _req(x, torch.float32, "x")
     x = x.contiguous()
     y = torch.empty(x.shape, device=x.device, dtype=dtype)
-    check(_lib.load().seer_cast_f32_dt(_p(x), x.numel(), _p(y), _req16(y, "y"), _stream()), "seer_cast_f32_dt")
+    check(_lib.load().seer_cast_f32(_p(x), x.numel(), _p(y), _req16(y, "y"), _stream()), "seer_cast_f32")
     return y
 
 

@@ -39,6 +39,17 @@ def test_binding_matches_header(lib_path):
     assert b"invalid" in lib.seer_strerror(-22)
 
 
+def test_one_entry_point_per_kernel(lib_path):
+    """no `_dt` / `_pre` twin is declared, and the library exports no seer_* symbol beyond the header's: the forwarders of
+    ABI <= 25 are gone, not merely undeclared"""
+    import subprocess
+    names = _declared()
+    assert not [n for n in names if n.endswith(("_dt", "_pre"))]
+    out = subprocess.run(["nm", "-D", "--defined-only", str(lib_path)], capture_output=True, text=True, check=True).stdout
+    exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("seer_")})
+    assert exported == names
+
+
 def test_desc_struct_layout_matches_header():
     """field order of the ctypes structs == field order of the C structs (parsed from the header)."""
     from seervideoldm_amd import _lib
@@ -92,6 +103,30 @@ def test_argument_validation_without_gpu(lib_path):
     cf = (_lib.ColfinalItem * 1)()
     cf[0].ws, cf[0].nblocks, cf[0].NV, cf[0].C = 16, 4, 3, 320                     # NV is 1 or 2
     assert lib.seer_colfinal_grouped(cf, 1, None) == -22
+    # every entry point with a storage type: a dtype that is neither SEER_DT_BF16 (0) nor SEER_DT_F16 (1) is -22 with otherwise
+    # plausible arguments: 16 = an aligned non-NULL pointer, and shapes every entry point accepts, so that the dtype is the only
+    # reason for the refusal (with a good dtype these calls would launch, which is why only the bad one is made here) ...
+    P, bad = 16, 2
+    assert lib.seer_groupnorm_stats(P, 320, None, 0, 1, 64, 32, P, P, bad, None) == -22
+    assert lib.seer_groupnorm_apply(P, 320, None, 0, 1, 64, 32, P, 640.0, 1e-5, P, P, 0, P, bad, None) == -22
+    assert lib.seer_groupnorm_apply_from_colsums(P, 320, None, 0, P, 1, 1, None, 0, 0, 1, 256, 32, 2560.0, 1e-5, P, P, 0, P, bad, None) == -22
+    assert lib.seer_groupnorm_apply_fx(P, 320, None, 0, P, 1, None, 0, 1, 256, 32, 2560.0, 1e-5, P, P, 0, P, None, bad, None) == -22
+    assert lib.seer_groupnorm_stats_fx(P, 320, 1, 256, P, bad, None) == -22
+    assert lib.seer_layernorm(P, 4, 320, 320, P, P, 1e-5, P, 320, bad, None) == -22
+    assert lib.seer_softmax_rows(P, 0, 4, 256, 256, 1.0, P, 256, bad, None) == -22
+    assert lib.seer_linear_smallm(P, 2, 320, P, P, 1280, 0, 1, P, bad, None) == -22
+    assert lib.seer_conv_in(P, 1, 4, 2, 8, 8, P, P, 320, P, bad, None) == -22
+    assert lib.seer_conv_out(P, 1, 320, 2, 8, 8, P, P, 4, P, bad, None) == -22
+    assert lib.seer_cast_f32(P, 1024, P, bad, None) == -22
+    ff = (P, 320, P, 320, P, 320, 96, P, P, 1e-5, P, P, P, P, None, 0, 0, None)
+    assert lib.seer_ff_fused_c320(P, 320, P, P, *ff, bad, None) == -22
+    assert lib.seer_ff_fused_c320(None, 0, None, None, *ff, bad, None) == -22          # without the prologue
+    # ... and it is refused ahead of the shape classes that are not built: -22, not -38; a good dtype gets the -38
+    assert lib.seer_layernorm(P, 4, 2048, 2048, P, P, 1e-5, P, 2048, bad, None) == -22
+    assert lib.seer_layernorm(P, 4, 2048, 2048, P, P, 1e-5, P, 2048, 1, None) == -38
+    assert lib.seer_softmax_rows(P, 0, 4, 8192, 8192, 1.0, P, 8192, bad, None) == -22
+    assert lib.seer_softmax_rows(P, 0, 4, 8192, 8192, 1.0, P, 8192, 0, None) == -38
+    assert lib.seer_conv_out(P, 1, 320, 2, 8, 8, P, P, 4, P, 1, None) == -38           # fp16 conv_out exists for Cout = 3 only
 
 
 def test_header_is_plain_c_and_the_c_caller_links(lib_path):
