@@ -1,7 +1,7 @@
 /*
  * seer_hip.h -- C ABI of libseer_hip.so: the MI355X (gfx950) device kernels behind the
  * Seer DDIM denoising hot path (SeerUNet forward + CFG + DDIM update + VAE decode), the two steps that feed it
- * (FSTextTransformer, VAE encode) and the fine-tuning step of train.py (backward kernels, AdamW).
+ * (FSTextTransformer, VAE encode), the CLIP text tower in front of those, and the fine-tuning step of train.py (backward kernels, AdamW).
  *
  * Boundary rules (all entry points):
  *   - extern "C", plain pointers and sizes; every pointer is DEVICE memory unless it says "host".
@@ -76,6 +76,10 @@ const char* seer_build_arch(void);          /* "gfx950" */
                                 * VAE, which the reference never autocasts (inference_img.py:118, ddim_sampling_utils.py:37-41):
                                 * 11 significand bits at the bf16 MFMA rate.  Plain and conv launches, unsplit; not with GEGLU,
                                 * rotary or colsum */
+#define SEER_EPI_QUICKGELU 128u /* C = v * sigmoid(1.702 v), v = acc + bias: CLIP's quick-GELU (transformers QuickGELUActivation; the
+                                * text tower's mlp.fc1).  Applied where SEER_EPI_SILU is, and refused by the same launch classes (the
+                                * weight-stationary kernel, the 256 x 320 tile, the folded LayerNorm: such a request runs on the tile
+                                * kernel).  Together with SEER_EPI_SILU: SEER_EINVAL */
 
 typedef struct seer_gemm_desc {
     const void* A;          /* bf16 */
@@ -265,6 +269,32 @@ typedef struct seer_attn_desc {
 #define SEER_ATTN_F16 2u
 
 int seer_attn_fwd(const seer_attn_desc* desc /* host */, void* stream);
+
+/* ---- CLIP text tower (transformers CLIPTextModel, text_encoder of runwayml/stable-diffusion-v1-5; train.py:330-334,
+ * inference_img.py:147-161) -- the two pieces next to seer_gemm_bf16 / seer_layernorm ------------------------------------------ */
+/* Causal self-attention with a key padding mask over short sequences, head_dim 64 (CLIPAttention with the causal mask and
+ * `attention_mask` of CLIPTextTransformer.forward):
+ *   O[b*L + i][64 h + :] = sum_j softmax_j( <Q[b*L + i][64 h + :], K[b*L + j][64 h + :]> ) V[b*L + j][64 h + :]
+ * over the keys j that are VISIBLE to query i of sample b:  j <= i  and  key_mask[b][j] != 0.
+ * Q, K, V: bf16 column slices of ONE fused [batch * L][>= 3 * heads * 64] projection -- the same row stride ld_qkv (elements, a
+ * multiple of 8), heads are adjacent 64-column groups, pointers 16-byte aligned.  O: bf16 token-major [batch * L][ldo], ldo a multiple
+ * of 4, 8-byte aligned.  key_mask: uint8 [batch][L], or NULL = every key visible.  1 <= L <= 128, any heads.
+ * Q ARRIVES PRESCALED by scale * log2(e) (scale = 64^-0.5) from the producing GEMM's SEER_EPI_COLSCALE, the convention of
+ * SEER_ATTN_Q_PRESCALED: the kernel takes exp2 of the raw dot products.  fp32 scores and statistics, P rounded to bf16 for the PV
+ * product, v_mfma_f32_16x16x32_bf16 for both products; one pass (a 16-query tile sees all its keys at once: no online rescaling).
+ * A query WITHOUT a visible key (a mask that hides key 0 .. i) writes ZEROS, never NaN or inf.  transformers leaves such a row to
+ * the softmax of a row of equal minima (a uniform average, or NaN, by version): outside its contract; here it is defined, so a host
+ * never has to synchronise to validate a mask.
+ * SEER_EINVAL: a NULL / misaligned pointer, a stride below heads * 64 or off its multiple, batch, heads or L < 1.  SEER_ENOSYS:
+ * L > 128 (not built).  Both are decided before any launch. */
+int seer_attn_causal64(const void* Q, const void* K, const void* V, int32_t ld_qkv, void* O, int32_t ldo, const uint8_t* key_mask,
+                       int32_t batch, int32_t heads, int32_t L, void* stream);
+/* CLIPTextEmbeddings: x[b*L + l][:] = tok[ids[b][l]][:] + pos[l][:], summed in fp32, stored as bf16 [batch * L][ldx].  ids int64
+ * [batch][L] on the DEVICE; tok bf16 [vocab][C], pos bf16 [L_max][C], C % 8 == 0, L <= L_max, ldx >= C and a multiple of 8, pointers
+ * 16-byte aligned.  An id outside [0, vocab - 1] is CLAMPED into it inside the kernel: no id can read out of bounds (hosts that want
+ * an error check their ids before the upload). */
+int seer_embed_tokens(const int64_t* ids, int32_t batch, int32_t L, const void* tok, int32_t vocab, const void* pos, int32_t L_max,
+                      int32_t C, void* x, int32_t ldx, void* stream);
 
 /* Backward of the call above (the training step, train.py:380-381 through attention.py:622-630 / 632-703):
  * given dO, writes dQ, dK, dV (bf16, addressed like Q/K/V with their own strides, so they can be the column slices of one

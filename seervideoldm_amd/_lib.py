@@ -24,11 +24,13 @@ SEER_EPI_TRANS_OUT = 8
 SEER_EPI_ROTARY = 16
 SEER_EPI_COLSCALE = 32
 SEER_EPI_F16 = 64
+SEER_EPI_QUICKGELU = 128
 SEER_ENOSYS = -38
 SEER_DT_BF16, SEER_DT_F16 = 0, 1
 SEER_ATTN_Q_PRESCALED = 1
 SEER_ATTN_F16 = 2
 SEER_TILE_AUTO, SEER_TILE_128x128, SEER_TILE_64x64, SEER_TILE_128x64 = 0, 1, 2, 3
+SEER_TILE_WS = 19
 
 
 class SeerHipError(RuntimeError):
@@ -122,6 +124,8 @@ SIGNATURES = {
     "seer_gemm_rowstat_ok": ([C.POINTER(GemmDesc)], C.c_int32),
     "seer_gemm_lnfold_ok": ([C.POINTER(GemmDesc)], C.c_int32),
     "seer_attn_fwd": ([C.POINTER(AttnDesc), _vp], C.c_int),
+    "seer_attn_causal64": ([_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp], C.c_int),
+    "seer_embed_tokens": ([_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp], C.c_int),
     "seer_rotary_table": ([_vp, _i32, _i32, _vp, _vp], C.c_int),
     "seer_rotary_inplace": ([_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "seer_groupnorm_workspace_floats": ([_i32, _i32, _i64, _i32], C.c_int64),

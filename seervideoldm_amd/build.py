@@ -18,13 +18,14 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libseer_hip.so"
-SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "train.hip"]
+SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "train.hip"]
 ARCH = "gfx950"
 # per-source extra flags.  attention: keep the MFMA accumulators in VGPRs (gfx950's unified file allows it) -- the online
 # softmax touches S and O every key tile, and the default AGPR form costs ~220 v_accvgpr moves per tile per wave.
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention40.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "attention_bwd.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               "clip_text.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gemm_tn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # GEMM: the epilogue reads every accumulator once; VGPR form saves those moves (+0.7 % on the step, A/B in one run)
                "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],

@@ -19,6 +19,9 @@ runs the script with the aliases installed (`sys.argv`, `sys.path[0]` and `__mai
 when `diffusers` is importable; without it the reference keeps its fp32 torch VAE for `vae.decode` / `vae.encode`.
 `SEER_COMPAT_SAMPLER=plms` (read by `install()`) makes the scripts sample with `PLMSSampler` under the name `DDIMSampler`: the
 yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluations).
+`SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
+`CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
+then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
 """
 from __future__ import annotations
 
@@ -72,13 +75,21 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
 _finder = _AliasFinder()
 _sampler = None
+_clip_saved = None          # (transformers module, its own CLIPTextModel) while the native text encoder stands in
 
 
-def install(vae: bool = False, sampler: Optional[str] = None) -> None:
+def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
-    `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler; anything else keeps DDIMSampler"""
-    global _sampler
+    `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler; anything else keeps DDIMSampler.
+    `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
+    CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
+    global _sampler, _clip_saved
     _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
+    if (os.environ.get("SEER_COMPAT_CLIP", "") if clip is None else clip).strip().lower() == "native" and _clip_saved is None:
+        import transformers
+        from seervideoldm_amd import CLIPTextEncoder
+        _clip_saved = (transformers, transformers.CLIPTextModel)
+        transformers.CLIPTextModel = CLIPTextEncoder
     if _finder not in sys.meta_path:
         sys.meta_path.insert(0, _finder)
     for name in list(ALIASES) + _PARENTS:      # modules imported before install() (the reference's own) give way
@@ -93,6 +104,10 @@ def install(vae: bool = False, sampler: Optional[str] = None) -> None:
 
 
 def uninstall() -> None:
+    global _clip_saved
+    if _clip_saved is not None:
+        _clip_saved[0].CLIPTextModel = _clip_saved[1]
+        _clip_saved = None
     if _finder in sys.meta_path:
         sys.meta_path.remove(_finder)
     for name in list(ALIASES) + _PARENTS:

@@ -784,6 +784,7 @@ __global__ void __launch_bounds__(64 * WM * WN) seer_gemm_kernel(const seer_gemm
     // ---- epilogue: lane holds rows n = 4*fq + r (r = 0..3) of the 16x16 D tile, column m = frow
     const bool out_f32 = (p.epilogue & SEER_EPI_OUT_F32) != 0;
     const bool do_silu = (p.epilogue & SEER_EPI_SILU) != 0;
+    const bool do_qgelu = (p.epilogue & SEER_EPI_QUICKGELU) != 0;
     const bool trans = (p.epilogue & SEER_EPI_TRANS_OUT) != 0;
     bf16* Cb = reinterpret_cast<bf16*>(p.C) + (int64_t)z * p.strideC;
     // output row of GEMM row m: the identity, except for the phase convs, whose row (img, y, x) is pixel (2 y + a, 2 x + b)
@@ -859,7 +860,7 @@ __global__ void __launch_bounds__(64 * WM * WN) seer_gemm_kernel(const seer_gemm
 #pragma unroll
         for (int i = 0; i < TM; ++i) { rsum[i] = 0.f; rsq[i] = 0.f; }
     }
-    const bool fast_epi = staged && m0 + BM <= p.M && n0 + BN <= p.N && !do_silu &&
+    const bool fast_epi = staged && m0 + BM <= p.M && n0 + BN <= p.N && !do_silu && !do_qgelu &&
                           (!GEGLU || !(do_rot || (p.epilogue & SEER_EPI_COLSCALE))) && (!p.rowvec || (RV_PRE && rv_pre_ok)) &&
                           (!R || RES_PRE);          // a residual that was not prefetched takes the general body
     if (fast_epi) {
@@ -1052,6 +1053,10 @@ __global__ void __launch_bounds__(64 * WM * WN) seer_gemm_kernel(const seer_gemm
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = silu_f(v[r]);
                 }
+                if (do_qgelu) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = quick_gelu_f(v[r]);
+                }
                 if (do_rot && n < p.rot_cols) {
                     // rotary on q|k columns (attention.py:649-651): channel inside its head = n % head_dim; the lane's 4
                     // consecutive columns are two interleaved pairs (x0,x1) -> (x0 c - x1 s, x1 c + x0 s)
@@ -1226,6 +1231,10 @@ __device__ __forceinline__ f32x4 splitk_reduce_quad(const seer_gemm_desc& p, int
     if (p.epilogue & SEER_EPI_SILU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = silu_f(v[r]);
+    }
+    if (p.epilogue & SEER_EPI_QUICKGELU) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = quick_gelu_f(v[r]);
     }
     if ((p.epilogue & SEER_EPI_COLSCALE) && n < p.col_scale_cols) {
 #pragma unroll
@@ -1478,6 +1487,7 @@ int prepare(seer_gemm_desc& d, int* splits) {
     if (!(d.epilogue & SEER_EPI_TRANS_OUT) && (d.ldc % 4)) return SEER_EINVAL;
     if (d.residual && (d.ldr % 4)) return SEER_EINVAL;
     if (d.rowvec && d.rows_per_batch <= 0) return SEER_EINVAL;
+    if ((d.epilogue & SEER_EPI_SILU) && (d.epilogue & SEER_EPI_QUICKGELU)) return SEER_EINVAL;      // one activation per launch
     if (d.epilogue & SEER_EPI_ROTARY) {
         if (!d.rot_table || d.rot_head_dim <= 0 || d.rot_head_dim % 4 || d.rot_dim <= 0 || d.rot_dim % 4 ||
             d.rot_dim > d.rot_head_dim || d.rot_tokens_per_batch <= 0 || d.rot_cols % d.rot_head_dim || geglu)
@@ -1782,7 +1792,7 @@ extern "C" int32_t seer_gemm_colsum_rows(const seer_gemm_desc* desc) {
 int ln_resolve(const seer_gemm_desc& in) {
     seer_gemm_desc d = in;
     const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0;
-    if (d.mode != SEER_GEMM_PLAIN || d.batch > 1 || (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_SILU)))
+    if (d.mode != SEER_GEMM_PLAIN || d.batch > 1 || (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_SILU | SEER_EPI_QUICKGELU)))
         return 0;
     if (d.ldc % 8 || d.N % (geglu ? 16 : 8) || (reinterpret_cast<uintptr_t>(d.C) & 15)) return 0;      // the kernel's `staged`
     if (d.rowstat && (geglu || d.colsum || d.colsum_fx)) return 0;

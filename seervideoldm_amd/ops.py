@@ -146,7 +146,7 @@ class FxArena:
 # ------------------------------------------------------------------------------------------------------------
 def gemm(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, rowvec=None, rows_per_batch=0,
          a2: Optional[torch.Tensor] = None, geglu=False, silu=False, out_f32=False, out: Optional[torch.Tensor] = None,
-         tile=0, splits=0, rotary=None, col_scale=None, colsum_batch=0, rowstat=False, ln=None) -> Optional[torch.Tensor]:
+         tile=0, splits=0, rotary=None, col_scale=None, colsum_batch=0, rowstat=False, ln=None, quick_gelu=False) -> Optional[torch.Tensor]:
     """out[M,N] = epi(a[M,K1] | a2[M,K-K1]) @ w[N,K]^T ; a/a2 may be row-strided views (last dim contiguous).
     rowstat = True or an FxArena: out.rowstats = RowStats of the output rows (None when this launch cannot accumulate them).
     ln = (RowStats of a, wsum, eps): a holds UN-normalised rows and w / bias are fold_layernorm()'s W' / b' -- the LayerNorm is
@@ -155,7 +155,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, rowvec=N
     left (or None when this launch cannot produce them; the caller then runs groupnorm_stats on the output).
     rotary = (cos_sin table, tokens_per_batch, pos_offset, head_dim, rot_dim, cols): rotate columns < cols in the epilogue.
     col_scale = (factor, cols): multiply output columns < cols by factor (the q columns of a projection carry the softmax
-    scale * log2(e) for attention(..., q_prescaled=True))."""
+    scale * log2(e) for attention(..., q_prescaled=True)).
+    quick_gelu: out = v * sigmoid(1.702 v), v = acc + bias (SEER_EPI_QUICKGELU: the CLIP text tower's fc1); not together with silu."""
     dt = _req16(a, "a"); _req16(w, "w", a)
     assert a.dim() == 2 and w.dim() == 2 and a.stride(1) == 1 and w.is_contiguous()
     M, K1 = a.shape
@@ -187,6 +188,7 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, bias=None, residual=None, rowvec=N
         d.rowvec, d.rowvec_ld, d.rows_per_batch = _p(rowvec), rowvec.stride(0), rows_per_batch
     d.mode = _lib.SEER_GEMM_PLAIN
     d.epilogue = (_lib.SEER_EPI_GEGLU if geglu else 0) | (_lib.SEER_EPI_SILU if silu else 0) | \
+                 (_lib.SEER_EPI_QUICKGELU if quick_gelu else 0) | \
                  (_lib.SEER_EPI_OUT_F32 if (out.dtype == torch.float32) else 0) | (_lib.SEER_EPI_F16 if dt else 0)
     assert out.dtype in (torch.float32, a.dtype)
     if rotary is not None:
@@ -443,6 +445,38 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     if _desc_only:
         return d
     check(_lib.load().seer_attn_fwd(C.byref(d), _stream()), "seer_attn_fwd")
+    return out
+
+
+def attn_causal64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, *, batch: int, heads: int, L: int,
+                  key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Causal self-attention with a key padding mask, head_dim 64, L <= 128 (seer_attn_causal64: the CLIP text tower).  q / k / v are
+    column slices [batch*L, heads*64] of ONE fused bf16 projection (same row stride), q prescaled by qk_prescale(64); out bf16
+    [batch*L, >= heads*64] token-major; key_mask uint8 [batch, L] (0 = hidden) or None.  A query without a visible key gets zeros."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (out, "out")):
+        _req(t, bf16, n)
+        assert t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == batch * L and t.shape[1] >= heads * 64
+    assert q.stride(0) == k.stride(0) == v.stride(0), "q, k, v are slices of one fused projection"
+    if key_mask is not None:
+        _req(key_mask, torch.uint8, "key_mask")
+        assert key_mask.shape == (batch, L) and key_mask.is_contiguous()
+    check(_lib.load().seer_attn_causal64(_p(q), _p(k), _p(v), q.stride(0), _p(out), out.stride(0), _p(key_mask), batch, heads, L,
+                                         _stream()), "seer_attn_causal64")
+    return out
+
+
+def embed_tokens(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[b*L + l] = tok[ids[b, l]] + pos[l] (fp32 sum, bf16 store): ids int64 [b, L] on the device, tok bf16 [vocab, C], pos bf16
+    [L_max, C].  The kernel clamps ids into the table; callers that want an error validate them on the host before the upload."""
+    _req(ids, torch.int64, "ids"); _req(tok, bf16, "tok"); _req(pos, bf16, "pos")
+    assert ids.dim() == 2 and ids.is_contiguous() and tok.is_contiguous() and pos.is_contiguous() and tok.shape[1] == pos.shape[1]
+    b, L = ids.shape
+    if out is None:
+        out = torch.empty((b * L, tok.shape[1]), device=ids.device, dtype=bf16)
+    _req(out, bf16, "out")
+    assert out.shape == (b * L, tok.shape[1]) and out.stride(1) == 1
+    check(_lib.load().seer_embed_tokens(_p(ids), b, L, _p(tok), tok.shape[0], _p(pos), pos.shape[0], tok.shape[1], _p(out),
+                                        out.stride(0), _stream()), "seer_embed_tokens")
     return out
 
 

@@ -126,6 +126,27 @@ def fstext_param_shapes(num_frames=16, num_layers=8, channels=768, n_heads=8, cr
     return sh
 
 
+def clip_text_param_shapes(vocab_size=49408, hidden_size=768, intermediate_size=3072, num_hidden_layers=12,
+                           max_position_embeddings=77):
+    """CLIPTextModel state dict (transformers models/clip/modeling_clip.py; `text_encoder/` of runwayml/stable-diffusion-v1-5 as
+    train.py:199 / inference_img.py:85 load it): 123.06 M parameters at the defaults.  The `position_ids` buffer of the
+    checkpoint is not listed: it is arange(max_position_embeddings)."""
+    sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    C, P = hidden_size, "text_model."
+    sh[P + "embeddings.token_embedding.weight"] = (vocab_size, C)
+    sh[P + "embeddings.position_embedding.weight"] = (max_position_embeddings, C)
+    for n in range(num_hidden_layers):
+        lp = f"{P}encoder.layers.{n}."
+        for nm in ("k_proj", "v_proj", "q_proj", "out_proj"):
+            sh[f"{lp}self_attn.{nm}.weight"] = (C, C); sh[f"{lp}self_attn.{nm}.bias"] = (C,)
+        sh[lp + "layer_norm1.weight"] = (C,); sh[lp + "layer_norm1.bias"] = (C,)
+        sh[lp + "mlp.fc1.weight"] = (intermediate_size, C); sh[lp + "mlp.fc1.bias"] = (intermediate_size,)
+        sh[lp + "mlp.fc2.weight"] = (C, intermediate_size); sh[lp + "mlp.fc2.bias"] = (C,)
+        sh[lp + "layer_norm2.weight"] = (C,); sh[lp + "layer_norm2.bias"] = (C,)
+    sh[P + "final_layer_norm.weight"] = (C,); sh[P + "final_layer_norm.bias"] = (C,)
+    return sh
+
+
 def vae_param_shapes(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, out_ch=3):
     """SD VAE decoder in the vendored-ldm key layout (ldm/modules/diffusionmodules/model.py:462-533) + post_quant_conv."""
     sh: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
