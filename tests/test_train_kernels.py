@@ -1,8 +1,8 @@
 """Per-kernel parity of the training entry points (include/seer_hip.h, "training step") on a real MI355X: every backward
 kernel against torch fp32 autograd of the operator it differentiates, on seeded bf16-rounded inputs.
 
-Gradients are compared by relative L2 error per tensor (bf16 storage of P / dS and of the outputs gives ~1e-2) plus a loose
-element-wise bound.
+Gradients are compared by relative L2 error per tensor (bf16 storage of P / dS and of the outputs gives ~1e-2).  The per-row and
+per-element bounds against float64, the exact-arithmetic cases and the edge shapes are in tests/test_gpu_train_matrix.py.
 """
 import pytest
 import torch
@@ -343,7 +343,9 @@ def test_adamw_matches_torch(device):
         torch.nn.utils.clip_grad_norm_([ref_p], 0.3)
         opt.step()
         ss = train_ops.sumsq(g)
-        assert abs(ss.item() - (g.double() ** 2).sum().item()) < 1e-4 * ss.item()
+        # the two-stage sum of 25 blocks: 16 elements per thread + the 8-level tree + 25 partials in order + the squares' own rounding, each
+        # 2^-24 of a sum of non-negative terms (tests/test_gpu_train_matrix.py::test_sumsq_exact_and_bounded)
+        assert abs(ss.item() - (g.double() ** 2).sum().item()) <= (16 + 8 + 25 + 2) * 2.0 ** -24 * ss.item()
         train_ops.adamw_step(p, g, m, v, lr=1e-3, step=step, grad_sumsq=ss, max_norm=0.3, p_bf16=pb)
         assert (p - ref_p.detach()).abs().max() < 2e-6
         assert torch.equal(pb, p.to(bf16))
