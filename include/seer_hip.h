@@ -659,6 +659,25 @@ int seer_sumsq_f32(const float* g, int64_t n, float* out, float* workspace, void
 int seer_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream);
 
+/* The glue of train.py:349-365 between the VAE encoder and the UNet, in ONE launch: posterior sample, latent scale, DDPM add_noise
+ * and the `(b f) c h w -> b c f h w` rearranges (train.py:353-354,365).
+ *   moments        fp32 [b, F, 2C, HW]  encoder output of all F = f1 + f2 frames of every video, images in (b f) order, (mean | logvar)
+ *   eps_post       fp32 [b, F, C, HW]   posterior noise, or NULL: the mean is taken
+ *   noise          fp32 [b, C, f2, HW]  the DDPM noise (= the epsilon target of the loss)
+ *   timesteps      int64 [b];  alphas_cumprod fp32 [T] (DDPMScheduler.alphas_cumprod)
+ *   model_input    fp32 [b, C, F, HW]   cat[latents_x0, noisy_latents] along frames (train.py:365)
+ *   latents        fp32 [b, C, f2, HW]  the clean scaled latents of the f2 frames, or NULL: not written
+ * Per element, in fp32:  z = mean + exp(0.5 * clamp(logvar, -30, 20)) * eps  (the bits of seer_gaussian_sample),  lat = z * latent_scale;
+ *   f <  f1:  model_input[b, c, f] = lat
+ *   f >= f1:  model_input[b, c, f] = sqrt(a) * lat + sqrt(1 - a) * noise[b, c, f - f1],   a = alphas_cumprod[timesteps[b]]
+ * A timestep outside [0, T) is clamped into the table by the kernel, never dereferenced (callers reject it beforehand).  16-byte
+ * accesses along HW when HW % 4 == 0 and all five bases are 16-byte aligned, a scalar path otherwise: any HW > 0 is accepted.
+ * SEER_EINVAL: a NULL required pointer, a non-positive extent, f2 < 1 (f1 = 0, no conditioning frame, is allowed), F or b*C above
+ * 65535 (the launch grid). */
+int seer_train_inputs(const float* moments, const float* eps_post, const float* noise, const int64_t* timesteps,
+                      const float* alphas_cumprod, int32_t T, int32_t b, int32_t C, int32_t f1, int32_t f2, int32_t HW,
+                      float latent_scale, float* model_input, float* latents, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -493,12 +493,7 @@ __global__ void gaussian_sample_kernel(const float* __restrict__ mom, int C, int
     const int64_t chw = (int64_t)C * HW;
     const int64_t img = i / chw, r = i - img * chw;
     const float mean = mom[img * 2 * chw + r];
-    float v = mean;
-    if (noise) {
-        const float logvar = fminf(fmaxf(mom[img * 2 * chw + chw + r], -30.0f), 20.0f);
-        v = fmaf(__expf(0.5f * logvar), noise[i], mean);
-    }
-    out[i] = v;
+    out[i] = noise ? gaussian_sample_f(mean, mom[img * 2 * chw + chw + r], noise[i]) : mean;
 }
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }

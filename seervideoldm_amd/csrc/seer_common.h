@@ -169,6 +169,11 @@ __device__ __forceinline__ float ln_term(float acc, float rstd, float wsum, floa
 __device__ __forceinline__ float silu_f(float x) { return x / (1.0f + __expf(-x)); }
 // CLIP's quick-GELU (transformers QuickGELUActivation): x * sigmoid(1.702 x)
 __device__ __forceinline__ float quick_gelu_f(float x) { return x / (1.0f + __expf(-1.702f * x)); }
+// DiagonalGaussianDistribution.sample of one element (distributions.py:24-37): mean + exp(0.5 * clamp(logvar, -30, 20)) * eps.
+// ONE definition for seer_gaussian_sample and seer_train_inputs: the two return the same bits on the same inputs.
+__device__ __forceinline__ float gaussian_sample_f(float mean, float logvar, float eps) {
+    return fmaf(__expf(0.5f * fminf(fmaxf(logvar, -30.0f), 20.0f)), eps, mean);
+}
 // exact-erf GELU (F.gelu default, attention.py:785-793) without libm and with ONE transcendental:
 //     gelu(x) = relu(x) - |x| * Phi(-|x|),      Phi(-a) = 0.5 * erfc(a / sqrt 2) = 2^(a * R(a) - 1)
 // R = degree-5 fit of (log2(erfc(a/sqrt2)/2) + 1) / a on [0, 4*sqrt2], weighted for the absolute error of gelu; beyond the

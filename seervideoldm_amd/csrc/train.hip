@@ -846,6 +846,68 @@ __global__ void __launch_bounds__(256) axpby_kernel(float* y, const float* x /* 
     }
 }
 
+// train.py:349-365 behind the VAE encoder in one pass: posterior sample (gaussian_sample_f: the bits of seer_gaussian_sample), latent
+// scale, DDPM add_noise on the frames to predict, and the (b f) c hw -> b c f hw transpose on the way to the UNet's input.
+// grid (HW / V / 256, F, b*C): a block owns a stretch of one (b, c, f) row, so the frame branch, the timestep and the schedule
+// entry are block-uniform and no thread divides; one thread per V consecutive positions, V = 4: 16-byte loads and stores
+// (HW % 4 == 0, every base 16-byte aligned).  HBM-bound: 4 words read (mean, logvar, eps, noise) and 2 written per predicted element,
+// nothing is read twice.
+template <int V>
+__global__ void __launch_bounds__(256) train_inputs_kernel(const float* __restrict__ mom, const float* __restrict__ eps,
+                                                           const float* __restrict__ noise, const int64_t* __restrict__ ts,
+                                                           const float* __restrict__ acp, int T, int C, int f1, int HWv,
+                                                           float scale, float* __restrict__ x, float* __restrict__ lat) {
+    const int pv = blockIdx.x * 256 + threadIdx.x;
+    if (pv >= HWv) return;
+    const int p = pv * V;
+    const int F = gridDim.y, f = blockIdx.y;
+    const int c = blockIdx.z % C;
+    const int64_t bi = blockIdx.z / C;
+    const int64_t HW = (int64_t)HWv * V;
+    const int f2 = F - f1;
+    const int64_t img = bi * F + f;                                  // image of the (b f) encoder batch
+    const float* mp = mom + (img * 2 * C + c) * HW + p;
+    float mean[V], logvar[V], e[V], z[V], o[V], nz[V];
+    auto ld = [](const float* src, float (&d)[V]) {
+        if constexpr (V == 4) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) d[k] = v[k];
+        } else {
+            d[0] = *src;
+        }
+    };
+    auto st = [](float* dst, const float (&d)[V]) {
+        if constexpr (V == 4) *reinterpret_cast<f32x4*>(dst) = f32x4{d[0], d[1], d[2], d[3]};
+        else *dst = d[0];
+    };
+    ld(mp, mean);
+    if (eps) {
+        ld(mp + (int64_t)C * HW, logvar);
+        ld(eps + (img * C + c) * HW + p, e);
+#pragma unroll
+        for (int k = 0; k < V; ++k) z[k] = gaussian_sample_f(mean[k], logvar[k], e[k]) * scale;
+    } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) z[k] = mean[k] * scale;
+    }
+    float* xp = x + ((bi * C + c) * F + f) * HW + p;
+    if (f < f1) {
+        st(xp, z);
+        return;
+    }
+    const int64_t j = ((bi * C + c) * f2 + (f - f1)) * HW + p;       // noise / latents: [b, C, f2, HW]
+    int64_t t = ts[bi];
+    t = t < 0 ? 0 : (t >= T ? T - 1 : t);                            // never read outside the table (the wrapper rejects such t)
+    const float a = acp[t];
+    const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+    ld(noise + j, nz);
+#pragma unroll
+    for (int k = 0; k < V; ++k) o[k] = fmaf(sa, z[k], sb * nz[k]);
+    st(xp, o);
+    if (lat) st(lat + j, z);
+}
+
 }  // namespace
 
 extern "C" int seer_transpose_bf16(const void* x, int64_t rows, int32_t cols, int32_t ldx, void* y, int64_t ldy,
@@ -1169,6 +1231,30 @@ extern "C" int seer_text_loss_grad(const void* y, const float* target, int32_t b
                        (float)(2.0 / (n * F)), reinterpret_cast<bf16*>(dy), workspace);
     SEER_LAUNCH_CHECK();
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(64), 0, st, workspace, blocks, (float)(1.0 / n), loss);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_train_inputs(const float* moments, const float* eps_post, const float* noise, const int64_t* timesteps,
+                                 const float* alphas_cumprod, int32_t T, int32_t b, int32_t C, int32_t f1, int32_t f2, int32_t HW,
+                                 float latent_scale, float* model_input, float* latents, void* stream) {
+    if (!moments || !noise || !timesteps || !alphas_cumprod || !model_input) return SEER_EINVAL;
+    if (T <= 0 || b <= 0 || C <= 0 || f1 < 0 || f2 < 1 || HW <= 0) return SEER_EINVAL;   // f1 = 0: no conditioning frames
+    const int F = f1 + f2;
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(moments) | reinterpret_cast<uintptr_t>(eps_post) |
+                            reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(model_input) |
+                            reinterpret_cast<uintptr_t>(latents);
+    const bool vec = HW % 4 == 0 && (bases & 15) == 0;               // every row starts a multiple of HW floats behind its base
+    const int HWv = vec ? HW / 4 : HW;
+    if (F > 65535 || (int64_t)b * C > 65535) return SEER_EINVAL;      // grid y / z
+    const dim3 grid((unsigned)((HWv + 255) / 256), (unsigned)F, (unsigned)(b * C));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(train_inputs_kernel<4>, grid, dim3(256), 0, st, moments, eps_post, noise, timesteps, alphas_cumprod, T,
+                           C, f1, HWv, latent_scale, model_input, latents);
+    else
+        hipLaunchKernelGGL(train_inputs_kernel<1>, grid, dim3(256), 0, st, moments, eps_post, noise, timesteps, alphas_cumprod, T,
+                           C, f1, HWv, latent_scale, model_input, latents);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

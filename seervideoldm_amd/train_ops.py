@@ -347,3 +347,43 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
     check(_lib.load().seer_adamw_step(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
                                       float(eps), float(weight_decay), int(step), _p(grad_sumsq), float(max_norm), _p(p_bf16),
                                       _stream()), "seer_adamw_step")
+
+
+def train_inputs(moments: torch.Tensor, eps_post: Optional[torch.Tensor], noise: torch.Tensor, timesteps: torch.Tensor,
+                 alphas_cumprod: torch.Tensor, cond_frames: int, latent_scale: float = 0.18215, *,
+                 out: Optional[torch.Tensor] = None, latents: Optional[torch.Tensor] = None,
+                 _timesteps_in_range: bool = False) -> torch.Tensor:
+    """train.py:349-365 behind the VAE encoder in one launch (seer_train_inputs): posterior sample, latent scale, DDPM add_noise
+    and the frame concat.  moments fp32 [b*F, 2C, h, w]: `vae.encode` of all F frames of every video, images in (b f) order;
+    eps_post fp32 [b*F, C, h, w] (None: the posterior mean); noise fp32 [b, C, F - cond_frames, h, w]; timesteps int64 [b];
+    alphas_cumprod fp32 [T].  Returns model_input fp32 [b, C, F, h, w] (`out`, when given); `latents` (optional, shaped like
+    noise) receives the clean scaled latents of the noised frames.  A timestep outside [0, T) raises ValueError before the
+    launch: that check reads the timesteps back (one synchronisation when they live on the device); `_timesteps_in_range` is
+    the trainer's own: it skips that check for timesteps it has just drawn with randint(0, T), and is not for other callers."""
+    _req(moments, torch.float32, "moments"); _req(noise, torch.float32, "noise"); _req(alphas_cumprod, torch.float32, "alphas_cumprod")
+    _req(timesteps, torch.int64, "timesteps")
+    assert moments.dim() == 4 and noise.dim() == 5 and moments.is_contiguous() and noise.is_contiguous()
+    assert alphas_cumprod.dim() == 1 and alphas_cumprod.is_contiguous() and timesteps.is_contiguous()
+    b, Cc, f2, H, W = noise.shape
+    f1 = int(cond_frames)
+    Fr = f1 + f2
+    T = alphas_cumprod.numel()
+    assert f1 >= 0 and f2 >= 1 and moments.shape == (b * Fr, 2 * Cc, H, W), "moments: [b*F, 2C, h, w] of all F frames"
+    assert timesteps.shape == (b,)
+    if eps_post is not None:
+        _req(eps_post, torch.float32, "eps_post")
+        assert eps_post.is_contiguous() and eps_post.shape == (b * Fr, Cc, H, W)
+    if not _timesteps_in_range:
+        lo, hi = int(timesteps.min()), int(timesteps.max())
+        if lo < 0 or hi >= T:
+            raise ValueError(f"train_inputs: timesteps must lie in [0, {T}) (the alphas_cumprod table), got [{lo}, {hi}]")
+    if out is None:
+        out = torch.empty((b, Cc, Fr, H, W), device=moments.device, dtype=torch.float32)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == (b, Cc, Fr, H, W)
+    if latents is not None:
+        _req(latents, torch.float32, "latents")
+        assert latents.is_contiguous() and latents.shape == noise.shape
+    check(_lib.load().seer_train_inputs(_p(moments), _p(eps_post), _p(noise), _p(timesteps), _p(alphas_cumprod), T, b, Cc, f1, f2,
+                                        H * W, float(latent_scale), _p(out), _p(latents), _stream()), "seer_train_inputs")
+    return out

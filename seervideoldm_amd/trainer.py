@@ -46,6 +46,24 @@ def cosine_lr(step: int, base_lr: float, warmup_steps: int, total_steps: int) ->
     return base_lr * max(0.0, 0.5 * (1.0 + math.cos(math.pi * 2.0 * 0.5 * progress)))
 
 
+def ddpm_alphas_cumprod(num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                        beta_schedule: str = "scaled_linear") -> torch.Tensor:
+    """The fp32 [T] table `DDPMScheduler(...).alphas_cumprod` that `add_noise` indexes (train.py:201,364; the defaults are
+    Stable Diffusion's scheduler_config.json): betas = linspace(sqrt(beta_start), sqrt(beta_end), T, float32) ** 2 for
+    "scaled_linear", linspace(beta_start, beta_end, T, float32) for "linear"; the cumulative product of 1 - beta in fp32.
+    A restatement of diffusers' arithmetic (schedulers/scheduling_ddpm.py), which is a third-party package that is not a
+    dependency here: it is checked against the closed form, not pinned against diffusers itself.  A run that already holds a
+    `DDPMScheduler` passes `noise_scheduler.alphas_cumprod` instead."""
+    T = int(num_train_timesteps)
+    if beta_schedule == "scaled_linear":
+        betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, T, dtype=f32) ** 2
+    elif beta_schedule == "linear":
+        betas = torch.linspace(beta_start, beta_end, T, dtype=f32)
+    else:
+        raise NotImplementedError(f"ddpm_alphas_cumprod: beta_schedule {beta_schedule!r} (scaled_linear or linear)")
+    return torch.cumprod(1.0 - betas, dim=0)
+
+
 class _Params:
     """flat fp32 master / gradient / Adam buffers with named views (packed layouts)."""
 
@@ -830,6 +848,68 @@ class SeerTrainer:
         noisy = a.sqrt() * latents + (1 - a).sqrt() * noise               # DDPMScheduler.add_noise (input preparation)
         x = torch.cat([latents_x0, noisy], 2)
         loss = self.forward_backward(x, noise, timesteps, text_cond_emb, latents_x0.shape[2], use_graph=use_graph,
+                                     on_unet_grads=self.start_unet_allreduce if self.pg is not None else None)
+        if self.accumulate():
+            self.optimizer_step(lr)
+        return loss
+
+    def step_from_batch(self, video: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *,
+                        vae, text_encoder, cond_frames: int, alphas_cumprod: torch.Tensor, lr: Optional[float] = None,
+                        use_graph: bool = False, noise: Optional[torch.Tensor] = None,
+                        timesteps: Optional[torch.Tensor] = None, posterior_noise: Optional[torch.Tensor] = None):
+        """The loop body of train.py:330-387 from a dataloader batch: video [b, 3, F, H, W] in [-1, 1], input_ids /
+        attention_mask as `CLIPTokenizer` returns them.  text_encoder: a `CLIPTextEncoder` (any callable whose result's [0] is
+        the last hidden state; it receives the ids and the mask on the trainer's device, as train.py:331-332 moves them); vae: this
+        package's `AutoencoderKL`; both frozen: they run under `torch.no_grad()`, no gradient flows into either.
+            text_cond_emb = text_encoder(input_ids, attention_mask=attention_mask)[0]          train.py:330-334
+            moments       = vae.encode(all b*F frames, (b f) order)                            train.py:349-350 (there: two calls)
+            model_input   = train_ops.train_inputs(...)   sample, * 0.18215, add_noise, concat  train.py:349-354,364-365
+            forward_backward, accumulate, optimizer_step(lr)                                   train.py:344-345,367-387
+        ONE encode where the reference makes two: every norm of the VAE and its attention are per image, so the split of the
+        frames over two calls is not semantic.  Epsilon prediction only (train.py:371-372).
+        Random numbers that are not passed in are drawn as train.py draws them, in its order:
+            1. posterior noise of the frames to predict,  torch.randn([b*f2, 4, h, w]) on the device    train.py:349
+            2. posterior noise of the conditioning frames, torch.randn([b*f1, 4, h, w]) on the device   train.py:350
+            3. the DDPM noise, torch.randn([b, 4, f2, h, w]) on the CPU, then moved                     train.py:357
+            4. the timesteps, torch.randint(0, T, (b,)) on the device                                   train.py:360-362
+        so a seeded run consumes the device generator and the CPU generator as the reference does.  Injected instead: noise
+        [b, 4, f2, h, w], timesteps [b] (outside [0, T): ValueError), posterior_noise [b*F, 4, h, w] in (b f) order over ALL
+        frames.  Returns the loss; `self.last_inputs` = (model_input, noise, timesteps, text_cond_emb) of this call."""
+        if video.dim() != 5:
+            raise ValueError(f"step_from_batch: video [b, 3, F, H, W], got {tuple(video.shape)}")
+        b, _, Fr, H, W = video.shape
+        f1 = int(cond_frames)
+        if Fr <= f1 or f1 < 0:
+            raise ValueError(f"step_from_batch: video has {Fr} frames, cond_frames={f1} leaves none to predict")
+        if self.fstext.num_frames != Fr:
+            raise ValueError(f"step_from_batch: the FSTextTransformer is set to {self.fstext.num_frames} frames, the video has "
+                             f"{Fr}: call fstext.set_numframe({Fr}) first (train.py:187)")
+        dev, f2 = self.device, Fr - f1
+        if attention_mask is not None:
+            attention_mask = attention_mask.to(dev)
+        frames = video.to(dev).permute(0, 2, 1, 3, 4).reshape(b * Fr, video.shape[1], H, W)       # 'b c f h w -> (b f) c h w'
+        with torch.no_grad():                                                                      # the frozen part
+            text_cond_emb = text_encoder(input_ids.to(dev), attention_mask=attention_mask)[0].to(dev, f32)
+            moments = vae.encode(frames).latent_dist.parameters                                    # fp32 [b*F, 2C, h, w]
+        Cz, h, w = moments.shape[1] // 2, moments.shape[2], moments.shape[3]
+        if posterior_noise is None:
+            eps_f2 = torch.randn((b, f2, Cz, h, w), device=dev, dtype=f32)                          # draw 1 (train.py:349)
+            eps_f1 = torch.randn((b, f1, Cz, h, w), device=dev, dtype=f32)                          # draw 2 (train.py:350)
+            posterior_noise = torch.cat([eps_f1, eps_f2], 1)                                       # frame order of the video
+        posterior_noise = posterior_noise.to(dev, f32).reshape(b * Fr, Cz, h, w).contiguous()
+        if noise is None:
+            noise = torch.randn((b, Cz, f2, h, w))                                                 # draw 3: CPU generator (train.py:357)
+        noise = noise.to(dev, f32).contiguous()
+        T = alphas_cumprod.numel()
+        drawn = timesteps is None
+        if drawn:
+            timesteps = torch.randint(0, T, (b,), device=dev)                                       # draw 4 (train.py:360-362)
+        timesteps = torch.as_tensor(timesteps).to(dev, torch.int64).reshape(b).contiguous()
+        acp = alphas_cumprod.to(dev, f32).contiguous()
+        model_input = self.tops.train_inputs(moments.contiguous(), posterior_noise, noise, timesteps, acp, f1,
+                                             _timesteps_in_range=drawn)
+        self.last_inputs = (model_input, noise, timesteps, text_cond_emb)
+        loss = self.forward_backward(model_input, noise, timesteps, text_cond_emb, f1, use_graph=use_graph,
                                      on_unet_grads=self.start_unet_allreduce if self.pg is not None else None)
         if self.accumulate():
             self.optimizer_step(lr)
