@@ -658,6 +658,21 @@ int seer_sumsq_f32(const float* g, int64_t n, float* out, float* workspace, void
  * receives the bf16 working copy of the updated parameters. */
 int seer_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                     float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream);
+/* The same step with 8-bit optimizer state (train.py:214-222 `use_8bit_adam`; block-wise dynamic quantisation after the 8-bit
+ * optimizers paper; this project's own format, NOT interchangeable with bitsandbytes' state files).  A block is 256 consecutive
+ * elements.  Per element two uint8 codes cm / cv, per block two fp32 scales absmax_m / absmax_v [n / 256]; qmap_m (signed) and
+ * qmap_v (unsigned) are the code books, 256 ascending fp32 entries each.  Fresh state: cm = 127, cv = 0 (the zero codes), scales 0.
+ * Per block, in fp32 and in the order of seer_adamw_step:
+ *   m = qmap_m[cm] * absmax_m,  v = qmap_v[cv] * absmax_v;   m = b1 m + (1 - b1) g',  v = b2 v + (1 - b2) g' g'  (g' = clipped g)
+ *   p = p (1 - lr wd) - (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)          with the new m, v BEFORE they are quantised
+ *   absmax_m' = max |m|, absmax_v' = max v over the block;  cm' / cv' = the code of the entry nearest to m / absmax_m', v / absmax_v'
+ *   (a tie goes either way; the zero code when the block maximum is 0).
+ * A non-finite moment stays out of the block maximum, so the scales remain finite; its own code is defined but meaningless.
+ * p_bf16 (optional) as above.  SEER_EINVAL, nothing launched: a NULL required pointer, n <= 0, n % 256 != 0, step < 1, p or g not
+ * 16-byte aligned, cm / cv / a float array not 4-byte aligned, p_bf16 not 8-byte aligned. */
+int seer_adamw8_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v, const float* qmap_m,
+                     const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                     int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream);
 
 /* The glue of train.py:349-365 between the VAE encoder and the UNet, in ONE launch: posterior sample, latent scale, DDPM add_noise
  * and the `(b f) c h w -> b c f h w` rearranges (train.py:353-354,365).

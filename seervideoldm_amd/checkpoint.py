@@ -83,8 +83,15 @@ def _names(tr: SeerTrainer):
     return un, fn
 
 
+def _fp32_state_only(tr: SeerTrainer) -> None:
+    if getattr(tr, "use_8bit_adam", False):
+        raise ValueError("the torch.optim.AdamW optimizer.bin of save_checkpoint / load_checkpoint holds fp32 moments; a trainer with "
+                         "use_8bit_adam=True keeps 8-bit state: use SeerTrainer.save_state / load_optimizer_state")
+
+
 def optimizer_state_dict(tr: SeerTrainer, lr: Optional[float] = None) -> Dict:
     """the trainer's Adam moments as `torch.optim.AdamW.state_dict()` in the reference's parameter order"""
+    _fp32_state_only(tr)
     un, fn = _names(tr)
     order = reference_param_order(un, fn)
     m = tr.trainable_state_dict_of(tr.pu.m, tr.pf.m)
@@ -108,6 +115,7 @@ def optimizer_state_dict(tr: SeerTrainer, lr: Optional[float] = None) -> Dict:
 
 def load_optimizer_state_dict(tr: SeerTrainer, sd: Dict) -> None:
     """inverse of optimizer_state_dict; also accepts a file written by the reference (no names: its own order is assumed)"""
+    _fp32_state_only(tr)
     un, fn = _names(tr)
     order = sd.get("param_names") or reference_param_order(un, fn)
     n_u = sd.get("n_unet", len(un))

@@ -786,6 +786,93 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
     }
 }
 
+// 8-bit AdamW (train.py:214-222 `use_8bit_adam`): both moments live as one uint8 code per element plus one fp32 scale per block
+// of 256 elements (block-wise dynamic quantisation; the code books are 256 sorted fp32 entries each, signed for m, unsigned for v).
+// One wave owns one block, four consecutive elements per lane: 16-byte accesses of p and g, 4-byte accesses of the codes.  The
+// arithmetic is adamw_kernel's, expression for expression, on the dequantised moments; p takes the UNquantised new moments.
+// Both block maxima are wave reductions by shuffles, so the loop has no barrier: the only one follows the code-book copy.
+//
+// adam8_encode: the code of the entry of the sorted book nearest to x, branch-free.  Eight halving steps find the last entry <= x
+// (entry 0 when there is none, or for a NaN: every comparison is false), then the nearer of it and its upper neighbour wins.
+// The first two steps read entries 128 and 64 / 192 for every element: they come from registers (q128, q64, q192).
+__device__ __forceinline__ unsigned adam8_encode(const float* __restrict__ q, float q128, float q64, float q192, float x) {
+    int lo = x >= q128 ? 128 : 0;
+    lo += x >= (lo ? q192 : q64) ? 64 : 0;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) lo += x >= q[lo + s] ? s : 0;
+    const int hi = lo < 255 ? lo + 1 : 255;
+    return x - q[lo] > q[hi] - x ? (unsigned)hi : (unsigned)lo;
+}
+
+__device__ __forceinline__ float adam8_wave_max(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+    return x;
+}
+
+__global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, const float* __restrict__ g, uint8_t* __restrict__ cm,
+                                                     uint8_t* __restrict__ cv, float* __restrict__ absmax_m,
+                                                     float* __restrict__ absmax_v, const float* __restrict__ qmap_m,
+                                                     const float* __restrict__ qmap_v, int64_t nblk, float lr, float b1, float b2,
+                                                     float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ sumsq,
+                                                     float max_norm, bf16* __restrict__ p_bf16) {
+    __shared__ float qm[256], qv[256];
+    qm[threadIdx.x] = qmap_m[threadIdx.x];
+    qv[threadIdx.x] = qmap_v[threadIdx.x];
+    __syncthreads();
+    const float m128 = qm[128], m64 = qm[64], m192 = qm[192], v128 = qv[128], v64 = qv[64], v192 = qv[192];
+    float coef = 1.0f;
+    if (sumsq) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
+    const int lane = threadIdx.x & 63;
+    const float inf = __builtin_huge_valf();
+    for (int64_t blk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); blk < nblk; blk += (int64_t)gridDim.x * 4) {
+        const int64_t q4 = blk * 64 + lane;                    // this lane's group of four elements
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[q4];
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[q4];
+        const unsigned cmw = reinterpret_cast<const unsigned*>(cm)[q4], cvw = reinterpret_cast<const unsigned*>(cv)[q4];
+        const float am = absmax_m[blk], av = absmax_v[blk];
+        float mi[4], vi[4];
+        float mx = 0.f, vx = 0.f;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float gi = gv[e] * coef;
+            float pi = pv[e] * (1.0f - lr * wd);
+            mi[e] = b1 * (qm[(cmw >> (8 * e)) & 255u] * am) + (1.0f - b1) * gi;
+            vi[e] = b2 * (qv[(cvw >> (8 * e)) & 255u] * av) + (1.0f - b2) * gi * gi;
+            const float denom = sqrtf(vi[e]) / bc2_sqrt + eps;
+            pi -= (lr / bc1) * (mi[e] / denom);
+            pv[e] = pi;
+            // a non-finite moment (non-finite gradient) stays out of the block maximum: the scales remain finite numbers
+            const float ma = fabsf(mi[e]);
+            mx = fmaxf(mx, ma < inf ? ma : 0.f);
+            vx = fmaxf(vx, vi[e] < inf ? vi[e] : 0.f);
+        }
+        mx = adam8_wave_max(mx);
+        vx = adam8_wave_max(vx);
+        unsigned cmo = 0, cvo = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const unsigned a = mx > 0.f ? adam8_encode(qm, m128, m64, m192, mi[e] / mx) : 127u;     // 127 / 0: the zero codes
+            const unsigned b = vx > 0.f ? adam8_encode(qv, v128, v64, v192, vi[e] / vx) : 0u;
+            cmo |= a << (8 * e);
+            cvo |= b << (8 * e);
+        }
+        reinterpret_cast<f32x4*>(p)[q4] = pv;
+        reinterpret_cast<unsigned*>(cm)[q4] = cmo;
+        reinterpret_cast<unsigned*>(cv)[q4] = cvo;
+        if (lane == 0) {
+            absmax_m[blk] = mx;
+            absmax_v[blk] = vx;
+        }
+        if (p_bf16) {
+            bf16x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = (bf16)pv[e];
+            reinterpret_cast<bf16x4*>(p_bf16)[q4] = o;
+        }
+    }
+}
+
 
 // text loss of the FSTextTransformer initialisation stage (train.py:346-347, `--text_loss`): loss_text = mean_{b,l,c}
 // (mean_f y[b,f,l,c] - t[b,l,c])^2; its gradient 2 (mean_f y - t) / (b l C F) is ADDED to dy for every frame.
@@ -1205,6 +1292,28 @@ extern "C" int seer_adamw_step(float* p, const float* g, float* m, float* v, int
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n,
                        lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_sumsq, max_norm,
                        reinterpret_cast<bf16*>(p_bf16));
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_adamw8_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v,
+                                const float* qmap_m, const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps,
+                                float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16,
+                                void* stream) {
+    if (!p || !g || !cm || !cv || !absmax_m || !absmax_v || !qmap_m || !qmap_v || n <= 0 || n % 256 || step < 1) return SEER_EINVAL;
+    const uintptr_t wide = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g);
+    const uintptr_t narrow = reinterpret_cast<uintptr_t>(cm) | reinterpret_cast<uintptr_t>(cv) | reinterpret_cast<uintptr_t>(absmax_m) |
+                             reinterpret_cast<uintptr_t>(absmax_v) | reinterpret_cast<uintptr_t>(qmap_m) |
+                             reinterpret_cast<uintptr_t>(qmap_v) | reinterpret_cast<uintptr_t>(grad_sumsq);
+    if ((wide & 15) || (narrow & 3) || (reinterpret_cast<uintptr_t>(p_bf16) & 7)) return SEER_EINVAL;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    const int64_t nblk = n / 256;
+    int64_t blocks = (nblk + 3) / 4;               // four waves, one 256-element block each per trip
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(adamw8_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, cm, cv,
+                       absmax_m, absmax_v, qmap_m, qmap_v, nblk, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
+                       grad_sumsq, max_norm, reinterpret_cast<bf16*>(p_bf16));
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

@@ -349,6 +349,64 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
                                       _stream()), "seer_adamw_step")
 
 
+ADAM8_BLOCK = 256           # elements per quantisation block of the 8-bit optimizer state
+ADAM8_ZERO_CODES = (127, 0)  # the codes of 0.0 in the signed / unsigned book: a fresh state
+_adam8_qmaps: dict = {}
+
+
+def adam8_codebooks() -> Tuple[torch.Tensor, torch.Tensor]:
+    """The two code books of the 8-bit optimizer state (fp32 [256] each, ascending, on the host): `qmap_m` signed, `qmap_v`
+    unsigned.  Dynamic quantisation after the 8-bit optimizers paper: for i = 0..6 the midpoints of linspace(0.1, 1, n_i), scaled by
+    10**(i-6), with n_i = 2**i + 1 and both signs (signed) or n_i = 2**(i+1) + 1 (unsigned); plus 0 and 1.  Built in float64,
+    sorted, rounded to fp32."""
+    import numpy as np
+
+    def book(signed: bool):
+        vals = [0.0, 1.0]
+        for i in range(7):
+            b = np.linspace(0.1, 1.0, 2 ** (i if signed else i + 1) + 1, dtype=np.float64)
+            mid = (b[:-1] + b[1:]) / 2 * 10.0 ** (i - 6)
+            vals += mid.tolist()
+            if signed:
+                vals += (-mid).tolist()
+        q = torch.tensor(sorted(vals), dtype=torch.float64).to(torch.float32)
+        assert q.numel() == 256 and bool((q[1:] > q[:-1]).all())
+        return q
+
+    qm, qv = book(True), book(False)
+    assert float(qm[ADAM8_ZERO_CODES[0]]) == 0.0 and float(qv[ADAM8_ZERO_CODES[1]]) == 0.0
+    return qm, qv
+
+
+def adam8_qmaps(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the code books on `device`: built once, uploaded once per device"""
+    key = str(torch.device(device))
+    if key not in _adam8_qmaps:
+        _adam8_qmaps[key] = tuple(q.to(device).contiguous() for q in adam8_codebooks())
+    return _adam8_qmaps[key]
+
+
+def adamw8_step(p: torch.Tensor, g: torch.Tensor, cm: torch.Tensor, cv: torch.Tensor, absmax_m: torch.Tensor,
+                absmax_v: torch.Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, step: int,
+                grad_sumsq: Optional[torch.Tensor] = None, max_norm: float = 1.0, p_bf16: Optional[torch.Tensor] = None) -> None:
+    """adamw_step with 8-bit state (seer_adamw8_step): cm, cv uint8 [n], absmax_m, absmax_v fp32 [n / 256], n % 256 == 0."""
+    n = p.numel()
+    for t, name in ((p, "p"), (g, "g"), (absmax_m, "absmax_m"), (absmax_v, "absmax_v")):
+        _req(t, torch.float32, name)
+    for t, name in ((cm, "cm"), (cv, "cv")):
+        _req(t, torch.uint8, name)
+    assert all(t.is_contiguous() for t in (p, g, cm, cv, absmax_m, absmax_v))
+    assert n % ADAM8_BLOCK == 0 and g.numel() == cm.numel() == cv.numel() == n, "flat buffers of a multiple of 256 elements"
+    assert absmax_m.numel() == absmax_v.numel() == n // ADAM8_BLOCK
+    if p_bf16 is not None:
+        _req(p_bf16, bf16, "p_bf16")
+        assert p_bf16.is_contiguous() and p_bf16.numel() == n
+    qm, qv = adam8_qmaps(p.device)
+    check(_lib.load().seer_adamw8_step(_p(p), _p(g), _p(cm), _p(cv), _p(absmax_m), _p(absmax_v), _p(qm), _p(qv), n, float(lr),
+                                       float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                       _p(grad_sumsq), float(max_norm), _p(p_bf16), _stream()), "seer_adamw8_step")
+
+
 def train_inputs(moments: torch.Tensor, eps_post: Optional[torch.Tensor], noise: torch.Tensor, timesteps: torch.Tensor,
                  alphas_cumprod: torch.Tensor, cond_frames: int, latent_scale: float = 0.18215, *,
                  out: Optional[torch.Tensor] = None, latents: Optional[torch.Tensor] = None,

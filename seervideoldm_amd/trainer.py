@@ -64,24 +64,45 @@ def ddpm_alphas_cumprod(num_train_timesteps: int = 1000, beta_start: float = 0.0
     return torch.cumprod(1.0 - betas, dim=0)
 
 
-class _Params:
-    """flat fp32 master / gradient / Adam buffers with named views (packed layouts)."""
+FP32_FORMAT = "adam-fp32"              # optimizer.bin of save_state: fp32 m, v (files of this kind carry no "format" entry)
+ADAM8_FORMAT = "adam8-block256"        # 8-bit codes + one fp32 scale per 256-element block (use_8bit_adam)
 
-    def __init__(self, tensors: "Dict[str, torch.Tensor]", device):
+
+class _Params:
+    """flat fp32 master / gradient / Adam buffers with named views (packed layouts).  Every tensor starts on a multiple of `align`
+    elements and n is one; the padding has a zero gradient and stays zero.  adam8: the moments are 8-bit codes cm / cv with one fp32
+    scale per 256-element block (absmax_m / absmax_v; seer_adamw8_step) instead of the fp32 buffers m / v, which are None then;
+    with align = 256 no block spans two tensors, so a tensor's optimizer state depends on its own values only."""
+
+    def __init__(self, tensors: "Dict[str, torch.Tensor]", device, align: int = 8, adam8: bool = False):
+        assert align % 8 == 0 and (not adam8 or align % 256 == 0)
         self.names = list(tensors)
         self.shapes = {k: tuple(v.shape) for k, v in tensors.items()}
         self.offsets, off = {}, 0
         for k, v in tensors.items():
             self.offsets[k] = off
-            off += (v.numel() + 7) // 8 * 8            # keep every view 16/32-byte aligned
+            off += (v.numel() + align - 1) // align * align            # keep every view 16/32-byte aligned
         self.n = off
         self.p = torch.zeros((off,), device=device, dtype=f32)
         for k, v in tensors.items():
             self.view(self.p, k).copy_(v.to(device, f32))
         self.g = torch.zeros_like(self.p)
-        self.m = torch.zeros_like(self.p)
-        self.v = torch.zeros_like(self.p)
+        self.adam8 = bool(adam8)
+        self.m = self.v = self.cm = self.cv = self.absmax_m = self.absmax_v = None
+        if adam8:
+            self.cm = torch.full((off,), 127, device=device, dtype=torch.uint8)      # the codes of 0.0 in the two books
+            self.cv = torch.zeros((off,), device=device, dtype=torch.uint8)
+            self.absmax_m = torch.zeros((off // 256,), device=device, dtype=f32)
+            self.absmax_v = torch.zeros((off // 256,), device=device, dtype=f32)
+        else:
+            self.m = torch.zeros_like(self.p)
+            self.v = torch.zeros_like(self.p)
         self.pb = self.p.to(bf16)
+
+    def state(self) -> "Dict[str, torch.Tensor]":
+        """the optimizer state tensors by name"""
+        names = ("cm", "cv", "absmax_m", "absmax_v") if self.adam8 else ("m", "v")
+        return {k: getattr(self, k) for k in names}
 
     def view(self, flat: torch.Tensor, k: str) -> torch.Tensor:
         o = self.offsets[k]
@@ -142,8 +163,11 @@ def _pack_fstext_fp32(sd: Dict[str, torch.Tensor], num_layers: int) -> "Dict[str
 class SeerTrainer:
     def __init__(self, unet: SeerUNet, fstext: FSTextTransformer, *, lr: float = 1e-4, betas=(0.9, 0.999),
                  weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, gradient_accumulation_steps: int = 1,
-                 text_loss: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None):
+                 text_loss: bool = False, use_8bit_adam: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None):
         self.ops, self.tops = ops, tops
+        # train.py:214-222 / configs/train.yaml:27: AdamW with block-wise quantised 8-bit moments (seer_adamw8_step; this project's
+        # own state format, not bitsandbytes').  The clip, the data-parallel averaging and the accumulation do not change.
+        self.use_8bit_adam = bool(use_8bit_adam)
         self.accum = int(gradient_accumulation_steps)           # configs/train.yaml:13, train.py:321 (accelerator.accumulate)
         self._micro = 0
         self.text_loss = bool(text_loss)                       # train.py:346-347,377-378 (configs/train.yaml text_loss)
@@ -155,8 +179,9 @@ class SeerTrainer:
         self.step_count = 0
         sd_u = {k: v for k, v in unet.state_dict().items()}
         sd_f = {k: v for k, v in fstext.state_dict().items()}
-        self.pu = _Params(_pack_temporal_fp32(sd_u), self.device)
-        self.pf = _Params(_pack_fstext_fp32(sd_f, fstext.num_layers), self.device)
+        pk = dict(align=256, adam8=True) if self.use_8bit_adam else {}
+        self.pu = _Params(_pack_temporal_fp32(sd_u), self.device, **pk)
+        self.pf = _Params(_pack_fstext_fp32(sd_f, fstext.num_layers), self.device, **pk)
         for P in (self.pu, self.pf):                            # mean of the micro-batch gradients when accumulating
             P.acc = torch.zeros_like(P.g) if self.accum > 1 else None
         # working weights: bf16 views for matrices, fp32 master views for biases / norm affine; the frozen rest comes from
@@ -831,13 +856,35 @@ class SeerTrainer:
             hu.wait()
             self.tops.axpby(gu, gu, 1.0 / ws, 0.0)
         ss = self.tops.sumsq(gu)                                           # clip_grad_norm_(sunet.parameters()) only
-        self.tops.adamw_step(self.pu.p, gu, self.pu.m, self.pu.v, grad_sumsq=ss, max_norm=self.max_grad_norm,
-                             p_bf16=self.pu.pb, **kw)
+        self._adamw(self.pu, gu, grad_sumsq=ss, max_norm=self.max_grad_norm, **kw)
         if hf is not None:
             hf.wait()
             self.tops.axpby(gf, gf, 1.0 / ws, 0.0)
-        self.tops.adamw_step(self.pf.p, gf, self.pf.m, self.pf.v, p_bf16=self.pf.pb, **kw)
+        self._adamw(self.pf, gf, **kw)
         self.grad_norm_sq = ss
+
+    def _adamw(self, P: _Params, g: torch.Tensor, **kw) -> None:
+        if P.adam8:
+            self.tops.adamw8_step(P.p, g, P.cm, P.cv, P.absmax_m, P.absmax_v, p_bf16=P.pb, **kw)
+        else:
+            self.tops.adamw_step(P.p, g, P.m, P.v, p_bf16=P.pb, **kw)
+
+    def optimizer_state_bytes(self) -> int:
+        """bytes of optimizer state held for both segments (fp32: 8 per element; 8-bit: 2 per element + 8 per 256-element block)"""
+        return sum(t.numel() * t.element_size() for P in (self.pu, self.pf) for t in P.state().values())
+
+    def optimizer_moments(self) -> "Dict[str, Tuple[torch.Tensor, torch.Tensor]]":
+        """{'unet': (m, v), 'fstext': (m, v)}: the Adam moments as flat fp32 tensors in the packed layout (copies; in 8-bit mode
+        dequantised: code-book entry times the block's scale).  For inspection and tests: `trainable_state_dict_of` unpacks them."""
+        out = {}
+        for key, P in (("unet", self.pu), ("fstext", self.pf)):
+            if P.adam8:
+                qm, qv = self.tops.adam8_qmaps(self.device)
+                rep = lambda a: a.repeat_interleave(256)
+                out[key] = (qm[P.cm.long()] * rep(P.absmax_m), qv[P.cv.long()] * rep(P.absmax_v))
+            else:
+                out[key] = (P.m.clone(), P.v.clone())
+        return out
 
     def train_step(self, latents_x0, latents, noise, timesteps, text_cond_emb, alphas_cumprod, lr: Optional[float] = None,
                    use_graph: bool = False):
@@ -956,18 +1003,24 @@ class SeerTrainer:
         cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}
         torch.save(cpu(self.unet.state_dict()), os.path.join(save_path, "pytorch_model.bin"))
         torch.save(cpu(self.fstext.state_dict()), os.path.join(save_path, "pytorch_model_1.bin"))
-        torch.save({"step_count": self.step_count, "micro": self._micro, "epoch": epoch, "global_step": global_step,
-                    "unet": {"m": self.pu.m.cpu(), "v": self.pu.v.cpu()}, "fstext": {"m": self.pf.m.cpu(), "v": self.pf.v.cpu()}},
-                   os.path.join(save_path, "optimizer.bin"))
+        st = {"step_count": self.step_count, "micro": self._micro, "epoch": epoch, "global_step": global_step,
+              "unet": {k: t.cpu() for k, t in self.pu.state().items()}, "fstext": {k: t.cpu() for k, t in self.pf.state().items()}}
+        if self.use_8bit_adam:          # (a file without "format" is the fp32 one: m and v)
+            st["format"] = ADAM8_FORMAT
+        torch.save(st, os.path.join(save_path, "optimizer.bin"))
         return save_path
 
     def load_optimizer_state(self, save_path: str) -> None:
         import os
         st = torch.load(os.path.join(save_path, "optimizer.bin"), map_location="cpu")
+        fmt, mine = st.get("format", FP32_FORMAT), ADAM8_FORMAT if self.use_8bit_adam else FP32_FORMAT
+        if fmt != mine:
+            raise ValueError(f"optimizer.bin holds {fmt!r} state, this trainer keeps {mine!r} (use_8bit_adam={self.use_8bit_adam}); "
+                             f"the formats are {FP32_FORMAT!r} (fp32 m, v) and {ADAM8_FORMAT!r} (8-bit codes + block scales)")
         self.step_count, self._micro = int(st["step_count"]), int(st["micro"])
         for P, key in ((self.pu, "unet"), (self.pf, "fstext")):
-            P.m.copy_(st[key]["m"])
-            P.v.copy_(st[key]["v"])
+            for k, t in P.state().items():
+                t.copy_(st[key][k])
 
     def trainable_state_dict(self) -> "Dict[str, Dict[str, torch.Tensor]]":
         """{'unet': {...}, 'fstext': {...}} fp32 tensors under the REFERENCE's parameter names (unpacked)."""
