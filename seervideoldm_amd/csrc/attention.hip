@@ -88,7 +88,10 @@ struct TokMap {
 // F16 (SEER_ATTN_F16): Q, K, V and O hold IEEE half instead of bf16 -- the same 16-bit loads, LDS images and transposed reads (the
 // bf16 vector types below are containers of bits); only the MFMA opcode, the constant 1.0 of the denominator column, the conversion
 // of P and the output pack differ.  P <= 2^defer_thr = 16 is far inside the half range; probabilities below 6e-8 flush to zero.
-template <int D, bool DBUF, bool F16 = false>
+// LSE (training launches at D = 40 / 80, where the denominator of O comes out of the P V MFMA): the lse statistic gets a denominator of
+// its own, the fp32 sum of the UNROUNDED P.  The MFMA's is the sum of the 16-bit P -- right for O, whose numerator holds the same P, but
+// 2^-9 relative off as a statistic (tests/test_gpu_attn_fwd_matrix.py: lse 127x outside its fp32 allowance, against 0.02x at D = 96).
+template <int D, bool DBUF, bool F16 = false, bool LSE = false>
 __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, const int ws_log2, const float defer_thr) {
     using C = AttnCfg<D>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -299,7 +302,7 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
 #endif
                 }
             }
-            if constexpr (!LSUM_MFMA) {
+            if constexpr (!LSUM_MFMA || LSE) {
                 float psum = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) psum += sacc[r];
@@ -370,7 +373,9 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
     else l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
     // training: log2-domain log-sum-exp of the scaled scores, read back by seer_attn_bwd
-    if (p.lse && lh == 0 && qi < p.Sq) p.lse[(int64_t)y * p.Sq + qi] = m_run + __builtin_amdgcn_logf(l_tot);
+    float l_stat = l_tot;
+    if constexpr (LSUM_MFMA && LSE) l_stat = l_run + __shfl_xor(l_run, 32, 64);
+    if (p.lse && lh == 0 && qi < p.Sq) p.lse[(int64_t)y * p.Sq + qi] = m_run + __builtin_amdgcn_logf(l_stat);
     if (qi < p.Sq) {
         bf16* orow = Og + (int64_t)tok(qi) * p.o_ss;
 #pragma unroll
@@ -394,14 +399,14 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
     }
 }
 
-template <int D, bool DBUF, bool F16 = false>
+template <int D, bool DBUF, bool F16 = false, bool LSE = false>
 int launch_attn2(const seer_attn_desc& d, int ws_log2, float thr, hipStream_t st) {
     int nbatch = d.batch;
     if (ws_log2 >= 0) nbatch *= (d.H >> ws_log2) * (d.W >> ws_log2);
     dim3 grid((d.Sq + 127) / 128, nbatch * d.heads, 1);
     constexpr size_t lds = AttnCfg<D>::LDS_BYTES / (DBUF ? 1 : 2);
     static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit: would need a hipFuncSetAttribute opt-in");
-    hipLaunchKernelGGL((seer_attn_kernel<D, DBUF, F16>), grid, dim3(256), lds, st, d, ws_log2, thr);
+    hipLaunchKernelGGL((seer_attn_kernel<D, DBUF, F16, LSE>), grid, dim3(256), lds, st, d, ws_log2, thr);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }
@@ -412,6 +417,12 @@ template <int D>
 int launch_attn(const seer_attn_desc& d, int ws_log2, hipStream_t st) {
     constexpr float thr = 4.0f;
     if (d.flags & SEER_ATTN_F16) return launch_attn2<D, false, true>(d, ws_log2, thr, st);      // IEEE-half operands: the generic kernel
+    if constexpr (AttnCfg<D>::DV > D) {              // the denominator rides in the P V product: lse sums the unrounded P itself
+        if (d.lse) {
+            if (d.variant == 6) return launch_attn2<D, true, false, true>(d, ws_log2, thr, st);
+            return launch_attn2<D, false, false, true>(d, ws_log2, thr, st);
+        }
+    }
     if constexpr (AttnCfg<D>::LDS_BYTES <= 64 * 1024) {
         if (d.variant == 6) return launch_attn2<D, true>(d, ws_log2, thr, st);
     }

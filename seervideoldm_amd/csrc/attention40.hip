@@ -210,11 +210,14 @@ extern "C" long long* seer_lab_a40_stamps() {
 // per-tile wait + barrier + issue burst was a third of a tile period (profiles/r02_attn40_stamps.log).
 // F16 (SEER_ATTN_F16): IEEE-half operands.  Only the TRACKED form exists there: the fast path fixes its reference after 32 keys and lives
 // off bf16's 8 exponent bits (P up to 2^127); with the reference tracked P <= 2^14 fits the half range.
-template <int QB, bool TRACK_ONLY, bool PLAIN, int NST = 2, bool F16 = false>
+// LSE (lse requested: always the tracked form): the statistic's denominator is the fp32 sum of the UNROUNDED P, kept per lane next to
+// the MFMA's sum of the rounded P that O divides by (see seer_attn_kernel, attention.hip).
+template <int QB, bool TRACK_ONLY, bool PLAIN, int NST = 2, bool F16 = false, bool LSE = false>
 __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn40_kernel(const seer_attn_desc p, const int ws_log2_arg, const int nqb) {
     const int ws_log2 = PLAIN ? -1 : ws_log2_arg;
     const bool causal = PLAIN ? false : (p.causal != 0);
     static_assert(!F16 || TRACK_ONLY, "IEEE-half operands: the tracked form only");
+    static_assert(!LSE || (TRACK_ONLY && !F16), "lse: the tracked bf16 form");
     constexpr int D = A40_D;
     constexpr int QW = 32 * QB;                      // queries per wave
     // NST K|V stages + the constant region
@@ -378,6 +381,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x16 oacc[QB][2];
     float m_run[QB];
+    [[maybe_unused]] float l_stat[QB];               // LSE: this lane's share (16 keys of every 32-key block) of sum_j P_j in fp32
 
     auto load_kfrags = [&](unsigned kst, bf16x8 (&kf)[3]) {          // kst: LDS address of the sub tile's first K row
         const unsigned kp = kst + k_off;
@@ -417,6 +421,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
         for (int qb = 0; qb < QB; ++qb) {
             oacc[qb][0] = zero16;
             oacc[qb][1] = zero16;
+            if constexpr (LSE) l_stat[qb] = 0.f;
             set_ref(qb, 0.f);
         }
 
@@ -566,6 +571,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
                                 oacc[qb][0][r] *= alpha;
                                 oacc[qb][1][r] *= alpha;
                             }
+                            if constexpr (LSE) l_stat[qb] *= alpha;
                             set_ref(qb, m_new);
                         }
                     }
@@ -574,6 +580,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
 #pragma unroll
                     for (int i = 0; i < 8; ++i) {
                         const float e0 = __builtin_amdgcn_exp2f(s[2 * i]), e1 = __builtin_amdgcn_exp2f(s[2 * i + 1]);
+                        if constexpr (LSE) l_stat[qb] += e0 + e1;
                         if constexpr (TRACK)
                             pk[i >> 2][i & 3] = pack2t<F16>(e0, e1);
                         else        // truncation: {e1[31:16], e0[31:16]}
@@ -640,7 +647,9 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
         const float inv = l > 0.f ? 1.0f / l : 0.f;
         const int qi = q0w + 32 * qb + lq;
         // training: log2-domain log-sum-exp of the scaled scores, read back by seer_attn_bwd
-        if (p.lse && lh == 0 && qi < p.Sq) p.lse[(int64_t)y * p.Sq + qi] = m_run[qb] + __builtin_amdgcn_logf(l);
+        float ls = l;
+        if constexpr (LSE) ls = l_stat[qb] + __shfl_xor(l_stat[qb], 32, 64);
+        if (p.lse && lh == 0 && qi < p.Sq) p.lse[(int64_t)y * p.Sq + qi] = m_run[qb] + __builtin_amdgcn_logf(ls);
         unsigned char* orow = ost + (32 * qb + lq) * A40_ROWB + 8 * lh;      // lane holds d = 32 dt + 8 g + 4 h + (0..3)
 #pragma unroll
         for (int g = 0; g < 5; ++g) {                // g = 4: d tile 1, rows 32..39
@@ -719,7 +728,9 @@ int seer_attn40_launch(const seer_attn_desc& d, int ws_log2, hipStream_t st) {
     }
     const int nqb = (d.Sq + 127) / 128;
     dim3 grid((unsigned)(nqb * nbatch * d.heads));
-    if (track && plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
+    if (track && d.lse && plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true, 2, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
+    else if (track && d.lse) hipLaunchKernelGGL((seer_attn40_kernel<1, true, false, 2, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
+    else if (track && plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
     else if (track) hipLaunchKernelGGL((seer_attn40_kernel<1, true, false>), grid, dim3(256), 0, st, d, ws_log2, nqb);
     else if (plain) hipLaunchKernelGGL((seer_attn40_kernel<1, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
     else hipLaunchKernelGGL((seer_attn40_kernel<1, false, false>), grid, dim3(256), 0, st, d, ws_log2, nqb);
