@@ -727,10 +727,12 @@ ROWCHAIN_C, ROWCHAIN_ROWS = 320, 96
 
 
 def rowchain_pack(w: torch.Tensor) -> torch.Tensor:
-    """w [n * 320, 320] (16-bit) -> the n matrices in the fragment order of rowchain() (seer_rowchain_pack).  Once per model."""
+    """w [n * 320, 320] (16-bit; rows may be strided by a multiple of 8 elements) -> the n matrices in the fragment order of rowchain()
+    (seer_rowchain_pack), contiguous.  Once per model."""
     _req16(w, "w")
-    assert w.dim() == 2 and w.shape[1] == ROWCHAIN_C and w.shape[0] % ROWCHAIN_C == 0 and w.is_contiguous()
-    out = torch.empty_like(w)
+    assert w.dim() == 2 and w.shape[1] == ROWCHAIN_C and w.shape[0] % ROWCHAIN_C == 0
+    assert w.stride(1) == 1 and w.stride(0) >= ROWCHAIN_C and w.stride(0) % 8 == 0
+    out = torch.empty(w.shape, device=w.device, dtype=w.dtype)
     check(_lib.load().seer_rowchain_pack(_p(w), w.stride(0), w.shape[0] // ROWCHAIN_C, _p(out), _stream()), "seer_rowchain_pack")
     return out
 
