@@ -211,6 +211,24 @@ int32_t seer_gemm_rowstat_ok(const seer_gemm_desc* desc /* host */);
 int32_t seer_gemm_lnfold_ok(const seer_gemm_desc* desc /* host */);
 /* bytes of zeroed counter memory (desc->sync) the call would use to reduce its K slices inside the launch (0: none) */
 int64_t seer_gemm_sync_bytes(const seer_gemm_desc* desc /* host */);
+/* The launch plan of this exact descriptor (read-only; nothing is launched): out = status (what seer_gemm_bf16 would return
+ * before it launches), kernel (SEER_GEMM_KERNEL_*), tile (SEER_TILE_*: the tile instantiation; SEER_TILE_T256x320 on that
+ * kernel; under SEER_GEMM_KERNEL_WS the tile that runs should that launch hand back), K slices, reduce pass (SEER_GEMM_REDUCE_*).
+ * A negative status -- bad arguments, or a feature (column sums, row statistics, GEGLU) the selected launch cannot carry -- comes
+ * with kernel NONE and zeros.  This is the HOST's decision.  Two things happen
+ * after it and depend on the device's CU count: the 256 x 320 launch clamps its K slices to the resident workgroups, and the
+ * weight-stationary launch may hand back to the tile kernel.  Returns SEER_EINVAL for a NULL argument, else SEER_OK. */
+#define SEER_GEMM_KERNEL_NONE 0
+#define SEER_GEMM_KERNEL_TILE 1      /* seer_gemm_kernel, one launch */
+#define SEER_GEMM_KERNEL_SPLITK 2    /* its split-K form + a reduce pass (desc.workspace) */
+#define SEER_GEMM_KERNEL_WS 3        /* weight-stationary (gemm_ws.hip) */
+#define SEER_GEMM_KERNEL_T320 4      /* 256 x 320 tile (gemm_t320.hip); K slices reduced inside the launch */
+#define SEER_GEMM_REDUCE_NONE 0
+#define SEER_GEMM_REDUCE_PLAIN 1
+#define SEER_GEMM_REDUCE_COLSUM 2         /* + per-tile column sums (desc.colsum) */
+#define SEER_GEMM_REDUCE_COLSUM_FX64 3    /* + accumulated column sums (desc.colsum_fx) on 64-row blocks */
+#define SEER_GEMM_REDUCE_COLSUM_FX32 4    /* ... on 32-row blocks */
+int seer_gemm_plan(const seer_gemm_desc* desc /* host */, int32_t out[5]);
 
 /* ---- attention -------------------------------------------------------------------------- */
 /* Replaces xformers.ops.memory_efficient_attention as called from CrossAttention

@@ -31,6 +31,8 @@ SEER_ATTN_Q_PRESCALED = 1
 SEER_ATTN_F16 = 2
 SEER_TILE_AUTO, SEER_TILE_128x128, SEER_TILE_64x64, SEER_TILE_128x64 = 0, 1, 2, 3
 SEER_TILE_WS = 19
+SEER_GEMM_KERNEL_NONE, SEER_GEMM_KERNEL_TILE, SEER_GEMM_KERNEL_SPLITK, SEER_GEMM_KERNEL_WS, SEER_GEMM_KERNEL_T320 = 0, 1, 2, 3, 4
+SEER_GEMM_REDUCE_NONE, SEER_GEMM_REDUCE_PLAIN, SEER_GEMM_REDUCE_COLSUM, SEER_GEMM_REDUCE_COLSUM_FX64, SEER_GEMM_REDUCE_COLSUM_FX32 = 0, 1, 2, 3, 4
 
 
 class SeerHipError(RuntimeError):
@@ -123,6 +125,7 @@ SIGNATURES = {
     "seer_gemm_sync_bytes": ([C.POINTER(GemmDesc)], C.c_int64),
     "seer_gemm_rowstat_ok": ([C.POINTER(GemmDesc)], C.c_int32),
     "seer_gemm_lnfold_ok": ([C.POINTER(GemmDesc)], C.c_int32),
+    "seer_gemm_plan": ([C.POINTER(GemmDesc), C.POINTER(C.c_int32)], C.c_int),
     "seer_attn_fwd": ([C.POINTER(AttnDesc), _vp], C.c_int),
     "seer_attn_causal64": ([_vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i32, _vp], C.c_int),
     "seer_embed_tokens": ([_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32, _vp], C.c_int),

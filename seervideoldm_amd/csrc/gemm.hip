@@ -1392,16 +1392,13 @@ int launch_tile(const seer_gemm_desc& d, hipStream_t st) {
     }
     const bool conv = d.mode == SEER_GEMM_CONV3X3;
     const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0;
-    if (conv && geglu) return SEER_EINVAL;
-    if ((d.colsum || d.colsum_fx) && (geglu || !tile_colsum_ok<BM, BN, NS, WM, WN>() || !colsum_store_ok(d))) return SEER_EINVAL;
-    if ((d.rowstat || d.ln_rowstat) && !tile_ln_ok<BM, BN, NS, WM, WN>()) return SEER_EINVAL;
     if (conv) {
         hipLaunchKernelGGL((seer_gemm_kernel<BM, BN, true, false, false, NS, WM, WN, F16>), grid, dim3(64 * WM * WN), lds, st, d);
     } else if (geglu) {
         if constexpr (GEGLU_OK)
             hipLaunchKernelGGL((seer_gemm_kernel<BM, BN, false, true, false, NS, WM, WN, F16>), grid, dim3(64 * WM * WN), lds, st, d);
         else
-            return SEER_EINVAL;
+            return SEER_EINVAL;          // (plan_gemm refuses GEGLU on these tiles)
     } else {
         hipLaunchKernelGGL((seer_gemm_kernel<BM, BN, false, false, false, NS, WM, WN, F16>), grid, dim3(64 * WM * WN), lds, st, d);
     }
@@ -1410,7 +1407,7 @@ int launch_tile(const seer_gemm_desc& d, hipStream_t st) {
 }
 
 template <int BM, int BN, int NS, bool F16 = false>
-int launch_split_tile(const seer_gemm_desc& d, hipStream_t st) {
+int launch_split_tile(const seer_gemm_desc& d, int reduce, hipStream_t st) {
     const int tiles_m = (d.M + BM - 1) / BM, tiles_n = (d.N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, d.splits);
     const size_t lds = (size_t)(NS == 0 ? 2 : NS) * (BM + BN) * BK * sizeof(bf16);
@@ -1419,16 +1416,13 @@ int launch_split_tile(const seer_gemm_desc& d, hipStream_t st) {
     else
         hipLaunchKernelGGL((seer_gemm_kernel<BM, BN, false, false, true, NS, 2, 2, F16>), grid, dim3(256), lds, st, d);
     SEER_LAUNCH_CHECK();
-    if (d.colsum_fx) {
-        if (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_GEGLU)) return SEER_EINVAL;
-        if (splitk_fx_rows(d.M) == 64)
-            hipLaunchKernelGGL((seer_splitk_reduce_fx_kernel<64, 16, 4>), dim3((unsigned)((d.N + 63) / 64), (unsigned)((d.M + 63) / 64)),
-                               dim3(256), 0, st, d);
-        else
-            hipLaunchKernelGGL((seer_splitk_reduce_fx_kernel<32, 32, 1>), dim3((unsigned)((d.N + 31) / 32), (unsigned)((d.M + 31) / 32)),
-                               dim3(256), 0, st, d);
-    } else if (d.colsum) {
-        if (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_GEGLU)) return SEER_EINVAL;
+    if (reduce == SEER_GEMM_REDUCE_COLSUM_FX64) {
+        hipLaunchKernelGGL((seer_splitk_reduce_fx_kernel<64, 16, 4>), dim3((unsigned)((d.N + 63) / 64), (unsigned)((d.M + 63) / 64)),
+                           dim3(256), 0, st, d);
+    } else if (reduce == SEER_GEMM_REDUCE_COLSUM_FX32) {
+        hipLaunchKernelGGL((seer_splitk_reduce_fx_kernel<32, 32, 1>), dim3((unsigned)((d.N + 31) / 32), (unsigned)((d.M + 31) / 32)),
+                           dim3(256), 0, st, d);
+    } else if (reduce == SEER_GEMM_REDUCE_COLSUM) {
         const int cs_rows = splitk_cs_rows(d.M);
         hipLaunchKernelGGL(seer_splitk_reduce_colsum_kernel, dim3((unsigned)((d.N + 255) / 256),
                            (unsigned)((d.M + cs_rows - 1) / cs_rows)), dim3(256), 0, st, d);
@@ -1441,20 +1435,18 @@ int launch_split_tile(const seer_gemm_desc& d, hipStream_t st) {
 }
 
 template <bool F16>
-int launch_split_t(const seer_gemm_desc& d, hipStream_t st) {
-    if (d.tile == SEER_TILE_64x64) return launch_split_tile<64, 64, 0, F16>(d, st);        // register-staged (A/B testing)
-    if (d.tile == SEER_TILE_G64x64_3) return launch_split_tile<64, 64, 3, F16>(d, st);
-    if (d.tile == SEER_TILE_G128x128_2) return launch_split_tile<128, 128, 2, F16>(d, st);
-    if (d.tile == SEER_TILE_G96x160_2) return launch_split_tile<96, 160, 2, F16>(d, st);
-    // auto: prepare() already wrote its tile choice into d.tile; anything else keeps the 64x64 ring
-    return launch_split_tile<64, 64, 3, F16>(d, st);
-}
-int launch_split(const seer_gemm_desc& d, hipStream_t st) {
-    return (d.epilogue & SEER_EPI_F16) ? launch_split_t<true>(d, st) : launch_split_t<false>(d, st);
+int launch_split_t(int tile, const seer_gemm_desc& d, int reduce, hipStream_t st) {
+    switch (tile) {                      // the four tiles choose_split() hands out
+        case SEER_TILE_64x64: return launch_split_tile<64, 64, 0, F16>(d, reduce, st);        // register-staged (A/B testing)
+        case SEER_TILE_G64x64_3: return launch_split_tile<64, 64, 3, F16>(d, reduce, st);
+        case SEER_TILE_G128x128_2: return launch_split_tile<128, 128, 2, F16>(d, reduce, st);
+        case SEER_TILE_G96x160_2: return launch_split_tile<96, 160, 2, F16>(d, reduce, st);
+        default: return SEER_EINVAL;
+    }
 }
 
-// validate + normalise a descriptor; returns SEER_OK and the number of K slices the call will use in *splits
-int prepare(seer_gemm_desc& d, int* splits) {
+// the argument checks of every launch; normalises K1 / lda2 / batch and the strides of the phase convs in place.  No decisions.
+int validate(seer_gemm_desc& d) {
     if (d.M <= 0 || d.N <= 0 || d.K <= 0) return SEER_EINVAL;
     if (d.K % BK) return SEER_EINVAL;
     if (!d.A || !d.W || !d.C) return SEER_EINVAL;
@@ -1497,9 +1489,15 @@ int prepare(seer_gemm_desc& d, int* splits) {
         if (geglu || d.col_scale_cols <= 0 || d.col_scale_cols % 4 || d.col_scale_cols > d.N) return SEER_EINVAL;
     }
     if (d.batch <= 1) d.batch = 1;
+    return SEER_OK;
+}
 
-    // split-K decision: few output tiles and a long K loop (deep-level convs / linears, M = 384 .. 1536)
-    int s = 1;
+// split-K decision for a validated descriptor whose d.tile names a tile kernel or AUTO: few output tiles and a long K loop
+// (deep-level convs / linears, M = 384 .. 1536).  Returns the K slices (1: no split) and the tile that runs them.
+struct split_choice { int splits, tile; };
+split_choice choose_split(const seer_gemm_desc& d) {
+    const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0;
+    int s = 1, tile = d.tile;
     const bool can_split = d.batch == 1 && !geglu && !(d.epilogue & (SEER_EPI_TRANS_OUT | SEER_EPI_ROTARY)) &&
                            (d.tile == SEER_TILE_AUTO || d.tile == SEER_TILE_64x64 || d.tile == SEER_TILE_G64x64_3 ||
                             d.tile == SEER_TILE_G128x128_2 || d.tile == SEER_TILE_G96x160_2) &&
@@ -1516,17 +1514,14 @@ int prepare(seer_gemm_desc& d, int* splits) {
             // the 4x4 level (x16) and, with fewer frames or one CFG half per rank, the same levels sliced deeper.
             const long t128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
             const long blocks64 = (long)((d.M + 63) / 64) * ((d.N + 63) / 64);
-            // (round 2 kept a plain GEMM whose 64x64 grid already holds ~2 blocks per CU and whose K is only moderately long -- the
-            // 8x8-level feed-forward output projection, 1536 x 1280 x 5120 -- on the 5-stage 64x64 ring unsplit, 40.8 against 47.4 us
-            // for 128x128 x 4 slices + the reduce pass; since the staging path lost its address arithmetic the slices win, 35.2
-            // against 40.0: profiles/r04_ff2_tile_sweep.log)
-            const bool unsplit_ring = false;
+            // (the 8x8-level feed-forward output projection, 1536 x 1280 x 5120: 35.2 us on 128x128 x 4 slices + the reduce pass against
+            // 40.0 unsplit on the 5-stage 64x64 ring: profiles/r04_ff2_tile_sweep.log)
             int s128 = 1;
             // (cold weights, r06_lab_cold_weights.log / r06_lab_cold_train.log: a PLAIN product is sliced to ONE round of the chip, not two
             //  -- 1536 x 1280 x 6400: 2 slices 41.3 against 43.3 us for 4; 768 x 1280 x 10240: 4 slices 37.0 against 45.3 for 8; 924 x 768 x
             //  6144: 4 slices 23.8 against 30.7 -- while the convs, whose slices are ten times longer, keep two)
             const long split_target = d.mode == SEER_GEMM_PLAIN ? 180 : 400, split_accept = d.mode == SEER_GEMM_PLAIN ? 180 : 200;
-            if (d.N % 128 == 0 && d.N >= 640 && d.M >= 256 && t128 < 256 && nk >= 64 && !unsplit_ring)
+            if (d.N % 128 == 0 && d.N >= 640 && d.M >= 256 && t128 < 256 && nk >= 64)
                 while (t128 * s128 < split_target && s128 < 16 && nk / (2 * s128) >= 11) s128 *= 2;
             // N = 320 on half the rows (one CFG half per rank: 12 288 rows = 256 tiles of 96x160, one lone workgroup per CU, which
             // runs a K tile no faster than two co-resident ones do): two K slices bring the second workgroup back.  3x3 convs only
@@ -1542,28 +1537,26 @@ int prepare(seer_gemm_desc& d, int* splits) {
             if (d.tile == SEER_TILE_AUTO && d.mode == SEER_GEMM_CONV3X3 && d.M <= 384 && d.N % 160 == 0 && nk >= 160 && t96160 <= 32) {
                 s = (int)(256 / t96160);
                 while (s > 1 && nk / s < 11) s >>= 1;
-                d.tile = SEER_TILE_G96x160_2;
+                tile = SEER_TILE_G96x160_2;
             } else
             if (s128 > 1 && t128 * s128 >= split_accept && d.tile == SEER_TILE_AUTO) {
                 s = s128;
-                d.tile = SEER_TILE_G128x128_2;
+                tile = SEER_TILE_G128x128_2;
             // (with COLD weights the 320 -> 320 conv, K = 2880, is faster unsplit -- 34.8 against 40.6 us -- and the longer ones keep their
             //  two slices: 60.9 against 63.7, 81.3 against 91.7; profiles/r06_lab_cold_train_convs.log)
             } else if (d.N == 320 && d.mode == SEER_GEMM_CONV3X3 && t96160 >= 128 && t96160 <= 256 && nk >= 80 &&
                        d.tile == SEER_TILE_AUTO) {
                 s = 2;
-                d.tile = SEER_TILE_G96x160_2;
+                tile = SEER_TILE_G96x160_2;
             } else {
-                const long blocks = blocks64;
-                if (blocks <= 160 && nk >= 160) s = blocks <= 40 ? 16 : 8;      // 4x4 / 8x8 level convs of a frame shard
-                else if (blocks <= 160 && nk >= 40) s = nk / 20 < 8 ? nk / 20 : 8;
-                else if (blocks <= 512 && nk >= 80 && !unsplit_ring) s = 4;
-                if (s > 1 && d.tile == SEER_TILE_AUTO) d.tile = SEER_TILE_G64x64_3;
+                if (blocks64 <= 160 && nk >= 160) s = blocks64 <= 40 ? 16 : 8;      // 4x4 / 8x8 level convs of a frame shard
+                else if (blocks64 <= 160 && nk >= 40) s = nk / 20 < 8 ? nk / 20 : 8;
+                else if (blocks64 <= 512 && nk >= 80) s = 4;
             }
         }
     }
-    *splits = s;
-    return SEER_OK;
+    if (tile == SEER_TILE_AUTO) tile = SEER_TILE_G64x64_3;      // no tile rule above: the 64x64 ring runs the slices
+    return {s, tile};
 }
 
 // the tile an unsplit, non-weight-stationary launch of `d` runs (d.tile, or the AUTO choice)
@@ -1579,10 +1572,10 @@ int resolve_tile(const seer_gemm_desc& d) {
         const int n128 = (d.N + 127) / 128 * 128;
         const bool n_fits_128 = (n128 - d.N) * 8 <= d.N;           // <= 12.5 % padded columns
         const long t128160 = (long)((d.M + 127) / 128) * ((d.N + 159) / 160) * d.batch;
-        const long t96160_ = (long)((d.M + 95) / 96) * ((d.N + 159) / 160) * d.batch;
+        const long t96160 = (long)((d.M + 95) / 96) * ((d.N + 159) / 160) * d.batch;
         // (12 288 rows x 320 -- one CFG half, or the b = 1 fine-tuning step -- are 256 tiles of 96x160: one round; 16.2 / 28.6 / 12.9 us
         //  against 19.6 / 33.9 / 15.1 on 128x64 with cold weights, r06_lab_cold_train.log)
-        if ((d.N == 320 || d.N == 960) && nk >= 5 && (t128160 >= 256 || (d.N == 320 && t96160_ >= 224 && t96160_ <= 256)) &&
+        if ((d.N == 320 || d.N == 960) && nk >= 5 && (t128160 >= 256 || (d.N == 320 && t96160 >= 224 && t96160 <= 256)) &&
             !(d.epilogue & SEER_EPI_GEGLU)) {
             // (with the fast epilogue the 160-wide tiles also win at K = 320 .. 960, where the register-staged 64x64 tile used to:
             //  projections of the 320-wide level 17.5 -> 15.6 / 14.4 -> 12.0 us, its 1x1 shortcuts 20.0 -> 16.2 / 26.5 -> 20.6, and
@@ -1590,7 +1583,6 @@ int resolve_tile(const seer_gemm_desc& d) {
             // N = 320 in two 160-wide tiles: no padded columns, 0.45x the L2->LDS traffic of 64x64.  Rows per tile: whichever
             // of 128 / 96 leaves the last round of tiles fuller -- 24 576 rows (the 32x32 level at CFG batch 2) are 384 tiles
             // of 128 rows (1.5 per CU) but 512 of 96 rows (2 per CU): +13 % on the 320->320 conv (profiles/r01_tile96.log)
-            const long t96160 = (long)((d.M + 95) / 96) * ((d.N + 159) / 160) * d.batch;
             auto fill = [](long t) { return (double)t / (256.0 * (double)((t + 255) / 256)); };
             tile = fill(t96160) > fill(t128160) + 0.05 ? SEER_TILE_G96x160_2 : SEER_TILE_G128x160_2;
             // the rotary epilogue (temporal q|k|v) reads a (cos, sin) row per output row: fewer, taller tiles re-read less of the
@@ -1632,7 +1624,7 @@ int resolve_tile(const seer_gemm_desc& d) {
             tile = SEER_TILE_G96x128_2;         // 768 x 3840 x 1280 (b = 1 step, 8x8 level): 240 tiles, 14.9 against 20.6 us cold on 128x64
         else if (d.mode == SEER_GEMM_PLAIN && t12864 >= 200 && t12864 < 256 && nk >= 10) tile = SEER_TILE_G128x64_3;   // (3072 x 640 x 640: 7.7 against 10.5)
         else if (t12864 >= 256 && nk >= 5) tile = SEER_TILE_G128x64_3;   // (K = 320 too: 8.9 vs 9.7 us on 12 288 x 320, r02_half_rows.log)
-        else if (nk >= 64) tile = SEER_TILE_G64x64_5;        // long K on few tiles: deeper ring (see prepare(), unsplit_ring)
+        else if (nk >= 64) tile = SEER_TILE_G64x64_5;        // long K on few tiles: deeper ring
         else if (nk >= 12) tile = SEER_TILE_G64x64_3;
         else tile = SEER_TILE_64x64;
     }
@@ -1658,26 +1650,19 @@ double t320_model_us(const seer_gemm_desc& d, int S) {
     const double fixed = (d.epilogue & SEER_EPI_GEGLU) ? 12.0 : 7.0;      // prologue + epilogue of a tile (the erf epilogue: +5 us)
     return rounds * (((nk + S - 1) / S) * t_iter + fixed) + slab + 3.0;
 }
-int t320_best_split(const seer_gemm_desc& d, bool can_split, double* t_best) {
+int t320_best_split(const seer_gemm_desc& d) {
     static const int cand[] = {1, 2, 3, 4, 5, 6, 8, 10, 12, 16};
     const int nk = d.K / BK;
     int best = 1;
     double tb = t320_model_us(d, 1);
-    if (can_split)
-        for (int S : cand) {
-            if (S > nk / 4) break;                   // a slice keeps at least four K tiles
-            const double t = t320_model_us(d, S);
-            if (t < tb) { tb = t; best = S; }
-        }
-    if (t_best) *t_best = tb;
+    for (int S : cand) {
+        if (S > nk / 4) break;                   // a slice keeps at least four K tiles
+        const double t = t320_model_us(d, S);
+        if (t < tb) { tb = t; best = S; }
+    }
     return best;
 }
-bool t320_buffers_ok(const seer_gemm_desc& d, int s) {
-    return d.workspace && d.workspace_bytes >= seer_gemm_t320_workspace_bytes(d, s) && d.sync &&
-           d.sync_bytes >= seer_gemm_t320_sync_bytes(d, s);
-}
-// assume_buffers: a size query -- plan as if workspace and sync will be provided; the launch plans with what it was given
-int t320_plan(const seer_gemm_desc& d, bool assume_buffers = false) {
+int t320_plan(const seer_gemm_desc& d, bool assume_buffers) {
     if (d.rowstat || d.ln_rowstat) return 0;          // row statistics / folded LayerNorm live in the tile kernel
     if (d.tile != SEER_TILE_T256x320 && d.tile != SEER_TILE_AUTO) return 0;
     if (d.mode != SEER_GEMM_PLAIN && d.mode != SEER_GEMM_CONV3X3) return 0;
@@ -1686,31 +1671,26 @@ int t320_plan(const seer_gemm_desc& d, bool assume_buffers = false) {
     const bool phases = d.mode == SEER_GEMM_CONV3X3 && d.upsample == 2;
     const bool can_split = !geglu && d.batch <= 1 && !phases && d.splits != 1;
     if (d.tile == SEER_TILE_T256x320) {
-        int s = 1;
-        if (can_split) {
-            const int nk = d.K / BK;
-            s = d.splits > 1 ? d.splits : t320_best_split(d, true, nullptr);
-            if (s > nk / 4) s = nk / 4;
-            if (s > 16) s = 16;
-            if (s < 1) s = 1;
-            if (!assume_buffers && s > 1 && !t320_buffers_ok(d, s)) s = 1;      // asked for by name: run it unsplit
-        }
-        return s;
+        if (!can_split) return 1;
+        const int nk = d.K / BK;
+        int s = d.splits > 1 ? d.splits : t320_best_split(d);
+        if (s > nk / 4) s = nk / 4;
+        if (s > 16) s = 16;
+        if (s < 1) s = 1;
+        const bool room = d.workspace && d.workspace_bytes >= seer_gemm_t320_workspace_bytes(d, s) && d.sync &&
+                          d.sync_bytes >= seer_gemm_t320_sync_bytes(d, s);
+        return (!assume_buffers && s > 1 && !room) ? 1 : s;      // asked for by name without room to split: run it unsplit
     }
     // AUTO
     if (d.M % 256 || d.splits > 1) return 0;          // (ragged row tiles and explicit split requests stay with the smaller tiles)
-    double t = 0.0;
     // AUTO never splits K on this kernel: the in-launch reduction waits for peer workgroups, which is only safe when this process
     // has the GPU to itself (gemm_t320.hip); ask for SEER_TILE_T256x320 + splits by name where that holds
-    (void)can_split;
-    const int s = t320_best_split(d, false, &t);
+    const double t = t320_model_us(d, 1);
     const double flops = 2.0 * d.M * d.N * (double)d.K * (phases ? 4 : d.batch > 1 ? d.batch : 1);
     // FLOP per us.  (Convs: since the small tiles' gather lost its address arithmetic they reach 1.0-1.2 PFLOP/s on long-K convs
     // with many rows -- profiles/r04_t320_recalibration.log -- and the big tile is rarely ahead there.)
     const double rate = d.mode == SEER_GEMM_CONV3X3 ? 1.10e9 : geglu ? 0.78e9 : 0.85e9;
-    if (!(t < flops / rate)) return 0;
-    if (!assume_buffers && s > 1 && !t320_buffers_ok(d, s)) return 0;         // no room to split: the smaller tiles take it
-    return s;
+    return t < flops / rate ? 1 : 0;
 }
 
 template <int BM_, int BN_, int NS_, int WM_ = 2, int WN_ = 2>
@@ -1741,81 +1721,142 @@ int dispatch_tile(int tile, F&& f) {
     }
 }
 
+// what the plan has to know about a tile instantiation (bm == 0: not a tile code)
+struct tile_traits { int bm, bn; bool colsum_ok, ln_ok; };
+tile_traits traits_of(int tile) {
+    tile_traits t{};
+    dispatch_tile(tile, [&t](auto tag) {
+        using T = decltype(tag);
+        t = {T::BM, T::BN, tile_colsum_ok<T::BM, T::BN, T::NS, T::WM, T::WN>(), tile_ln_ok<T::BM, T::BN, T::NS, T::WM, T::WN>()};
+        return SEER_OK;
+    });
+    return t;
+}
+
+// ---- folded LayerNorm (seer_gemm_desc::rowstat / ln_rowstat): such launches stay on the tile kernel, unsplit, with a staged
+// bf16 output.  Can `tile` carry the row statistics `d` asks for?
+bool ln_resolve(const seer_gemm_desc& d, const tile_traits& tile) {
+    const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0;
+    if (d.mode != SEER_GEMM_PLAIN || d.batch > 1 || (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_SILU | SEER_EPI_QUICKGELU)))
+        return false;
+    if (d.ldc % 8 || d.N % (geglu ? 16 : 8) || (reinterpret_cast<uintptr_t>(d.C) & 15)) return false;      // the kernel's `staged`
+    if (d.rowstat && (geglu || d.colsum || d.colsum_fx)) return false;
+    if (d.ln_rowstat && (d.A2 || !d.ln_wsum || (reinterpret_cast<uintptr_t>(d.ln_wsum) & 15))) return false;
+    return tile.ln_ok;
+}
+
+// ---- the launch plan: which kernel a descriptor gets, decided ONCE.  seer_gemm_bf16 launches it, the host queries read it.
+struct gemm_plan {
+    int status;                          // SEER_OK: seer_gemm_bf16 launches this plan; else the code it returns
+    int kernel, tile, splits, reduce;    // SEER_GEMM_KERNEL_* (NONE: validate() refused, nothing else is set), the tile (under WS: the one
+                                         // that runs if that launch hands back), K slices, SEER_GEMM_REDUCE_*; set whatever status says
+    seer_gemm_desc d;                    // validated + normalised; d.tile: a tile kernel's code or AUTO; d.splits: still the request
+    int colsum_rows, colsum_fx_rows;     // rows per partial of desc.colsum / desc.colsum_fx this launch leaves (0: it cannot)
+    bool ln_ok;                          // rowstat / ln_rowstat: asked for and carried
+};
+
+// assume_buffers: a size query -- plan as if workspace and sync will be provided; the launch plans with what it was given
+gemm_plan plan_gemm(const seer_gemm_desc& in, bool assume_buffers) {
+    gemm_plan p{};
+    p.d = in;
+    seer_gemm_desc& d = p.d;
+    p.status = validate(d);
+    if (p.status != SEER_OK) return p;
+    const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0, sums = d.colsum || d.colsum_fx, sums_stored = colsum_store_ok(d);
+    const bool rows_ln = d.rowstat || d.ln_rowstat;       // row statistics / folded LayerNorm: tile kernel, unsplit
+    const int s320 = t320_plan(d, assume_buffers);
+    // an ineligible T256x320 request is AUTO; WS / AUTO_TILED are AUTO as far as tile and split-K selection go
+    const int requested = d.tile == SEER_TILE_T256x320 ? SEER_TILE_AUTO : d.tile;
+    d.tile = (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) ? SEER_TILE_AUTO : requested;
+    const split_choice sc = choose_split(d);
+    const bool slices = !s320 && sc.splits > 1 &&          // the smaller tiles slice K, and have the workspace for it
+                        (assume_buffers || (d.workspace && d.workspace_bytes >= (int64_t)sc.splits * d.M * d.N * (int64_t)sizeof(float)));
+    auto take = [&p](int kernel, int tile, int splits) { p.kernel = kernel; p.tile = tile; p.splits = splits; };
+    tile_traits tile{};
+    if (s320) {
+        take(SEER_GEMM_KERNEL_T320, SEER_TILE_T256x320, s320);
+    } else if (slices && !rows_ln) {
+        take(SEER_GEMM_KERNEL_SPLITK, sc.tile, sc.splits);
+        p.reduce = !d.colsum_fx ? (d.colsum ? SEER_GEMM_REDUCE_COLSUM : SEER_GEMM_REDUCE_PLAIN)
+                 : splitk_fx_rows(d.M) == 64 ? SEER_GEMM_REDUCE_COLSUM_FX64 : SEER_GEMM_REDUCE_COLSUM_FX32;
+    } else {
+        const bool ws = !sums && !rows_ln && seer_gemm_ws_eligible(d) &&
+                        (requested == SEER_TILE_WS || (requested == SEER_TILE_AUTO && seer_gemm_ws_profitable(d)));
+        take(ws ? SEER_GEMM_KERNEL_WS : SEER_GEMM_KERNEL_TILE, resolve_tile(d), 1);
+        tile = traits_of(p.tile);
+    }
+    p.ln_ok = rows_ln && ln_resolve(d, tile);
+    // rows per column-sum partial of this launch.  256 x 320: one per wave row (64 rows) unsplit, per 16-row fragment when K is split;
+    // split-K: the strips of the reduce pass (the accumulating one owns bigger row blocks); else the tile's rows
+    const bool split = p.kernel == SEER_GEMM_KERNEL_SPLITK;
+    const int rows = !sums_stored ? 0 : s320 ? (d.M % 256 ? 0 : s320 > 1 ? 16 : 64)
+                   : (p.kernel == SEER_GEMM_KERNEL_TILE && tile.colsum_ok) ? tile.bm : 0;
+    // (slices && rows_ln: that launch stays unsplit and leaves TILE rows, but the queries have always answered with the strips there.
+    //  No caller asks for both; kept as it was, to be changed with a fixture of its own.)
+    p.colsum_rows = slices && sums_stored ? splitk_cs_rows(d.M) : rows;
+    p.colsum_fx_rows = slices && sums_stored ? splitk_fx_rows(d.M) : rows;
+    // what the launch cannot carry.  colsum_fx: no partial of this launch may straddle two batch elements
+    const bool fx_bad = d.colsum_fx && (d.colsum || d.colsum_fx_reps < 1 || d.colsum_fx_rows <= 0 || d.M % d.colsum_fx_rows ||
+                                        !p.colsum_fx_rows || d.colsum_fx_rows % p.colsum_fx_rows);
+    const bool sums_bad = sums && (split ? (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_GEGLU)) != 0 : !rows);
+    // (tile / weight-stationary launches: a tile code; GEGLU has no conv form, and its value / gate n-tile pairs must sit in one wave)
+    const bool tile_bad = !s320 && !split && (!tile.bm || (geglu && (d.mode == SEER_GEMM_CONV3X3 || (tile.bn / 32) % 2)));
+    if (fx_bad || sums_bad || tile_bad || (rows_ln && !p.ln_ok)) p.status = SEER_EINVAL;
+    return p;
+}
+
 }  // namespace
+
+extern "C" int seer_gemm_plan(const seer_gemm_desc* desc, int32_t out[5]) {
+    if (!desc || !out) return SEER_EINVAL;
+    const gemm_plan p = plan_gemm(*desc, false);
+    const bool ok = p.status == SEER_OK;          // a refused launch reports its status alone
+    out[0] = p.status; out[1] = ok ? p.kernel : 0; out[2] = ok ? p.tile : 0; out[3] = ok ? p.splits : 0; out[4] = ok ? p.reduce : 0;
+    return SEER_OK;
+}
 
 extern "C" int64_t seer_gemm_workspace_bytes(const seer_gemm_desc* desc) {
     if (!desc) return SEER_EINVAL;
-    seer_gemm_desc d = *desc;
-    const int s320 = t320_plan(d, true);
-    const int64_t w320 = s320 ? seer_gemm_t320_workspace_bytes(d, s320) : 0;
-    if (d.tile == SEER_TILE_T256x320) d.tile = SEER_TILE_AUTO;
-    if (d.tile == SEER_TILE_WS || d.tile == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;
-    int s = 1;
-    const int rc = prepare(d, &s);
-    if (rc != SEER_OK) return rc;
+    const gemm_plan p = plan_gemm(*desc, true);
+    if (p.kernel == SEER_GEMM_KERNEL_NONE) return p.status;
     // (a launch that is planned for the 256 x 320 tile but arrives without `sync` falls back to the smaller tiles: room for both)
-    const int64_t wold = s > 1 ? (int64_t)s * d.M * d.N * (int64_t)sizeof(float) : 0;
+    const int s = choose_split(p.d).splits;
+    const int64_t w320 = p.kernel == SEER_GEMM_KERNEL_T320 ? seer_gemm_t320_workspace_bytes(p.d, p.splits) : 0;
+    const int64_t wold = s > 1 ? (int64_t)s * p.d.M * p.d.N * (int64_t)sizeof(float) : 0;
     return w320 > wold ? w320 : wold;
 }
 
 extern "C" int64_t seer_gemm_sync_bytes(const seer_gemm_desc* desc) {
     if (!desc) return SEER_EINVAL;
-    if (const int s320 = t320_plan(*desc, true)) return seer_gemm_t320_sync_bytes(*desc, s320);
-    return 0;
+    const gemm_plan p = plan_gemm(*desc, true);
+    return p.kernel == SEER_GEMM_KERNEL_T320 ? seer_gemm_t320_sync_bytes(p.d, p.splits) : 0;
 }
 
+// the three column-sum / row-statistics queries ask about the launch WITH that feature: address 16 stands for its buffer
 extern "C" int32_t seer_gemm_colsum_rows(const seer_gemm_desc* desc) {
     if (!desc) return 0;
     seer_gemm_desc d = *desc;
-    if (const int s320 = t320_plan(d))            // one partial per wave row (64 rows) unsplit, per 16-row fragment when K is split
-        return ((d.epilogue & SEER_EPI_GEGLU) || !colsum_store_ok(d) || d.M % 256) ? 0 : (s320 > 1 ? 16 : 64);
-    if (d.tile == SEER_TILE_T256x320) d.tile = SEER_TILE_AUTO;
-    const int requested = d.tile;
-    if (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;
-    int s = 1;
-    if (prepare(d, &s) != SEER_OK) return 0;
-    if (!colsum_store_ok(d)) return 0;
-    if (s > 1 && d.workspace && d.workspace_bytes >= (int64_t)s * d.M * d.N * (int64_t)sizeof(float))
-        return d.batch <= 1 ? splitk_cs_rows(d.M) : 0;          // split-K: the reduce pass leaves them
-    d.splits = 1;
-    d.tile = desc->tile == SEER_TILE_T256x320 ? SEER_TILE_AUTO : desc->tile;
-    if (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;
-    const int rows = dispatch_tile(resolve_tile(d), [&](auto t) {
-        using T = decltype(t);
-        return tile_colsum_ok<T::BM, T::BN, T::NS, T::WM, T::WN>() ? (int)T::BM : 0;
-    });
-    return rows > 0 ? rows : 0;           // an unknown tile code comes back as a negative status
+    if (!d.colsum && !d.colsum_fx) d.colsum = reinterpret_cast<float*>(16);
+    return plan_gemm(d, false).colsum_rows;
 }
 
-// ---- folded LayerNorm (seer_gemm_desc::rowstat / ln_rowstat): such launches stay on the tile kernel, unsplit, with a staged
-// bf16 output.  Returns the tile code the launch takes, 0 when it cannot carry row statistics.
-int ln_resolve(const seer_gemm_desc& in) {
-    seer_gemm_desc d = in;
-    const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0;
-    if (d.mode != SEER_GEMM_PLAIN || d.batch > 1 || (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_SILU | SEER_EPI_QUICKGELU)))
-        return 0;
-    if (d.ldc % 8 || d.N % (geglu ? 16 : 8) || (reinterpret_cast<uintptr_t>(d.C) & 15)) return 0;      // the kernel's `staged`
-    if (d.rowstat && (geglu || d.colsum || d.colsum_fx)) return 0;
-    if (d.ln_rowstat && (d.A2 || !d.ln_wsum || (reinterpret_cast<uintptr_t>(d.ln_wsum) & 15))) return 0;
-    const bool special = d.tile == SEER_TILE_T256x320 || d.tile == SEER_TILE_WS || d.tile == SEER_TILE_AUTO_TILED;
-    if (special) d.tile = SEER_TILE_AUTO;
-    int sp = 1;
-    if (prepare(d, &sp) != SEER_OK) return 0;
-    d.splits = 1;
-    d.tile = special ? SEER_TILE_AUTO : in.tile;
-    const int tile = resolve_tile(d);
-    const int ok = dispatch_tile(tile, [&](auto t) {
-        using T = decltype(t);
-        return tile_ln_ok<T::BM, T::BN, T::NS, T::WM, T::WN>() ? 1 : 0;
-    });
-    return ok == 1 ? tile : 0;
+extern "C" int32_t seer_gemm_colsum_fx_layout(const seer_gemm_desc* desc, int32_t rows_per_batch, int32_t* reps) {
+    if (reps) *reps = 1;
+    if (!desc || rows_per_batch <= 0 || desc->M % rows_per_batch) return 0;
+    seer_gemm_desc d = *desc;
+    if (!d.colsum && !d.colsum_fx) d.colsum_fx = reinterpret_cast<int64_t*>(16);
+    const int rows = plan_gemm(d, false).colsum_fx_rows;
+    if (rows <= 0 || rows_per_batch % rows) return 0;
+    const int adds = rows_per_batch / rows;       // adds per address and launch without replicas
+    if (reps) *reps = adds <= 24 ? 1 : adds <= 48 ? 2 : adds <= 96 ? 4 : 8;
+    return rows;
 }
 
 extern "C" int32_t seer_gemm_rowstat_ok(const seer_gemm_desc* desc) {
     if (!desc) return 0;
     seer_gemm_desc d = *desc;
-    if (!d.rowstat) d.rowstat = reinterpret_cast<int64_t*>(16);      // the question is about the launch WITH row statistics
-    return ln_resolve(d) ? 1 : 0;
+    if (!d.rowstat) d.rowstat = reinterpret_cast<int64_t*>(16);
+    return plan_gemm(d, false).ln_ok ? 1 : 0;
 }
 
 extern "C" int32_t seer_gemm_lnfold_ok(const seer_gemm_desc* desc) {
@@ -1824,76 +1865,28 @@ extern "C" int32_t seer_gemm_lnfold_ok(const seer_gemm_desc* desc) {
     // than the tile kernel with the fold (58.7 vs 65.5 us, profiles/r02_tile_sweep_fastepi.log, against 7.6 us of LayerNorm)
     seer_gemm_desc d = *desc;
     d.ln_rowstat = nullptr;
-    if (d.tile == SEER_TILE_AUTO && !d.colsum && !d.colsum_fx && !d.rowstat && seer_gemm_ws_eligible(d) && seer_gemm_ws_profitable(d)) return 0;
-    return ln_resolve(*desc) ? 1 : 0;
-}
-
-extern "C" int32_t seer_gemm_colsum_fx_layout(const seer_gemm_desc* desc, int32_t rows_per_batch, int32_t* reps) {
-    if (reps) *reps = 1;
-    if (!desc || rows_per_batch <= 0 || desc->M % rows_per_batch) return 0;
-    int rows = seer_gemm_colsum_rows(desc);       // tile rows; 64 / 16 on the 256 x 320 tile; the strip of the split-K reduce pass
-    if (rows <= 0) return 0;
-    seer_gemm_desc d = *desc;
-    if (!t320_plan(d)) {
-        if (d.tile == SEER_TILE_T256x320 || d.tile == SEER_TILE_WS || d.tile == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;
-        int s = 1;
-        if (prepare(d, &s) == SEER_OK && s > 1 && d.workspace && d.workspace_bytes >= (int64_t)s * d.M * d.N * (int64_t)sizeof(float))
-            rows = splitk_fx_rows(d.M);           // the accumulating reduce pass owns bigger row blocks
-    }
-    if (rows_per_batch % rows) return 0;
-    const int adds = rows_per_batch / rows;       // adds per address and launch without replicas
-    if (reps) *reps = adds <= 24 ? 1 : adds <= 48 ? 2 : adds <= 96 ? 4 : 8;
-    return rows;
+    if (d.tile == SEER_TILE_AUTO && plan_gemm(d, false).kernel == SEER_GEMM_KERNEL_WS) return 0;
+    return plan_gemm(*desc, false).ln_ok ? 1 : 0;
 }
 
 extern "C" int seer_gemm_bf16(const seer_gemm_desc* desc, void* stream) {
     if (!desc) return SEER_EINVAL;
-    seer_gemm_desc d = *desc;
+    gemm_plan p = plan_gemm(*desc, false);
+    if (p.status != SEER_OK) return p.status;
+    p.d.splits = p.splits;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (d.colsum_fx) {                  // accumulated column sums: no partial of this launch may straddle two batch elements
-        if (d.colsum) return SEER_EINVAL;
-        int reps = 1;
-        if (seer_gemm_colsum_fx_layout(desc, d.colsum_fx_rows, &reps) <= 0 || d.colsum_fx_reps < 1) return SEER_EINVAL;
+    const bool f16 = (p.d.epilogue & SEER_EPI_F16) != 0;
+    switch (p.kernel) {
+        case SEER_GEMM_KERNEL_T320: return seer_gemm_t320_launch(p.d, p.splits, st);
+        case SEER_GEMM_KERNEL_SPLITK:
+            return f16 ? launch_split_t<true>(p.tile, p.d, p.reduce, st) : launch_split_t<false>(p.tile, p.d, p.reduce, st);
+        case SEER_GEMM_KERNEL_WS:
+            if (const int rc = seer_gemm_ws_launch(p.d, st); rc != SEER_ENOSYS) return rc;
+            [[fallthrough]];             // not on this device: the tile kernel takes it
+        default:
+            return dispatch_tile(p.tile, [&](auto t) {
+                using T = decltype(t);
+                return f16 ? launch_tile<T::BM, T::BN, T::NS, T::WM, T::WN, true>(p.d, st) : launch_tile<T::BM, T::BN, T::NS, T::WM, T::WN>(p.d, st);
+            });
     }
-    const bool rows_ln = d.rowstat || d.ln_rowstat;       // row statistics / folded LayerNorm: tile kernel, unsplit
-    if (rows_ln && !ln_resolve(d)) return SEER_EINVAL;
-    if (const int s320 = rows_ln ? 0 : t320_plan(d)) {
-        int sp = 1;
-        seer_gemm_desc chk = d;
-        chk.tile = SEER_TILE_AUTO;
-        const int rc320 = prepare(chk, &sp);         // the same argument checks as every other launch
-        if (rc320 != SEER_OK) return rc320;
-        d.K1 = chk.K1; d.lda2 = chk.lda2; d.batch = chk.batch; d.strideA = chk.strideA; d.strideW = chk.strideW; d.strideC = chk.strideC;
-        if ((d.colsum || d.colsum_fx) && ((d.epilogue & SEER_EPI_GEGLU) || !colsum_store_ok(d) || d.M % 256)) return SEER_EINVAL;
-        return seer_gemm_t320_launch(d, s320, st);
-    }
-    if (d.tile == SEER_TILE_T256x320) d.tile = SEER_TILE_AUTO;      // not eligible: the tile kernels take it
-    const int requested = d.tile;       // WS / AUTO_TILED are AUTO as far as tile and split-K selection go
-    if (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;
-    int s = 1;
-    const int rc = prepare(d, &s);
-    if (rc != SEER_OK) return rc;
-    if (s > 1 && !rows_ln && d.workspace && d.workspace_bytes >= (int64_t)s * d.M * d.N * (int64_t)sizeof(float)) {
-        d.splits = s;
-        return launch_split(d, st);
-    }
-    d.splits = 1;
-    d.tile = desc->tile == SEER_TILE_T256x320 ? SEER_TILE_AUTO : desc->tile;            // prepare() may have picked a split tile; unsplit launches choose their own below
-    if (!d.colsum && !d.colsum_fx && !rows_ln && seer_gemm_ws_eligible(d) &&
-        (requested == SEER_TILE_WS || (requested == SEER_TILE_AUTO && seer_gemm_ws_profitable(d)))) {
-        const int rc_ws = seer_gemm_ws_launch(d, st);
-        if (rc_ws != SEER_ENOSYS) return rc_ws;
-    }
-    if (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) d.tile = SEER_TILE_AUTO;   // the tile kernel picks its own
-
-    const int tile = resolve_tile(d);
-    if (d.epilogue & SEER_EPI_F16)
-        return dispatch_tile(tile, [&](auto t) {
-            using T = decltype(t);
-            return launch_tile<T::BM, T::BN, T::NS, T::WM, T::WN, true>(d, st);
-        });
-    return dispatch_tile(tile, [&](auto t) {
-        using T = decltype(t);
-        return launch_tile<T::BM, T::BN, T::NS, T::WM, T::WN>(d, st);
-    });
 }
