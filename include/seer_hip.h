@@ -193,6 +193,18 @@ typedef struct seer_gemm_desc {
 #define SEER_TILE_WS 19
 #define SEER_TILE_T256x320 22  /* 8 waves (4 x 2), 64 x 160 wave tiles, 142 FLOP per LDS-fill byte; N % 320 == 0; K slices reduced inside the launch (desc.sync) */
 #define SEER_TILE_AUTO_TILED 20   /* AUTO restricted to the tile kernel (A/B runs against the weight-stationary kernel) */
+/* AUTO with a LAYOUT-INVARIANT plan: kernel, tile, K slices and reduce pass are a function of mode, stride / upsample, the epilogue
+ * flags, N, K, K1 and which optional outputs are asked (colsum / colsum_fx / rowstat / ln_rowstat) -- never of M, n_img, Hin / Win,
+ * pointer values, a workspace being handed in, or the device.  An output row is then the same bits whatever other rows the launch
+ * holds: its K loop runs the same tile's order, its K slices have the same bounds and are added in slice order.  The plan is a tile
+ * launch or the split-K pair, never the weight-stationary or the 256 x 320 kernel (both depend on the device).  A plan with K slices
+ * needs desc.workspace of seer_gemm_workspace_bytes(): without it the launch is SEER_EINVAL, not an unsplit launch.  The column sums
+ * of a split plan cover fixed row blocks (colsum: 16 rows, colsum_fx: 32), and the four feature queries answer independently of M
+ * (seer_gemm_colsum_fx_layout still refuses a rows_per_batch its fixed row block does not divide).  One exception to "no pointer
+ * values": whether column sums can be taken from the stored tile reads the 16-byte alignment of C (with ldc and strideC), as under
+ * every request, so seer_gemm_colsum_rows / seer_gemm_colsum_fx_layout answer for the alignment they are asked with.
+ * Rule table: DESIGN.md. */
+#define SEER_TILE_AUTO_INVARIANT 23
 
 int seer_gemm_bf16(const seer_gemm_desc* desc /* host */, void* stream);
 /* bytes of workspace the call would use for split-K with this descriptor (0: it will not split) */

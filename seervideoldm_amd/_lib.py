@@ -31,6 +31,7 @@ SEER_ATTN_Q_PRESCALED = 1
 SEER_ATTN_F16 = 2
 SEER_TILE_AUTO, SEER_TILE_128x128, SEER_TILE_64x64, SEER_TILE_128x64 = 0, 1, 2, 3
 SEER_TILE_WS = 19
+SEER_TILE_AUTO_INVARIANT = 23      # AUTO with a plan that does not look at M, the workspace or the device (include/seer_hip.h)
 SEER_GEMM_KERNEL_NONE, SEER_GEMM_KERNEL_TILE, SEER_GEMM_KERNEL_SPLITK, SEER_GEMM_KERNEL_WS, SEER_GEMM_KERNEL_T320 = 0, 1, 2, 3, 4
 SEER_GEMM_REDUCE_NONE, SEER_GEMM_REDUCE_PLAIN, SEER_GEMM_REDUCE_COLSUM, SEER_GEMM_REDUCE_COLSUM_FX64, SEER_GEMM_REDUCE_COLSUM_FX32 = 0, 1, 2, 3, 4
 

@@ -848,8 +848,11 @@ __global__ void __launch_bounds__(64 * WM * WN) seer_gemm_kernel(const seer_gemm
     // residual into the staged C tile (every FF, projection, q|k|v and conv GEMM of the U-Net).  The general body below tests each descriptor flag for each of the
     // TM x TN accumulator quads and recomputes the staging address per quad: ~30 VALU instructions per quad, 3.2 us of VALU
     // issue per 256x256 tile and 1.6 us per 128x128 tile (profiles/r02_pp8_stamps.log).  Here every term is its own pass over
-    // the accumulators behind ONE wave-uniform branch, in the general body's order of additions (bit-identical results), and
-    // the staging address is one XOR per fragment column plus an immediate offset per fragment row.
+    // the accumulators behind ONE wave-uniform branch, in the general body's order of additions, and the staging address is one
+    // XOR per fragment column plus an immediate offset per fragment row.  The two bodies are NOT bit-identical in every class: the
+    // folded LayerNorm's term in front of a GEGLU differed in its last bits on MI355X (below; probably an fma contracted in one
+    // body and not in the other).  Follow-up: make ln_term contract alike in both, then the layout-invariant request can take
+    // this body again and stop paying the general body's VALU time on every tile.
     // row statistics of the output (seer_gemm_desc::rowstat): each lane adds the fp32 values of its quads per fragment row, the
     // four lanes of a row meet by two lane exchanges, one atomic pair per (row, wave column)
     constexpr bool RS_OK = !GEGLU && !SPLIT && tile_ln_ok<BM, BN, NS, WM, WN>();
@@ -860,7 +863,10 @@ __global__ void __launch_bounds__(64 * WM * WN) seer_gemm_kernel(const seer_gemm
 #pragma unroll
         for (int i = 0; i < TM; ++i) { rsum[i] = 0.f; rsq[i] = 0.f; }
     }
-    const bool fast_epi = staged && m0 + BM <= p.M && n0 + BN <= p.N && !do_silu && !do_qgelu &&
+    // (the layout-invariant request keeps EVERY tile on the general body: a row must not get other bits for sitting in a full tile in
+    //  one launch and in the ragged last tile of another -- measured on MI355X: the GEGLU projection with the folded LayerNorm, 192 rows
+    //  against 384, differed in its last bits between the two bodies)
+    const bool fast_epi = staged && m0 + BM <= p.M && n0 + BN <= p.N && !do_silu && !do_qgelu && p.tile != SEER_TILE_AUTO_INVARIANT &&
                           (!GEGLU || !(do_rot || (p.epilogue & SEER_EPI_COLSCALE))) && (!p.rowvec || (RV_PRE && rv_pre_ok)) &&
                           (!R || RES_PRE);          // a residual that was not prefetched takes the general body
     if (fast_epi) {
@@ -1287,12 +1293,13 @@ __global__ void __launch_bounds__(256) seer_splitk_reduce_kernel(const seer_gemm
 // at 16 rows per block the 384-row convs ran 120 blocks of 64-deep load chains, +12 us (profiles/r02_gn_colsums.log).
 // (Round 2 took this kernel out when a two-process test differed in the last bits with column sums on; the cause was elsewhere --
 // a packed-fp32 instruction form in the rotary epilogue, profiles/r03_flake_root_cause.md -- and it is back.)
-__host__ __device__ inline int splitk_cs_rows(int M) { return M >= 2048 ? 16 : 4; }
+// (inv: the layout-invariant plan, SEER_TILE_AUTO_INVARIANT -- one row block whatever M; the launch hands the request on in desc.tile)
+__host__ __device__ inline int splitk_cs_rows(int M, bool inv) { return (inv || M >= 2048) ? 16 : 4; }
 __global__ void __launch_bounds__(256) seer_splitk_reduce_colsum_kernel(const seer_gemm_desc p) {
     __shared__ float part[4][64][8];
     const int cq = threadIdx.x & 63, rl = threadIdx.x >> 6;
     const int n = (blockIdx.x * 64 + cq) * 4;
-    const int cs_rows = splitk_cs_rows(p.M);
+    const int cs_rows = splitk_cs_rows(p.M, p.tile == SEER_TILE_AUTO_INVARIANT);
     const int mb = blockIdx.y * cs_rows;
     float sm[4] = {0.f, 0.f, 0.f, 0.f}, sq[4] = {0.f, 0.f, 0.f, 0.f};
     if (n < p.N) {
@@ -1357,7 +1364,7 @@ __global__ void __launch_bounds__(256) seer_splitk_reduce_fx_kernel(const seer_g
         fx_add(o + p.N, b);
     }
 }
-__host__ inline int splitk_fx_rows(int M) { return M >= 1024 ? 64 : 32; }
+__host__ inline int splitk_fx_rows(int M, bool inv) { return (!inv && M >= 1024) ? 64 : 32; }
 
 // the kernel's `staged` condition, host side: column sums are taken from the staged bf16 tile
 bool colsum_store_ok(const seer_gemm_desc& d) {
@@ -1423,7 +1430,7 @@ int launch_split_tile(const seer_gemm_desc& d, int reduce, hipStream_t st) {
         hipLaunchKernelGGL((seer_splitk_reduce_fx_kernel<32, 32, 1>), dim3((unsigned)((d.N + 31) / 32), (unsigned)((d.M + 31) / 32)),
                            dim3(256), 0, st, d);
     } else if (reduce == SEER_GEMM_REDUCE_COLSUM) {
-        const int cs_rows = splitk_cs_rows(d.M);
+        const int cs_rows = splitk_cs_rows(d.M, d.tile == SEER_TILE_AUTO_INVARIANT);
         hipLaunchKernelGGL(seer_splitk_reduce_colsum_kernel, dim3((unsigned)((d.N + 255) / 256),
                            (unsigned)((d.M + cs_rows - 1) / cs_rows)), dim3(256), 0, st, d);
     } else {
@@ -1745,6 +1752,53 @@ bool ln_resolve(const seer_gemm_desc& d, const tile_traits& tile) {
     return tile.ln_ok;
 }
 
+// ---- the layout-invariant plan (SEER_TILE_AUTO_INVARIANT): the choices of choose_split() / resolve_tile() with the row count, the
+// grid's fill and the device taken out.  What is left to decide on is mode, N, K, the epilogue flags, batch > 1 and the optional
+// outputs asked, so rows 0 .. M-1 of a launch are the same bits whatever rows follow them.  One (N, K) class gets ONE choice for all
+// the row counts it occurs with (the choice of the default plan at the step's CFG pair, or the one between pair and half); table in
+// DESIGN.md.  No weight-stationary kernel, no 256 x 320 tile.
+split_choice invariant_split(const seer_gemm_desc& d) {
+    const int nk = d.K / BK;
+    const bool can_split = d.batch == 1 && !(d.epilogue & (SEER_EPI_GEGLU | SEER_EPI_TRANS_OUT | SEER_EPI_ROTARY)) && d.splits != 1 &&
+                           !d.rowstat && !d.ln_rowstat;
+    if (!can_split) return {1, SEER_TILE_AUTO};
+    if (d.splits > 1) return {d.splits < nk ? d.splits : nk, SEER_TILE_G64x64_3};      // slices asked for by number: the 64x64 ring, as AUTO
+    const bool conv = d.mode == SEER_GEMM_CONV3X3;
+    // the 8x8- and 4x4-level convs (N = 1280, K = 11 520 .. 23 040; 1536 / 384 rows at the CFG pair, 768 / 192 at one half): the
+    // default plan runs 4 slices at 1536 rows and 8 at 384; four serve both
+    if (conv && d.N % 160 == 0 && d.N >= 1024 && nk >= 88) return {4, SEER_TILE_G96x160_2};
+    // the 16x16-level convs (N = 640) from K = 5760 up: unsplit at 6144 rows, 4 slices at 3072 today; two
+    if (conv && d.N % 160 == 0 && d.N >= 512 && d.N < 1024 && nk >= 80) return {2, SEER_TILE_G96x160_2};
+    // ff.net.2 | proj_out of the 8x8 level (N = 1280, K = 6400): 2 slices at 1536 rows, 4 at 768 today
+    if (!conv && d.N % 128 == 0 && d.N >= 1024 && nk >= 88) return {4, SEER_TILE_G128x128_2};
+    return {1, SEER_TILE_AUTO};
+}
+
+int invariant_tile(const seer_gemm_desc& d) {
+    const int nk = d.K / BK;
+    const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0, rot = (d.epilogue & SEER_EPI_ROTARY) != 0;
+    const int ring64 = nk >= 64 ? SEER_TILE_G64x64_5 : nk >= 12 ? SEER_TILE_G64x64_3 : SEER_TILE_64x64;
+    const int n128 = (d.N + 127) / 128 * 128;
+    const bool n_fits_128 = (n128 - d.N) * 8 <= d.N;
+    int tile;
+    if (d.mode == SEER_GEMM_CONV3X3) tile = d.N % 160 == 0 ? SEER_TILE_G96x160_2 : ring64;      // every conv of the UNet; conv_out (N = 4)
+    else if (geglu) tile = SEER_TILE_G128x128_2;
+    else if ((d.N == 320 || d.N == 960) && nk >= 5) tile = rot ? SEER_TILE_G128x160_2 : SEER_TILE_G96x160_2;     // the 32x32 level
+    else if (d.N >= 1920 && n_fits_128) tile = (rot && d.N % 160 == 0) ? SEER_TILE_G96x160_2 : SEER_TILE_G128x128_2;   // q|k|v below it
+    else if (d.N >= 512 && d.N < 1024 && d.N % 64 == 0 && nk >= 5) tile = SEER_TILE_G128x64_3;      // the 16x16 level's projections
+    else tile = ring64;                                                                             // N = 1280: 8x8 and 4x4 level
+    // an optional output the tile cannot carry moves the launch to the first tile that can (a function of what is asked, not of M)
+    const int cand[] = {tile, SEER_TILE_G128x128_2, SEER_TILE_G128x64_3, SEER_TILE_G64x64_3, SEER_TILE_64x64};
+    for (int c : cand) {
+        const tile_traits t = traits_of(c);
+        if (geglu && (t.bn / 32) % 2) continue;
+        if ((d.rowstat || d.ln_rowstat) && !t.ln_ok) continue;
+        if ((d.colsum || d.colsum_fx) && !t.colsum_ok) continue;
+        return c;
+    }
+    return tile;
+}
+
 // ---- the launch plan: which kernel a descriptor gets, decided ONCE.  seer_gemm_bf16 launches it, the host queries read it.
 struct gemm_plan {
     int status;                          // SEER_OK: seer_gemm_bf16 launches this plan; else the code it returns
@@ -1752,6 +1806,7 @@ struct gemm_plan {
                                          // that runs if that launch hands back), K slices, SEER_GEMM_REDUCE_*; set whatever status says
     seer_gemm_desc d;                    // validated + normalised; d.tile: a tile kernel's code or AUTO; d.splits: still the request
     int colsum_rows, colsum_fx_rows;     // rows per partial of desc.colsum / desc.colsum_fx this launch leaves (0: it cannot)
+    int tile_splits;                     // the K slices the smaller tiles would run this descriptor with (whichever kernel took it)
     bool ln_ok;                          // rowstat / ln_rowstat: asked for and carried
 };
 
@@ -1764,13 +1819,17 @@ gemm_plan plan_gemm(const seer_gemm_desc& in, bool assume_buffers) {
     if (p.status != SEER_OK) return p;
     const bool geglu = (d.epilogue & SEER_EPI_GEGLU) != 0, sums = d.colsum || d.colsum_fx, sums_stored = colsum_store_ok(d);
     const bool rows_ln = d.rowstat || d.ln_rowstat;       // row statistics / folded LayerNorm: tile kernel, unsplit
-    const int s320 = t320_plan(d, assume_buffers);
+    // inv: the layout-invariant plan -- invariant_split() / invariant_tile() decide, nothing below looks at M or the workspace
+    const bool inv = d.tile == SEER_TILE_AUTO_INVARIANT;
+    const int s320 = inv ? 0 : t320_plan(d, assume_buffers);
     // an ineligible T256x320 request is AUTO; WS / AUTO_TILED are AUTO as far as tile and split-K selection go
     const int requested = d.tile == SEER_TILE_T256x320 ? SEER_TILE_AUTO : d.tile;
-    d.tile = (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED) ? SEER_TILE_AUTO : requested;
-    const split_choice sc = choose_split(d);
-    const bool slices = !s320 && sc.splits > 1 &&          // the smaller tiles slice K, and have the workspace for it
-                        (assume_buffers || (d.workspace && d.workspace_bytes >= (int64_t)sc.splits * d.M * d.N * (int64_t)sizeof(float)));
+    d.tile = (requested == SEER_TILE_WS || requested == SEER_TILE_AUTO_TILED || inv) ? SEER_TILE_AUTO : requested;
+    const split_choice sc = inv ? invariant_split(d) : choose_split(d);
+    p.tile_splits = sc.splits;
+    const bool room = d.workspace && d.workspace_bytes >= (int64_t)sc.splits * d.M * d.N * (int64_t)sizeof(float);
+    // the smaller tiles slice K, and have the workspace for it (inv: sliced whatever was handed in; without room it is refused below)
+    const bool slices = !s320 && sc.splits > 1 && (assume_buffers || room || inv);
     auto take = [&p](int kernel, int tile, int splits) { p.kernel = kernel; p.tile = tile; p.splits = splits; };
     tile_traits tile{};
     if (s320) {
@@ -1778,11 +1837,11 @@ gemm_plan plan_gemm(const seer_gemm_desc& in, bool assume_buffers) {
     } else if (slices && !rows_ln) {
         take(SEER_GEMM_KERNEL_SPLITK, sc.tile, sc.splits);
         p.reduce = !d.colsum_fx ? (d.colsum ? SEER_GEMM_REDUCE_COLSUM : SEER_GEMM_REDUCE_PLAIN)
-                 : splitk_fx_rows(d.M) == 64 ? SEER_GEMM_REDUCE_COLSUM_FX64 : SEER_GEMM_REDUCE_COLSUM_FX32;
+                 : splitk_fx_rows(d.M, inv) == 64 ? SEER_GEMM_REDUCE_COLSUM_FX64 : SEER_GEMM_REDUCE_COLSUM_FX32;
     } else {
         const bool ws = !sums && !rows_ln && seer_gemm_ws_eligible(d) &&
                         (requested == SEER_TILE_WS || (requested == SEER_TILE_AUTO && seer_gemm_ws_profitable(d)));
-        take(ws ? SEER_GEMM_KERNEL_WS : SEER_GEMM_KERNEL_TILE, resolve_tile(d), 1);
+        take(ws ? SEER_GEMM_KERNEL_WS : SEER_GEMM_KERNEL_TILE, inv ? invariant_tile(d) : resolve_tile(d), 1);
         tile = traits_of(p.tile);
     }
     p.ln_ok = rows_ln && ln_resolve(d, tile);
@@ -1793,8 +1852,8 @@ gemm_plan plan_gemm(const seer_gemm_desc& in, bool assume_buffers) {
                    : (p.kernel == SEER_GEMM_KERNEL_TILE && tile.colsum_ok) ? tile.bm : 0;
     // (slices && rows_ln: that launch stays unsplit and leaves TILE rows, but the queries have always answered with the strips there.
     //  No caller asks for both; kept as it was, to be changed with a fixture of its own.)
-    p.colsum_rows = slices && sums_stored ? splitk_cs_rows(d.M) : rows;
-    p.colsum_fx_rows = slices && sums_stored ? splitk_fx_rows(d.M) : rows;
+    p.colsum_rows = slices && sums_stored ? splitk_cs_rows(d.M, inv) : rows;
+    p.colsum_fx_rows = slices && sums_stored ? splitk_fx_rows(d.M, inv) : rows;
     // what the launch cannot carry.  colsum_fx: no partial of this launch may straddle two batch elements
     const bool fx_bad = d.colsum_fx && (d.colsum || d.colsum_fx_reps < 1 || d.colsum_fx_rows <= 0 || d.M % d.colsum_fx_rows ||
                                         !p.colsum_fx_rows || d.colsum_fx_rows % p.colsum_fx_rows);
@@ -1802,6 +1861,10 @@ gemm_plan plan_gemm(const seer_gemm_desc& in, bool assume_buffers) {
     // (tile / weight-stationary launches: a tile code; GEGLU has no conv form, and its value / gate n-tile pairs must sit in one wave)
     const bool tile_bad = !s320 && !split && (!tile.bm || (geglu && (d.mode == SEER_GEMM_CONV3X3 || (tile.bn / 32) % 2)));
     if (fx_bad || sums_bad || tile_bad || (rows_ln && !p.ln_ok)) p.status = SEER_EINVAL;
+    if (inv) {
+        if (split && !assume_buffers && !room) p.status = SEER_EINVAL;      // K slices without their workspace: an error, not an unsplit launch
+        d.tile = SEER_TILE_AUTO_INVARIANT;                                  // the reduce pass reads the request (splitk_cs_rows)
+    }
     return p;
 }
 
@@ -1820,7 +1883,7 @@ extern "C" int64_t seer_gemm_workspace_bytes(const seer_gemm_desc* desc) {
     const gemm_plan p = plan_gemm(*desc, true);
     if (p.kernel == SEER_GEMM_KERNEL_NONE) return p.status;
     // (a launch that is planned for the 256 x 320 tile but arrives without `sync` falls back to the smaller tiles: room for both)
-    const int s = choose_split(p.d).splits;
+    const int s = p.tile_splits;
     const int64_t w320 = p.kernel == SEER_GEMM_KERNEL_T320 ? seer_gemm_t320_workspace_bytes(p.d, p.splits) : 0;
     const int64_t wold = s > 1 ? (int64_t)s * p.d.M * p.d.N * (int64_t)sizeof(float) : 0;
     return w320 > wold ? w320 : wold;

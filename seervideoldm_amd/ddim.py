@@ -263,7 +263,7 @@ class DDIMSampler(object):
             return None
         ctx, L = eng._context(context)          # new prompt: the static context / K|V buffers are refreshed in place
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
-        key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape))
+        key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv)
         G = eng.graph_get(key)
         if G is None:
             G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L)

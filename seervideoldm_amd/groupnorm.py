@@ -19,13 +19,14 @@ def _classify(ops, srcs, use_colsums):
 
 
 def groupnorm(ops, x1, x2, batch, groups, rows_pb, eps, gamma, beta, silu, *, stats, use_colsums=True, fused=True, want_stats=False,
-              shard=None, sync=None, arena=None):
+              shard=None, sync=None, arena=None, exact=False):
     """GroupNorm over the rows of x1 | x2 (rows_pb rows per batch element) -> (y, did the statistics come from column sums?).
     stats: [batch, groups, 2] fp32 scratch of the caller; want_stats (with fused=False: the one-launch per-tile form leaves none): it
-    holds (sum, sumsq) on return.  shard, sync: parallel.FrameShard, the engine's sync_point; arena: the evaluation's ops.FxArena."""
+    holds (sum, sumsq) on return.  shard, sync: parallel.FrameShard, the engine's sync_point; arena: the evaluation's ops.FxArena.
+    exact: the exact-statistics form below whatever the shard layout (layout-invariant engines)."""
     srcs = [x1] if x2 is None else [x1, x2]
     count = rows_pb * (sum(x.shape[1] for x in srcs) // groups)
-    if shard is not None and shard.exact_stats and arena is not None and hasattr(ops, "groupnorm_stats_fx"):
+    if (exact or (shard is not None and shard.exact_stats)) and arena is not None and hasattr(ops, "groupnorm_stats_fx"):
         # frame shards (P > 1; batch groups alone exchange nothing and keep the forms below): EVERY GroupNorm normalises with exact
         # integer statistics -- a source whose producer left no accumulated sums (conv_in's output, tensors above the producers' row
         # limit) gets them from one pass over its rows; the sums stay with the tensor (a skip connection feeds a second GroupNorm

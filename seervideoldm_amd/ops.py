@@ -884,7 +884,7 @@ def conv_in(x: torch.Tensor, w_khwc: torch.Tensor, bias: torch.Tensor, dtype=bf1
     return y
 
 
-def conv_out(x: torch.Tensor, w_ohwc: torch.Tensor, bias: torch.Tensor, B: int, F: int, H: int, W: int) -> torch.Tensor:
+def conv_out(x: torch.Tensor, w_ohwc: torch.Tensor, bias: torch.Tensor, B: int, F: int, H: int, W: int, tile=0) -> torch.Tensor:
     """x [B*F*H*W, C0] bf16 -> [B, Cout, F, H, W] fp32 ; w fp32 [Cout,3,3,C0] (direct kernel) or, for Cout % 4 == 0,
     bf16 [Cout, 9*C0] in conv3x3 packing: implicit-GEMM on the MFMA path, batched over B with a transposed fp32 store
     (the [Cout, F*H*W] planes of NCFHW are C^T of the per-sample GEMM)."""
@@ -906,6 +906,7 @@ def conv_out(x: torch.Tensor, w_ohwc: torch.Tensor, bias: torch.Tensor, B: int, 
         d.epilogue = _lib.SEER_EPI_TRANS_OUT | _lib.SEER_EPI_OUT_F32 | (_lib.SEER_EPI_F16 if dt else 0)
         d.Hin, d.Win, d.Cin, d.Hout, d.Wout, d.stride, d.upsample = H, W, C0, H, W, 1, 0
         d.batch, d.strideA, d.strideW, d.strideC = B, M * C0, 0, Cout * M
+        d.tile = tile
         d.splits = 1
         _launch_gemm(d, x.device, "seer_gemm_bf16(conv_out)")
         return y

@@ -20,6 +20,7 @@ from typing import Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
+from . import _lib
 from . import ops as hip_ops
 from . import synth
 from .groupnorm import groupnorm, groupnorm_statistics
@@ -63,7 +64,7 @@ class SeerUNet(nn.Module):
                  up_block_types=("UpBlock3D", "CrossAttnUpBlock3D", "CrossAttnUpBlock3D", "CrossAttnUpBlock3D"),
                  block_out_channels=(320, 640, 1280, 1280), layers_per_block=2, downsample_padding=1,
                  mid_block_scale_factor=1, act_fn="silu", norm_num_groups=32, norm_eps=1e-5,
-                 cross_attention_dim=1280, attention_head_dim=8, compute_dtype=None):
+                 cross_attention_dim=1280, attention_head_dim=8, compute_dtype=None, layout_invariant=None):
         super().__init__()
         # the reference overwrites the block types / downsample padding with constants (unet_3d_condition.py:90-92)
         if len(block_out_channels) != 4:
@@ -95,6 +96,10 @@ class SeerUNet(nn.Module):
         if compute_dtype not in (None, torch.bfloat16, torch.float16):
             raise ValueError(f"compute_dtype {compute_dtype!r}: torch.bfloat16 or torch.float16 (fp32 accumulation either way)")
         self.compute_dtype = compute_dtype
+        # layout-invariant mode (off unless asked for): the output of one batch element depends on that element's inputs, the weights and
+        # the storage type only -- not on the batch it came in, the CFG layout, the rank / frame-shard layout or the device's CU count.
+        # True / False here or as an attribute before the first forward; None = the environment's SEER_LAYOUT_INVARIANT=1 (_Engine)
+        self.layout_invariant = layout_invariant
 
     # ---- construction / weights -------------------------------------------------------------------------------
     @classmethod
@@ -222,10 +227,46 @@ FX_MAX_ROWS = 100_000        # rows at the finest level up to which the LayerNor
 FX_MAX_ROWS_PB = int(os.environ.get("SEER_FX_MAX_ROWS_PB", "4096"))        # rows per batch element up to which a GroupNorm's statistics are accumulated in fixed point (_Engine._cb)
 
 
-def _switch(model, attr: str, env: Optional[str] = None) -> bool:
-    """an engine switch: the model's attribute if it is set, else the environment variable if the switch has one ("0" = off), else on"""
+def _switch(model, attr: str, env: Optional[str] = None, default: bool = True) -> bool:
+    """an engine switch: the model's attribute if it is set, else the environment variable if the switch has one, else `default`
+    (a switch that is on by default is turned off by "0", one that is off by default is turned on by "1")"""
     on = getattr(model, attr, None)
-    return bool(on) if on is not None else (env is None or os.environ.get(env, "1") != "0")
+    if on is not None:
+        return bool(on)
+    val = os.environ.get(env) if env is not None else None
+    return default if val is None else (val != "0" if default else val == "1")
+
+
+def _tiled(name):
+    """method of _InvariantOps: the backend's `name` with the layout-invariant tile request unless the caller names a tile"""
+    def call(self, *a, **k):
+        k.setdefault("tile", self.TILE)
+        return getattr(self._ops, name)(*a, **k)
+    call.__name__ = name
+    return call
+
+
+class _InvariantOps:
+    """an ops backend as the layout-invariant engine calls it: every launch of the GEMM family goes out with SEER_TILE_AUTO_INVARIANT
+    (a plan that does not look at the rows of the call or at the device, include/seer_hip.h), and the d = 40 attention kernel's
+    query-block form -- which AUTO picks by the workgroups of the call -- is pinned to the 32-query form.  Everything else is the
+    backend's own."""
+    TILE = _lib.SEER_TILE_AUTO_INVARIANT
+
+    def __init__(self, ops):
+        self._ops = ops
+
+    def __getattr__(self, name):
+        return getattr(self._ops, name)
+
+    gemm, gemm_batched, conv3x3 = _tiled("gemm"), _tiled("gemm_batched"), _tiled("conv3x3")
+    conv_up2x, conv_out = _tiled("conv_up2x"), _tiled("conv_out")
+
+    def attention(self, q, k, v, out, **kw):
+        # (IEEE-half operands always run the tracked form; key sequences under 256 the generic kernel: neither looks at the batch)
+        if kw.get("head_dim") == 40 and q.dtype == bf16 and kw.get("Sk", 0) >= 256:
+            kw.setdefault("variant", 3)
+        return self._ops.attention(q, k, v, out, **kw)
 
 
 def fx_arena(ops, sample, need: int, arena, retired: list):
@@ -278,6 +319,14 @@ class _Engine:
         self.ff_fused = self.ff_fold and _switch(model, "ff_fused", "SEER_FF_FUSED")
         self.rowchain = _switch(model, "rowchain", "SEER_ROWCHAIN") and hasattr(self.ops, "rowchain")
         self.ff_pre = self.rowchain and self.ff_fused and _switch(model, "ff_pre", "SEER_FF_PRE")
+        # layout_invariant (OFF unless asked for): every choice below that looks at the rows of the call, at the device or at the shard
+        #   layout is made per batch element on the clip's whole frame count instead -- the invariant GEMM plan and the pinned attention
+        #   form (_InvariantOps), exact integer GroupNorm statistics from the stored activations (no producer sums: their float partials
+        #   follow the tiles), the 320-channel launches by _pays320.  Same bits for any batch, CFG layout or shard layout; slower.
+        #   (fold_ln=False: the trainer's engine ignores it, as it ignores ln_fold)
+        self.inv = bool(fold_ln) and _switch(model, "layout_invariant", "SEER_LAYOUT_INVARIANT", default=False)
+        if self.inv:
+            self.ops = _InvariantOps(ops)
         self._fx_arena = None
         self._fx_retired: List[object] = []
         self._fx = None
@@ -434,9 +483,20 @@ class _Engine:
         self._stats_i += 1
         y, from_colsums = groupnorm(self.ops, x1, x2, B, self.G, rows_pb, eps, self.w[name + ".weight"], self.w[name + ".bias"], silu,
                                     stats=self._stats_arena[self._stats_i - 1], use_colsums=self.gn_colsums, fused=self.gn_fused,
-                                    shard=self.shard, sync=self.sync_point, arena=self._fx)
+                                    shard=self.shard, sync=self.sync_point, arena=self._fx, exact=self.inv)
         self.gn_from_colsums += from_colsums
         return y
+
+    def _rows_all(self, rows_pb):
+        """rows per batch element over ALL frames of the clip (a frame shard holds local_frames of total_frames)"""
+        sh = self.shard
+        return rows_pb if sh is None or not sh.local_frames else rows_pb // sh.local_frames * sh.total_frames
+
+    def _pays320(self, rows_pb):
+        """layout-invariant engines: do the row-owner launches of the 320-channel level (ops.rowchain, ops.ff_fused) run?  Decided on
+        the rows of ONE batch element over all its frames -- half of ops.FF_FUSED_MIN_ROWS, the rows from which a CFG pair takes them
+        by default -- and on nothing else: not the batch, not the shard's share, not the device."""
+        return self._rows_all(rows_pb) >= self.ops.FF_FUSED_MIN_ROWS // 2
 
     def _cb(self, B, rows_pb, for_chain=False):
         """`colsum_batch` of a launch whose output (rows_pb rows per batch element) feeds a GroupNorm: (B, arena) = accumulate in
@@ -444,7 +504,7 @@ class _Engine:
         64..128 channels: 160-byte pieces of a 640-byte row at the 32x32 level, ~20 % below the full-row kernel's bandwidth, and
         eight replicas to add per block): from the 16x16 level down 7.5 / 9.6 / 5.7 / 3.8 us against 8.4 / 12.1 / 7.6 / 5.7 for
         finalize + apply, at the 32x32 level 12.6 / 27.9 against 11.3 / 25.6 (profiles/r04_gn_fx_by_level.log)."""
-        if not self.gn_colsums:
+        if not self.gn_colsums or self.inv:         # (inv: every GroupNorm sums its stored activations exactly, _gn)
             return 0
         return (B, self._fx) if (self._fx is not None and (rows_pb <= FX_MAX_ROWS_PB or for_chain)) else B
 
@@ -455,6 +515,17 @@ class _Engine:
         that made the accumulated form lose at the 32x32 level is not run at all there).  Frame shards exchange the statistics
         between the two steps and keep the separate launches (batch groups alone run the single-process forms)."""
         ops = self.ops
+        if self.inv:        # (the chain reads exact sums, exchanged between frame shards first: _rc_in)
+            ok = bool(self.rowchain and C == ops.ROWCHAIN_C and hasattr(ops, "groupnorm_stats_fx") and self._pays320(rows_pb))
+            sh = self.shard
+            if ok and sh is not None and sh.local_frames:
+                # the launch needs ROWCHAIN_ROWS rows of a batch element on EVERY rank; falling back on one of them would give other
+                # bits than the unsharded clip.  Decided from the shard table every rank holds, before any exchange: all refuse together
+                least = rows_pb // sh.local_frames * min(sh.frame_counts)
+                if least < ops.ROWCHAIN_ROWS:
+                    raise RuntimeError(f"layout_invariant: {least} rows per batch element on the smallest of {len(sh.frame_counts)} frame "
+                                       f"shards, the GroupNorm -> q|k|v launch needs {ops.ROWCHAIN_ROWS}: use fewer frame shards")
+            return ok
         return bool(self.rowchain and (self.shard is None or not self.shard.exact_stats) and C == ops.ROWCHAIN_C and
                     rows_pb >= ops.ROWCHAIN_ROWS and ops.rowchain_pays(B * rows_pb))
 
@@ -464,12 +535,21 @@ class _Engine:
         ops, w = self.ops, self.w
         if not self._chain_ok(x.shape[1], B, rows_pb) or (p + ".rc.proj_in") not in w:
             return None
-        st, count, from_colsums = groupnorm_statistics(ops, x, B, self.G, rows_pb, stats=self._stats_arena[self._stats_i],
-                                                       use_colsums=self.gn_colsums)
+        if self.inv:
+            # exact integer sums of x's stored values, added over the frame shards: the statistics of the unsharded clip, bit for bit
+            if not isinstance(getattr(x, "colsums", None), ops.ColSumsFx):
+                x.colsums = ops.groupnorm_stats_fx(x, B, self._fx)
+            st, count, from_colsums = x.colsums, rows_pb * (x.shape[1] // self.G), False
+            if self.shard is not None:
+                count = self.shard.reduce_fx((st,), count, sync=self.sync_point)
+        else:
+            st, count, from_colsums = groupnorm_statistics(ops, x, B, self.G, rows_pb, stats=self._stats_arena[self._stats_i],
+                                                           use_colsums=self.gn_colsums)
         r = ops.rowchain(x, w[p + ".rc.proj_in"], b1=w[p + ".proj_in.bias"],
                          gn=(st, count, 1e-6, w[p + ".norm.weight"], w[p + ".norm.bias"], rows_pb, self.G),
                          ln=(w[tb + ".norm1.weight"], w[tb + ".norm1.bias"], 1e-5), w2f=w[tb + ".rc.qkv"], col_scale=(qs, 1), rotary=rotary)
         if r is None:
+            assert not self.inv, "layout_invariant: _chain_ok let a shape through that ops.rowchain refuses"
             return None
         self._stats_i += 1
         self.gn_from_colsums += from_colsums
@@ -523,6 +603,8 @@ class _Engine:
 
     def _ff_fused_rows(self, p, h):
         """will _ff_proj_out run transformer `p`'s feed-forward over the rows of h as the fused launch?"""
+        if self.inv:
+            return (p + ".ff_fused.w1f") in self.w and self._pays320(h.shape[0] // self._B)
         return (p + ".ff_fused.w1f") in self.w and self.ops.ff_fused_pays(h.shape[0])
 
     def _ff_pre(self, p, tb, h):
@@ -571,7 +653,7 @@ class _Engine:
                       Sq=HW, Sk=HW, q_prescaled=True)
         # text cross attention per frame (K/V depend on the context only: cached across DDIM steps)
         q = None
-        if rc is not None and (tb + ".rc.q") in w and ops.rowchain_pays(a.shape[0], products=2):
+        if rc is not None and (tb + ".rc.q") in w and (self._pays320(Fr * HW) if self.inv else ops.rowchain_pays(a.shape[0], products=2)):
             # attn1.to_out + residual (over h) -> norm2 -> attn2.to_q, one launch
             r2 = ops.rowchain(a, w[tb + ".rc.to_out"], b1=w[tb + ".attn1.to_out.0.bias"], res=h, h_out=h,
                               ln=(w[tb + ".norm2.weight"], w[tb + ".norm2.bias"], 1e-5), w2f=w[tb + ".rc.q"], col_scale=(qs, 1))
@@ -659,11 +741,14 @@ class _Engine:
                               Sq=Fr * HW, Sk=Fr * HW, causal=True, q_prescaled=True)
         # FF skips the conditioning frames (attention.py:241-246); frames are the slow index inside a batch element
         skip_f = cond_frame if self.shard is None else self.shard.local_cond_frames(cond_frame)
-        if skip_f <= 0 and self._ff_pre(p, tb, h):
+        # whole: every local row takes the feed-forward, so it runs in its folded / fused forms.  Layout-invariant engines decide on the
+        # CLIP's conditioning frames: a frame shard that holds none of them must run the form the unsharded clip runs on those frames
+        whole = skip_f <= 0 and not (self.inv and cond_frame > 0)
+        if whole and self._ff_pre(p, tb, h):
             return self._ff_proj_out(p, tb, h, x, self._cb(B, Fr * HW), a=a)    # attn1.to_out + residual inside the fused feed-forward launch
         ops.gemm(a, w[tb + ".attn1.to_out.0.weight"], bias=w[tb + ".attn1.to_out.0.bias"], residual=h, out=h,
-                 **({} if skip_f <= 0 and self._ff_fused_rows(p, h) else self._rs()))
-        if skip_f <= 0:
+                 **({} if whole and self._ff_fused_rows(p, h) else self._rs()))
+        if whole:
             return self._ff_proj_out(p, tb, h, x, self._cb(B, Fr * HW))
         elif skip_f < Fr:
             for b in range(B):
@@ -686,6 +771,7 @@ class _Engine:
         self._attn_wanted = {f"down_blocks.{i}.attentions.{lpb - 1}" for i in range(n - 1)} | {"mid_block.attentions.0"} | \
                             {f"up_blocks.{i}.attentions.{lpb}" for i in range(1, n)}
         self._ctx, self._ctx_len = ctx_bf16, ctx_len
+        self._B = B
         self._stats_arena = torch.empty((self.n_groupnorms(), B, self.G, 2), device=sample.device, dtype=torch.float32)
         self._stats_i = 0
         self.gn_from_colsums = 0        # GroupNorms of this forward that took their statistics from column sums
@@ -695,8 +781,8 @@ class _Engine:
         # the folded LayerNorm trades a launch per norm for atomics in proportion to the rows: ahead up to ~100 k rows at the finest
         # level (config 2: 24 576 rows -0.19 ms; 64x64 latent, 98 304 rows: even; bridge, 131 072 rows: +0.15 ms --
         # profiles/r04_fx_ln_other_configs.log), off above
-        small = B * Fr * H * W <= FX_MAX_ROWS
-        fx_gn = self.gn_fx and self.gn_colsums      # (per tensor: _cb; frame shards all-reduce the integer sums: FrameShard.reduce_fx)
+        small = (self._rows_all(Fr * H * W) if self.inv else B * Fr * H * W) <= FX_MAX_ROWS
+        fx_gn = (self.gn_fx and self.gn_colsums) or self.inv      # (per tensor: _cb; frame shards all-reduce the integer sums: FrameShard.reduce_fx)
         self._ln_on = self.ln_fold and small
         if (fx_gn or self._ln_on) and hasattr(ops, "FxArena"):
             # fixed-point accumulators of the evaluation: a [reps, B, 2, C] slot per colsum producer, a [rows, 2] slot per producer
@@ -809,7 +895,7 @@ class _Engine:
         """hipGraph replay of the shape-static step: ~1.3k launches -> one graph launch, or -- frame-sharded -- one graph
         launch per stretch between two collectives (GroupNorm statistics / K|V exchanges stay eager torch.distributed
         calls on the same stream)."""
-        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape))
+        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape), self.inv)
         g = self.graph_get(key)
         if g is None:
             # warm up eagerly (fills the K/V and rotary caches, creates process groups, lets allocations settle), then capture
