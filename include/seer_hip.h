@@ -519,6 +519,28 @@ int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
                            float scale, const float* coef, int32_t* step, const float* x, const float* noise, float* x_prev,
                            float* pred_x0, void* stream);
 
+/* The captured step over SLOTS (continuous batching, seervideoldm_amd/slots.py): the two kernels above with `slots` in the place of
+ * b and everything a replay must not freeze held per slot in device memory.  Row r of a [reps*slots, ...] tensor belongs to slot
+ * r % slots (uc rows, then c rows).  step: int32 [slots][2], the pair of seer_ddim_step_begin per slot; t_table: int64
+ * [slots][nsched]; coef: fp32 [slots][nsched][4]; scale: fp32 [slots], device memory.
+ *   seer_slot_step_begin     for every slot s: index = step[s][0], then step[s][1] = index; the sample rows of slot s =
+ *                            cat([x0_emb[s], x[s]], frames), `reps` (1 or 2) times; t_out[rep*slots + s] = t_table[s][max(index, 0)].
+ *                            An idle slot (index < 0) gets finite rows as long as its x / x0_emb are (the host zeroes them).
+ *   seer_slot_cfg_ddim_step  for every slot s: index = step[s][1].  index >= 0: the update of seer_cfg_ddim_step with cfg = 1,
+ *                            scale[s], row `index` of coef[s] and no noise term (eta = 0) -- the same device code, so an element gets
+ *                            the bits seer_cfg_ddim_step gives it -- then step[s][0] = index - 1.  index < 0 (or >= nsched, which no
+ *                            schedule produces): nothing of that slot is written, neither x_prev nor pred_x0 nor step.
+ *                            x_prev may be x; pred_x0 may be NULL.
+ * No kernel reads and writes the same word: replays walk every slot's schedule with no host-written scalar; the host writes
+ * step[s][0] only when it fills slot s.  Every pointer must be 4-byte aligned and no more (the int64 tables move as 32-bit words);
+ * SEER_EINVAL otherwise, and for slots < 1, nsched < 1, reps outside {1, 2}, cond_f >= F_total, a NULL pointer. */
+int seer_slot_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, int32_t slots, int32_t reps, int32_t C,
+                         int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched, int32_t* step,
+                         float* sample, int64_t* t_out, void* stream);
+int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                            const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x, float* x_prev,
+                            float* pred_x0, void* stream);
+
 /* CFG combine + PLMS update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:199-236; eta = 0, so no noise term), fp32.
  * e is the CFG-combined eps of this evaluation as in seer_cfg_ddim_step (frames >= cond_f only); h1, h2, h3 are earlier e,
  * newest first, each [b, C, F_pred, HW].  e' by `order`:

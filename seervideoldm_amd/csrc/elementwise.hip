@@ -2,6 +2,8 @@
 // conv_in / conv_out (layout change fused), casts, CFG + DDIM / PLMS update.
 #include "seer_common.h"
 #include <atomic>
+#include <cstdint>
+#include <initializer_list>
 
 namespace {
 
@@ -295,6 +297,20 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const bf16* __restric
 }
 
 // ---- CFG + DDIM update (fp32, one thread per latent element) ------------------------------------------------------
+// the update of element i from its CFG-combined eps e and row `index` of coef; one body for every form of the step, so an element
+// gets the same bits from each.  x may alias x_prev: the element is read before it is written.
+__device__ __forceinline__ void ddim_update(float e, const float* __restrict__ coef, int index, const float* x,
+                                            const float* __restrict__ noise, float* x_prev, float* __restrict__ pred_x0, int64_t i) {
+    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], sigma = coef[4 * index + 2], s1m = coef[4 * index + 3];
+    const float xv = x[i];
+    const float x0 = (xv - s1m * e) / sqrtf(a_t);
+    const float dir = sqrtf(1.f - a_prev - sigma * sigma) * e;
+    float nz = 0.f;
+    if (noise) nz = sigma * noise[i];
+    x_prev[i] = sqrtf(a_prev) * x0 + dir + nz;
+    if (pred_x0) pred_x0[i] = x0;
+}
+
 __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW,
                                 float scale, const float* __restrict__ coef, int index, const float* __restrict__ x,
                                 const float* __restrict__ noise, float* __restrict__ x_prev,
@@ -316,15 +332,7 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int cfg, int b, i
     } else {
         e = eps[eoff];
     }
-    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], sigma = coef[4 * index + 2],
-                s1m = coef[4 * index + 3];
-    const float xv = x[i];
-    const float x0 = (xv - s1m * e) / sqrtf(a_t);
-    const float dir = sqrtf(1.f - a_prev - sigma * sigma) * e;
-    float nz = 0.f;
-    if (noise) nz = sigma * noise[i];
-    x_prev[i] = sqrtf(a_prev) * x0 + dir + nz;
-    if (pred_x0) pred_x0[i] = x0;
+    ddim_update(e, coef, index, x, noise, x_prev, pred_x0, i);
 }
 
 // ---- the same step with its schedule index in DEVICE memory (a whole p_sample_ddim captured in one hipGraph: the kernel
@@ -374,14 +382,7 @@ __global__ void cfg_ddim_dev_kernel(const float* __restrict__ eps, int cfg, int 
     } else {
         e = eps[eoff];
     }
-    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], sigma = coef[4 * index + 2], s1m = coef[4 * index + 3];
-    const float xv = x[i];
-    const float x0 = (xv - s1m * e) / sqrtf(a_t);
-    const float dir = sqrtf(1.f - a_prev - sigma * sigma) * e;
-    float nz = 0.f;
-    if (noise) nz = sigma * noise[i];
-    x_prev[i] = sqrtf(a_prev) * x0 + dir + nz;
-    if (pred_x0) pred_x0[i] = x0;
+    ddim_update(e, coef, index, x, noise, x_prev, pred_x0, i);
 }
 
 // ---- CFG + PLMS update (ldm/models/diffusion/plms.py:199-236, eta = 0; fp32, one thread per latent element) -----------------
@@ -462,6 +463,52 @@ __global__ void cfg_plms_dev_kernel(const float* __restrict__ eps, int cfg, int 
     const float* h3 = ring + (int64_t)slot * n;
     plms_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), valid == 0 ? 0 : valid + 1, h1, h2, h3, i, coef, index,
                 x, x_prev, pred_x0, ring + (int64_t)slot * n);
+}
+
+// ---- the captured step over SLOTS (continuous batching, seervideoldm_amd/slots.py): per-slot forms of ddim_assemble_kernel and
+// cfg_ddim_dev_kernel.  Slot s owns rows s and slots + s of the [uc | c] pair, its own schedule tables t_table[s][nsched] and
+// coef[s][nsched][4], its own guidance scale scale[s] and its own counter pair step[s][0..1].  An idle slot (index < 0) still gets
+// finite input rows (the host zeroed its latents; its t is row 0 of its table) and its update writes nothing.  As above, no kernel
+// reads and writes the same word.  The int64 tables move as int32 pairs: no pointer is relied on beyond 4-byte alignment.
+__global__ void slot_assemble_kernel(const float* __restrict__ x0_emb, const float* __restrict__ x, int slots, int reps, int C, int f1,
+                                     int Fp, int HW, const int* __restrict__ t_table, int nsched, int* __restrict__ step,
+                                     float* __restrict__ sample, int* __restrict__ t_out) {
+    const int F = f1 + Fp;
+    const int64_t per_slot = (int64_t)C * F * HW;
+    const int64_t per = (int64_t)slots * per_slot;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per) return;
+    const int s = (int)(i / per_slot);
+    if (i == (int64_t)s * per_slot) {                    // the slot's first element: its counter and its timesteps
+        const int index = step[2 * s];
+        step[2 * s + 1] = index;
+        const int row = index < 0 ? 0 : (index < nsched ? index : nsched - 1);      // never outside the table
+        const int* t = t_table + 2 * ((int64_t)s * nsched + row);
+        for (int r = 0; r < reps; ++r) {
+            t_out[2 * (r * slots + s)] = t[0];
+            t_out[2 * (r * slots + s) + 1] = t[1];
+        }
+    }
+    const int hw = (int)(i % HW);
+    const int f = (int)((i / HW) % F);
+    const int64_t bc = i / ((int64_t)HW * F);            // s * C + c
+    const float v = f < f1 ? x0_emb[(bc * f1 + f) * HW + hw] : x[(bc * Fp + (f - f1)) * HW + hw];
+    for (int r = 0; r < reps; ++r) sample[i + r * per] = v;
+}
+
+// CFG always on, eta = 0 (no noise term): cfg_eps_at with scale[s], ddim_update with row step[s][1] of coef[s].  x may alias x_prev.
+__global__ void slot_cfg_ddim_kernel(const float* __restrict__ eps, int slots, int C, int Ft, int cond_f, int HW,
+                                     const float* __restrict__ scale, const float* __restrict__ coef, int nsched,
+                                     int* __restrict__ step, const float* x, float* x_prev, float* __restrict__ pred_x0) {
+    const int64_t per_slot = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)slots * per_slot) return;
+    const int s = (int)(i / per_slot);
+    const int index = step[2 * s + 1];
+    if (index < 0 || index >= nsched) return;            // idle (or a counter outside the table): nothing of this slot is written
+    if (i == (int64_t)s * per_slot) step[2 * s] = index - 1;
+    ddim_update(cfg_eps_at(eps, 1, slots, C, Ft, cond_f, HW, scale[s], i), coef + (int64_t)s * nsched * 4, index, x, nullptr, x_prev,
+                pred_x0, i);
 }
 
 // pointwise channel mix on NCHW fp32 (VAE post_quant_conv, 4 -> 4): y[n,co,p] = sum_ci W[co,ci] x[n,ci,p] + b[co]
@@ -672,6 +719,43 @@ extern "C" int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, 
     const int64_t n = (int64_t)b * C * (F_total - cond_f) * HW;
     hipLaunchKernelGGL(cfg_ddim_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, cfg, b, C, F_total,
                        cond_f, HW, scale, coef, step, x, noise, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+// the slot kernels rely on 4-byte alignment of every pointer (the int64 tables included) and on a grid that fits one dimension
+static inline bool slot_ptrs_ok(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & 3) return false;
+    return true;
+}
+
+extern "C" int seer_slot_step_begin(const float* x0_emb, const float* x, int32_t slots, int32_t reps, int32_t C, int32_t f1,
+                                    int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched, int32_t* step, float* sample,
+                                    int64_t* t_out, void* stream) {
+    if (!x || !t_table || !step || !sample || !t_out || slots < 1 || nsched < 1 || (reps != 1 && reps != 2) || C <= 0 || f1 < 0 ||
+        F_pred <= 0 || HW <= 0 || (f1 > 0 && !x0_emb))
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({x0_emb, x, t_table, step, sample, t_out})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * ((int64_t)f1 + F_pred) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_assemble_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x0_emb, x, slots, reps, C, f1,
+                       F_pred, HW, reinterpret_cast<const int*>(t_table), nsched, step, sample, reinterpret_cast<int*>(t_out));
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                       const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
+                                       float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !scale || !coef || !step || !x || !x_prev || slots < 1 || nsched < 1 || C <= 0 || cond_f < 0 || cond_f >= F_total ||
+        HW <= 0)
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({eps, scale, coef, step, x, x_prev, pred_x0})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * ((int64_t)F_total - cond_f) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_cfg_ddim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total, cond_f,
+                       HW, scale, coef, nsched, step, x, x_prev, pred_x0);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

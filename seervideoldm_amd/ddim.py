@@ -309,20 +309,29 @@ class DDIMSampler(object):
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
             self._graph_update(G, eps, cfg, scale, f1)
-        try:
-            body()                                   # warm-up: K|V / rotary caches, allocations
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                body()
-        except Exception as e:      # noqa: BLE001  capture refused: keep the launch-by-launch path
+        if capture_step(eng, key, G, body) is None:
             self._step_graph_broken = True
-            import warnings
-            warnings.warn(f"hipGraph capture of the sampler step failed ({type(e).__name__}: {e}); stepping launch by launch")
             return None
-        G["graph"] = g
-        eng.graph_put(key, G)
         return G
+
+
+def capture_step(eng, key, G, body):
+    """`body` (the launches of one sampler step over the static buffers in G) as ONE hipGraph: a warm-up run, the capture, and the
+    entry G -- with the graph under "graph" -- in the engine's graph cache under `key`.  Returns G, or None with a warning when the
+    capture is refused: the caller keeps the launch-by-launch path.  (DDIMSampler / PLMSSampler and slots.SlotSampler)"""
+    try:
+        body()                                       # warm-up: K|V / rotary caches, allocations
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            body()
+    except Exception as e:      # noqa: BLE001  capture refused: keep the launch-by-launch path
+        import warnings
+        warnings.warn(f"hipGraph capture of the sampler step failed ({type(e).__name__}: {e}); stepping launch by launch")
+        return None
+    G["graph"] = g
+    eng.graph_put(key, G)
+    return G
 
 
 def _from_rank0(unet, t: torch.Tensor) -> torch.Tensor:

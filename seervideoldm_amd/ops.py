@@ -987,6 +987,44 @@ def cfg_ddim_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, st
                                              _p(noise), _p(x_prev), _p(pred_x0), _stream()), "seer_cfg_ddim_step_dev")
 
 
+def slot_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: torch.Tensor, step: torch.Tensor, reps: int,
+                    sample: torch.Tensor, t_out: torch.Tensor) -> None:
+    """ddim_step_begin over slots (x [slots, C, Fp, h, w]): t_table int64 [slots, nsched] and step int32 [slots, 2] hold a schedule
+    and a counter pair per slot; row rep * slots + s of sample / t_out is slot s (include/seer_hip.h, seer_slot_step_begin)"""
+    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    slots, Cc, Fp, h, w = x.shape
+    f1 = 0 if x0_emb is None else x0_emb.shape[2]
+    if x0_emb is not None:
+        _req(x0_emb, torch.float32, "x0_emb")
+        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
+    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * slots, Cc, f1 + Fp, h, w)
+    assert t_table.is_contiguous() and t_table.dim() == 2 and t_table.shape[0] == slots
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
+    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.is_contiguous() and t_out.numel() == reps * slots
+    check(_lib.load().seer_slot_step_begin(_p(x0_emb), _p(x), slots, reps, Cc, f1, Fp, h * w, _p(t_table), t_table.shape[1],
+                                           _p(step), _p(sample), _p(t_out), _stream()), "seer_slot_step_begin")
+
+
+def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *,
+                       cond_f: int, x_prev: torch.Tensor, pred_x0: Optional[torch.Tensor]) -> None:
+    """cfg_ddim_step_dev over slots, CFG on, eta = 0: slot s updates x[s] from eps rows s and slots + s with scale[s] and row
+    step[s, 1] of coef[s] (fp32 [slots, nsched, 4]), then step[s, 0] = that index - 1; a slot whose index is negative is left
+    untouched.  x_prev may be x (include/seer_hip.h, seer_slot_cfg_ddim_step)"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    _req(scale, torch.float32, "scale")
+    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
+    slots, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
+    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
+    if pred_x0 is not None:
+        _req(pred_x0, torch.float32, "pred_x0")
+        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
+    check(_lib.load().seer_slot_cfg_ddim_step(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+                                              _p(x), _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
+
+
 def cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, order: int, *, cfg: bool, scale: float,
                   cond_f: int, history=(), x_prev: Optional[torch.Tensor] = None, pred_x0: Optional[torch.Tensor] = None,
                   e_out: Optional[torch.Tensor] = None, want_pred_x0=True, want_e=True):

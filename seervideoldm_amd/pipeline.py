@@ -14,10 +14,12 @@ Everything numeric runs in libseer_hip.so through SeerUNet / FSTextTransformer /
 """
 from __future__ import annotations
 
-from typing import List, Optional
+import itertools
+from typing import Iterable, Iterator, List, Optional, Tuple
 
 import torch
 
+from . import ops
 from .ddim import ddim_sample
 
 
@@ -49,6 +51,50 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
         clips.append(ddim_sample(sampler, sunet, vae, shape=(b, c_l, f2, h_l, w_l), c=c, start_code=noise, x0_emb=x0_emb,
                                  ddim_steps=ddim_steps, scale=scale, uc=uc))
     return clips
+
+
+@torch.no_grad()
+def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
+                   latent_generator: Optional[torch.Generator] = None, max_steps: int = 64) -> Iterator[Tuple[object, torch.Tensor]]:
+    """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
+    finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
+    empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag).  The VAE encode
+    (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
+    only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
+    (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
+    from .slots import SlotSampler
+    f1, f2 = cond_frames, num_frames - cond_frames
+    fstext_model.set_numframe(num_frames)
+    sampler: List[SlotSampler] = []
+
+    def admitted():
+        for r in requests:
+            x0_image = r["x0_image"]
+            if x0_image.shape[2] == 1:
+                x0_image = x0_image.expand(-1, -1, f1, -1, -1)
+            assert x0_image.shape[0] == 1 and x0_image.shape[2] == f1, "x0_image must hold one clip of one frame or cond_frames frames"
+            frames = x0_image.permute(0, 2, 1, 3, 4).reshape(f1, *x0_image.shape[1:2], *x0_image.shape[3:])    # (b f) c h w
+            lat = vae.encode(frames).latent_dist.sample(generator=latent_generator) * 0.18215
+            x0_emb = lat.reshape(1, f1, *lat.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()                     # b c f h w
+            c = fstext_model(context=r["text_emb"])
+            uc = r["empty_emb"].unsqueeze(1).expand(-1, c.shape[1], -1, -1).contiguous()
+            if not sampler:
+                _, c_l, _, h_l, w_l = x0_emb.shape
+                sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
+                                           max_steps=max_steps, device=x0_emb.device))
+            yield dict(x_T=r["noise"], x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
+                       tag=r.get("tag"))
+
+    reqs = admitted()
+    first = next(reqs, None)
+    if first is None:
+        return
+    for tag, lat in sampler[0].run(itertools.chain([first], reqs)):
+        n, ch, f, h, w = lat.shape
+        z = (lat.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
+        x = vae.decode(z).sample
+        x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
+        yield tag, ops.clamp01_(x.float())
 
 
 def concat_all_gather(t: torch.Tensor, process_group=None) -> torch.Tensor:

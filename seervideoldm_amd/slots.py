@@ -1,0 +1,225 @@
+"""SlotSampler -- continuous batching of clips in ONE captured DDIM step.
+
+The engine is bound by fixed costs, not by its matrix units: a second clip in the same step costs a fraction of a step
+("SlotSampler").  DDIMSampler cannot use that: it has one schedule index and one guidance scale for the whole batch,
+the scale is frozen into the captured graph, and a batch starts and ends together.  Here a fixed number of SLOTS share one step:
+
+    seer_slot_step_begin  ->  the UNet over [uc rows | c rows] of all slots  ->  seer_slot_cfg_ddim_step
+
+Each slot has its own schedule tables, step counter, guidance scale, prompt and conditioning frames, all in static device buffers, so
+the step is captured ONCE per (slots, clip shape, context shape, engine mode) -- neither the scale nor a schedule is part of the key --
+and a slot is refilled as soon as its clip is done.  The kernels count every slot's schedule down themselves; the host writes a
+slot's counter only when it fills the slot, and it knows from its own count when the slot finishes: step() reads nothing back.
+
+What a slot promises (INTEGRATION.md has the full list): under `SeerUNet(layout_invariant=True)` and scale != 1 the latent of a clip
+is bit for bit the one DDIMSampler.sample returns for that clip alone (batch 1, eta = 0, the same scale and start code), whatever the
+other slots hold and whenever it was admitted.  At scale == 1 the solo sampler evaluates once without CFG, a slot evaluates the pair
+and combines it with scale 1: not the same bits.  Without the invariant mode a slot is a row of a batch of `slots` clips: the same
+kernels, results within the layout tolerance.  The captured step and the launch-by-launch step give the same bits in either mode.
+The reference's per-step RNG draw (ddim_video.py:234) has no counterpart here: slots are deterministic, nothing consumes the device
+RNG stream.
+
+Out of scope: PLMS, eta > 0, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
+capture.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, Iterator, List, Optional, Tuple
+
+import torch
+
+from . import ops as hip_ops
+from .ddim import DDIMSampler, capture_step
+
+MAX_SLOTS = 4           # the time-embedding MLP (seer_linear_smallm) takes up to 8 rows: the [uc | c] pair of 4 slots
+
+
+class SlotSampler:
+    """`slots` clips of one shape in one step.  shape = (C, F_pred, h, w) of a clip's latent, cond_frames = f1 conditioning latents
+    in front of it (x0_emb), context_shape = (L, D) of one frame's text context.  `model_cond_frame` is the `cond_frame` the UNet is
+    called with -- DDIMSampler.sample's `cond_frames` keyword, which ddim_sample leaves at 0.  `ops` is the backend of the two
+    step-boundary kernels (tests inject a torch restatement to run the host logic on the CPU); a `unet` that is no SeerUNet is called
+    as `unet(sample, t, context, cond_frame=...)`."""
+
+    def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
+                 model_cond_frame: int = 0):
+        C, Fp, h, w = (int(v) for v in shape)
+        L, D = (int(v) for v in context_shape)
+        f1 = int(cond_frames)
+        if not 1 <= int(slots) <= MAX_SLOTS:
+            raise ValueError(f"slots = {slots}: 1 .. {MAX_SLOTS} (the [uc | c] rows of all slots go through the 8-row time embedding)")
+        if min(C, Fp, h, w, L, D) < 1 or f1 < 0 or int(max_steps) < 1:
+            raise ValueError(f"shape {tuple(shape)}, cond_frames {cond_frames}, context_shape {tuple(context_shape)}, max_steps {max_steps}")
+        if device is None:
+            p0 = next(unet.parameters(), None) if hasattr(unet, "parameters") else None
+            device = p0.device if p0 is not None else "cpu"
+        self.unet, self.ops, self.slots, self.max_steps = unet, ops, int(slots), int(max_steps)
+        self.shape, self.f1, self.context_shape, self.model_cond_frame = (C, Fp, h, w), f1, (L, D), int(model_cond_frame)
+        self.device = dev = torch.zeros((), device=device).device      # "cuda" -> the current device, with its index: what an engine reports
+        n, f32 = self.slots, torch.float32
+        # the static buffers of the step: everything the kernels and the UNet read, by address, for as long as this sampler lives
+        self._x = torch.zeros((n, C, Fp, h, w), device=dev, dtype=f32)
+        self._pred = torch.zeros_like(self._x)
+        self._x0 = torch.zeros((n, C, f1, h, w), device=dev, dtype=f32) if f1 else None
+        self._sample = torch.zeros((2 * n, C, f1 + Fp, h, w), device=dev, dtype=f32)
+        self._t = torch.zeros((2 * n,), device=dev, dtype=torch.long)
+        self._step = torch.full((n, 2), -1, device=dev, dtype=torch.int32)           # every slot idle
+        self._coef = torch.zeros((n, self.max_steps, 4), device=dev, dtype=f32)
+        self._coef[:, :, 0] = 1.0                    # a_t = 1 in the unused rows, as DDIMSampler's captured step keeps them
+        self._ttab = torch.zeros((n, self.max_steps), device=dev, dtype=torch.long)
+        self._scale = torch.ones((n,), device=dev, dtype=f32)
+        self._context = torch.zeros((2 * n, f1 + Fp, L, D), device=dev, dtype=f32)    # uc rows, then c rows
+        self._left = [0] * n                          # steps a slot still has to run; 0 = free
+        self._sched = DDIMSampler(dev)
+        self._tables: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._capture_refused = False
+
+    # ---- the queue's host side -----------------------------------------------------------------------------------------------
+    def free_slots(self) -> List[int]:
+        return [s for s, left in enumerate(self._left) if left == 0]
+
+    def active(self) -> List[int]:
+        return [s for s, left in enumerate(self._left) if left > 0]
+
+    def pred_x0(self, slot: int) -> torch.Tensor:
+        """a copy of the slot's pred_x0 of its last step (it stays readable after the slot retired, until the slot is refilled)"""
+        return self._pred[slot:slot + 1].clone()
+
+    def _schedule(self, S: int):
+        """DDIMSampler.make_schedule(S): the same tables bit for bit, made once per S"""
+        if S not in self._tables:
+            self._sched.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=False)
+            self._tables[S] = (self._sched.ddim_coef, self._sched._t_table)
+        return self._tables[S]
+
+    def _clip(self, t: Optional[torch.Tensor], want, what: str) -> torch.Tensor:
+        if t is None or tuple(t.shape) not in (tuple(want), (1, *want)):
+            raise ValueError(f"{what}: shape {None if t is None else tuple(t.shape)}, this sampler takes {tuple(want)} (with or without "
+                             "a leading 1)")
+        return t.reshape(want).to(device=self.device, dtype=torch.float32)
+
+    @torch.no_grad()
+    def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0.) -> int:
+        """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
+        [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
+        empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
+        scale the guidance scale.  The clip's tables, scale, start index, latents and its two context rows are written into the
+        slot's part of the static buffers; the engine's 16-bit context and the cross-attention K|V of the text blocks are then
+        refreshed at the next step through the engine's own context path -- over ALL slots, not only the one that changed (1 + 16
+        small launches per admission; a per-slot refresh is not built).
+        Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
+        constructor's, eta != 0 and a frame-sharded model."""
+        C, Fp, h, w = self.shape
+        F, (L, D) = self.f1 + Fp, self.context_shape
+        if eta != 0:
+            raise ValueError(f"eta = {eta}: slots run the deterministic update only (eta = 0)")
+        if getattr(self.unet, "_shard", None) is not None:
+            raise ValueError("a frame-sharded model cannot run slots: detach it (parallel.attach) first")
+        x_T = self._clip(x_T, (C, Fp, h, w), "x_T")
+        if self.f1:
+            x0_emb = self._clip(x0_emb, (C, self.f1, h, w), "x0_emb")
+        elif x0_emb is not None:
+            raise ValueError("x0_emb given to a sampler built with cond_frames = 0")
+        c, uc = self._clip(c, (F, L, D), "c"), self._clip(uc, (F, L, D), "uc")
+        coef, ttab = self._schedule(int(S))
+        n = int(coef.shape[0])
+        if n > self.max_steps:
+            raise ValueError(f"S = {S} makes a schedule of {n} entries, this sampler was built for max_steps = {self.max_steps}")
+        free = self.free_slots()
+        if not free:
+            raise RuntimeError(f"all {self.slots} slots are busy: step() until one finishes")
+        s = free[0]
+        self._coef[s, :n].copy_(coef)
+        self._ttab[s, :n].copy_(ttab)
+        self._scale[s:s + 1].fill_(float(scale))
+        self._x[s].copy_(x_T)
+        if self.f1:
+            self._x0[s].copy_(x0_emb)
+        self._context[s].copy_(uc)
+        self._context[self.slots + s].copy_(c)
+        self._step[s, :1].fill_(n - 1)               # the one host-written counter of the clip: the kernels count it down
+        self._left[s] = n
+        return s
+
+    # ---- the step ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self) -> List[Tuple[int, torch.Tensor]]:
+        """One step of every active slot (one replay, or the same three calls launch by launch).  Returns (slot, latent
+        [1, C, F_pred, h, w]) for the slots that finished with it: their latent is a copy, their buffers are zeroed and they are free
+        again.  Does nothing when every slot is idle."""
+        if not self.active():
+            return []
+        self._run_step()
+        done = []
+        for s in self.active():
+            self._left[s] -= 1
+            if self._left[s] == 0:
+                done.append((s, self._x[s:s + 1].clone()))
+                self._x[s].zero_()                   # an idle slot's rows stay finite (its counter is -1 by now: the kernels saw to it)
+                if self.f1:
+                    self._x0[s].zero_()
+        return done
+
+    def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
+        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=): fills free slots in request order (a
+        request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
+        finishing order."""
+        it, tags, more = iter(requests), {}, True
+        while True:
+            while more and self.free_slots():
+                r = next(it, None)
+                if r is None:
+                    more = False
+                    break
+                r = dict(r)
+                tag = r.pop("tag", None)
+                tags[self.submit(**r)] = tag
+            if not self.active():
+                return
+            for s, lat in self.step():
+                yield tags.pop(s), lat
+
+    def _body(self, model) -> None:
+        self.ops.slot_step_begin(self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t)
+        eps = model()
+        self.ops.slot_cfg_ddim_step(eps, self._x, self._scale, self._coef, self._step, cond_f=self.f1, x_prev=self._x,
+                                    pred_x0=self._pred)
+
+    def _run_step(self) -> None:
+        from .unet import SeerUNet
+        unet = self.unet
+        if not isinstance(unet, SeerUNet):
+            self._body(lambda: unet(self._sample, self._t, self._context, cond_frame=self.model_cond_frame).float().contiguous())
+            return
+        if unet._shard is not None or unet.config.center_input_sample:
+            raise ValueError("slots run an unsharded model without center_input_sample")
+        if self.shape[2] % 8 or self.shape[3] % 8:
+            raise ValueError("latent height/width must be multiples of 8 (three stride-2 levels + 4/8 windows)")
+        if unet._engine is None or unet._engine.device != self.device:
+            unet.prepare()
+        eng = unet._engine
+        ctx, L = eng._context(self._context)         # a new admission (or another caller's prompt since): refreshed in place, all slots
+        model = lambda: eng._forward(self._sample, self._t, ctx, L, self.model_cond_frame)
+        G = None
+        if (unet.use_graph and self.ops is hip_ops and unet._ops_backend is hip_ops and self._x.is_cuda
+                and not self._capture_refused and not getattr(eng, "_graph_broken", False)):
+            key = ("slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+            G = eng.graph_get(key)
+            if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
+                G = self._capture(eng, key, model)
+        if G is None:
+            self._body(model)
+        else:
+            G["graph"].replay()
+
+    def _capture(self, eng, key, model):
+        """the step as one hipGraph (ddim.capture_step: warm-up, capture, the engine's graph cache).  Warm-up and capture run with every
+        slot idle -- the update kernel then writes nothing and the begin kernel only what the next step rewrites -- so admitted clips
+        are where they were afterwards; the counters are put back on the device, nothing is read back."""
+        saved = self._step.clone()
+        self._step.fill_(-1)
+        G = capture_step(eng, key, dict(x=self._x, owner=self), lambda: self._body(model))
+        self._step.copy_(saved)
+        if G is None:
+            self._capture_refused = True
+        return G
