@@ -567,6 +567,45 @@ int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
                            float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state, const float* x,
                            float* x_prev, float* pred_x0, void* stream);
 
+/* The captured step over slots with a SAMPLER per slot: DDIM and PLMS clips side by side in one step (slots.py, plms=True).  The
+ * buffers of the two slot entry points above, and per slot in device memory
+ *   state   int32 [slots][8]: words 0..2 = (phase, valid, newest) of the slot's NEXT step, words 4..6 = the same three of the step
+ *           IN FLIGHT, words 3 and 7 unused;
+ *   ring    fp32 [slots][3][C*F_pred*HW]: earlier e of the slot, (valid, newest) read as in seer_cfg_plms_step_dev;
+ *   x_prov  fp32 [slots][C*F_pred*HW]: the provisional latent of a PLMS clip's first step.
+ * phase 0 = a DDIM clip, for all its steps; 1 = a PLMS clip's first step, first evaluation; 2 = its second evaluation; 3 = every
+ * later PLMS step.  A clip of n schedule entries takes n calls of the pair with phase 0, n + 1 with PLMS.
+ *   seer_slot_plms_step_begin  seer_slot_step_begin, and for every slot s: the in-flight words of state[s] = its next words; in
+ *                              phase 2 the sample rows come from x_prov[s] instead of x[s] and t_out is t_table[s][max(index - 1,
+ *                              0)], the NEXT timestep (plms.py:145).  An idle slot is treated the same way (finite rows as long as
+ *                              x, x0_emb and x_prov are).
+ *   seer_slot_cfg_plms_step    for every slot s: index = step[s][1], (phase, valid, newest) = the in-flight words, e = the CFG
+ *                              combination with scale[s], coefficient row `index` of coef[s].
+ *                                phase 0: exactly seer_slot_cfg_ddim_step's update; step[s][0] = index - 1.
+ *                                phase 1: x_prov[s] = seer_cfg_plms_step's order 0 of x[s]; e goes into ring entry 0; the next words
+ *                                         become (2, 1, 0).  x_prev[s], pred_x0[s] and step[s][0] are NOT written.
+ *                                phase 2: order 1 with h1 = ring entry `newest`, from x[s] into x_prev[s] and pred_x0[s]; e is not
+ *                                         kept; step[s][0] = index - 1; the next phase becomes 3.
+ *                                phase 3: order valid + 1 (order 0 for valid = 0) with h1, h2, h3 = ring entries newest,
+ *                                         (newest+2)%3, (newest+1)%3; e goes into entry (newest+1)%3; step[s][0] = index - 1; the
+ *                                         next (valid, newest) = (min(valid+1, 3), (newest+1)%3).
+ *                              The arithmetic is the device code of seer_cfg_ddim_step / seer_cfg_plms_step, so an element gets
+ *                              their bits.  A ring entry the order does not use is never read (it may hold NaN).  index < 0 or
+ *                              >= nsched: nothing of that slot is written -- no latent, no ring entry, no word of step or state.
+ *                              A phase outside 0..3 is read as 0; in phase 3 a (valid, newest) outside 0..3 x 0..2 is read as
+ *                              (0, 2), in phase 2 a newest outside 0..2 as 0: no word found on the device indexes outside the ring.
+ *                              x_prev may be x; pred_x0 may be NULL; x_prov may not be x.
+ * No kernel reads and writes the same word: begin reads next words (and step[s][0]) and writes in-flight words (and step[s][1]),
+ * the update reads in-flight words and writes next words.  The host writes step[s][0] and the next words of state[s] -- (1, 0, 2)
+ * for PLMS, (0, 0, 2) for DDIM -- only when it fills slot s.  Every pointer must be 4-byte aligned and no more; SEER_EINVAL
+ * otherwise, for everything the two entry points above refuse, for a NULL state, ring or x_prov, and for x_prov == x. */
+int seer_slot_plms_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, const float* x_prov, int32_t slots,
+                              int32_t reps, int32_t C, int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table,
+                              int32_t nsched, int32_t* step, int32_t* state, float* sample, int64_t* t_out, void* stream);
+int seer_slot_cfg_plms_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                            const float* scale, const float* coef, int32_t nsched, int32_t* step, int32_t* state, float* ring,
+                            const float* x, float* x_prov, float* x_prev, float* pred_x0, void* stream);
+
 /* decoded image post-process of ddim_sample (utils/ddim_sampling_utils.py:41): clamp((x+1)/2, 0, 1) in place */
 int seer_clamp01(float* x, int64_t n, void* stream);
 

@@ -7,7 +7,11 @@ Every setting has its own model (the engine keeps ONE static context: settings t
 every turn) and is warmed with one request first (step captured; the device memory that takes is reported).  Then the settings ALTERNATE in one process,
 `--repeats` times; a pass is timed on the host clock from the first admission to a device synchronise after the last clip, so
 admissions (schedule upload, context and K|V refresh) are inside.  Prints markdown (profiles/slot_sampler.md keeps a run):
-clips/s and ms per replayed step = pass time / replays of the pass.  `python scripts/exp_slot_sampler.py [--requests 8] [--repeats 3]`"""
+clips/s and ms per replayed step = pass time / replays of the pass.  `python scripts/exp_slot_sampler.py [--requests 8] [--repeats 3]`
+
+`--method plms` measures the step that carries a sampler per slot instead (profiles/slot_plms.md keeps a run), at 4 slots: the
+plms=True step against the plms=False step with DDIM requests in both, and a PLMS queue against PLMSSampler one clip after another
+(S steps are S + 1 model evaluations either way: "replays" counts evaluations there)."""
 import argparse
 import statistics
 import sys
@@ -17,7 +21,7 @@ from pathlib import Path
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from seervideoldm_amd import DDIMSampler, SeerUNet, SlotSampler, synth  # noqa: E402
+from seervideoldm_amd import DDIMSampler, PLMSSampler, SeerUNet, SlotSampler, synth  # noqa: E402
 
 F1, FP, HL, S, SCALE = 2, 10, 32, 30, 7.5
 
@@ -26,6 +30,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--requests", type=int, default=8)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--method", choices=("ddim", "plms"), default="ddim")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     dev = torch.device("cuda")
@@ -46,8 +51,8 @@ def main():
                  x0_emb=(torch.randn((1, 4, F1, HL, HL), generator=g) * 0.18215 * 5).to(dev),
                  c=torch.randn((1, F1 + FP, 77, D), generator=g).to(dev), uc=uc, S=S, scale=SCALE, tag=k) for k in range(args.requests)]
 
-    def sequential(m):
-        smp = DDIMSampler(dev)
+    def sequential(m, cls=DDIMSampler):
+        smp = cls(dev)
 
         def run(rs):
             out = []
@@ -56,13 +61,15 @@ def main():
                                     cond_frames=F1, unconditional_guidance_scale=r["scale"], unconditional_conditioning=r["uc"], eta=0.,
                                     x_T=r["x_T"], is_3d=True)
                 out.append(lat)
-            return out, len(rs) * int(smp.ddim_coef.shape[0])
+            return out, len(rs) * (int(smp.ddim_coef.shape[0]) + (cls is PLMSSampler))
         return run
 
-    def slotted(m, slots):
-        smp = SlotSampler(m, slots, shape=(4, FP, HL, HL), cond_frames=F1, context_shape=(77, D), device=dev, model_cond_frame=F1)
+    def slotted(m, slots, plms=False, method="ddim"):
+        smp = SlotSampler(m, slots, shape=(4, FP, HL, HL), cond_frames=F1, context_shape=(77, D), device=dev, model_cond_frame=F1,
+                          plms=plms)
 
         def run(rs):
+            rs = [dict(r, method=method) for r in rs]
             replays, step = [0], smp.step
 
             def counted():
@@ -77,8 +84,14 @@ def main():
         return run
 
     settings, taken = {}, {}
-    for name, make in (("DDIMSampler, b = 1, one clip after another", sequential), ("SlotSampler, 2 slots", lambda m: slotted(m, 2)),
-                       ("SlotSampler, 4 slots", lambda m: slotted(m, 4))):
+    makers = (("DDIMSampler, b = 1, one clip after another", sequential), ("SlotSampler, 2 slots", lambda m: slotted(m, 2)),
+              ("SlotSampler, 4 slots", lambda m: slotted(m, 4)))
+    if args.method == "plms":
+        makers = (("PLMSSampler, b = 1, one clip after another", lambda m: sequential(m, PLMSSampler)),
+                  ("SlotSampler(plms=True), 4 slots, PLMS requests", lambda m: slotted(m, 4, True, "plms")),
+                  ("SlotSampler(plms=False), 4 slots, DDIM requests", lambda m: slotted(m, 4)),
+                  ("SlotSampler(plms=True), 4 slots, DDIM requests", lambda m: slotted(m, 4, True, "ddim")))
+    for name, make in makers:
         m = model()
         m.prepare()                                   # the packed weights are the model's, not the step's
         torch.cuda.synchronize()
@@ -100,7 +113,8 @@ def main():
             assert len(out) == len(reqs)
     base = statistics.median(times[next(iter(settings))])
     print(f"{torch.cuda.get_device_name(0)}; {args.requests} requests of S = {S} ({replays[next(iter(settings))] // args.requests} schedule "
-          f"entries), CFG {SCALE}, {F1} + {FP} frames, {HL}x{HL} latent, bf16, default mode, captured steps; {args.repeats} alternated repeats")
+          f"{'entries' if args.method == 'ddim' else 'entries + 1 = evaluations of a PLMS clip'}), CFG {SCALE}, {F1} + {FP} frames, "
+          f"{HL}x{HL} latent, bf16, default mode, captured steps; {args.repeats} alternated repeats")
     print()
     print("| setting | replays per pass | s per pass, every repeat | median clips/s | median ms per replay | clips/s against b = 1 |")
     print("|---|---|---|---|---|---|")

@@ -511,6 +511,89 @@ __global__ void slot_cfg_ddim_kernel(const float* __restrict__ eps, int slots, i
                 pred_x0, i);
 }
 
+// ---- the same step with a SAMPLER per slot: DDIM and PLMS clips side by side.  state int32 [slots][8] = (phase, valid, newest, -)
+// of the NEXT step, then the same three words of the step IN FLIGHT; ring fp32 [slots][3][C*Fp*HW] = the slot's earlier e, x_prov
+// [slots][C*Fp*HW] its provisional latent.  The begin kernel reads next words and writes in-flight words, the update kernel reads
+// in-flight words and writes next words: as above, no kernel reads and writes the same word.  Phases (plms.py:145-160):
+//   0  DDIM, for the whole clip           1  PLMS first step, first evaluation: x_prov = order 0 of x, e -> ring slot 0
+//   2  PLMS first step, second evaluation at x_prov and the NEXT timestep: order 1 on x      3  PLMS later steps: order valid + 1
+// A phase outside 0..3 is read as 0; in phase 3 a (valid, newest) outside 0..3 x 0..2 is read as (0, 2), as cfg_plms_dev_kernel does.
+enum { SLOT_STATE_WORDS = 8, SLOT_IN_FLIGHT = 4 };
+
+__global__ void slot_plms_assemble_kernel(const float* __restrict__ x0_emb, const float* __restrict__ x,
+                                          const float* __restrict__ x_prov, int slots, int reps, int C, int f1, int Fp, int HW,
+                                          const int* __restrict__ t_table, int nsched, int* __restrict__ step,
+                                          int* __restrict__ state, float* __restrict__ sample, int* __restrict__ t_out) {
+    const int F = f1 + Fp;
+    const int64_t per_slot = (int64_t)C * F * HW;
+    const int64_t per = (int64_t)slots * per_slot;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= per) return;
+    const int s = (int)(i / per_slot);
+    const int* next = state + SLOT_STATE_WORDS * s;
+    const int phase = next[0];
+    if (i == (int64_t)s * per_slot) {                    // the slot's first element: its counter, its state and its timesteps
+        int index = step[2 * s];
+        step[2 * s + 1] = index;
+        int* fly = state + SLOT_STATE_WORDS * s + SLOT_IN_FLIGHT;
+        fly[0] = phase, fly[1] = next[1], fly[2] = next[2];
+        if (phase == 2) --index;                         // the second evaluation runs at t_next = t_table[max(index - 1, 0)]
+        const int row = index < 0 ? 0 : (index < nsched ? index : nsched - 1);      // never outside the table
+        const int* t = t_table + 2 * ((int64_t)s * nsched + row);
+        for (int r = 0; r < reps; ++r) {
+            t_out[2 * (r * slots + s)] = t[0];
+            t_out[2 * (r * slots + s) + 1] = t[1];
+        }
+    }
+    const int hw = (int)(i % HW);
+    const int f = (int)((i / HW) % F);
+    const int64_t bc = i / ((int64_t)HW * F);            // s * C + c
+    const float* lat = phase == 2 ? x_prov : x;
+    const float v = f < f1 ? x0_emb[(bc * f1 + f) * HW + hw] : lat[(bc * Fp + (f - f1)) * HW + hw];
+    for (int r = 0; r < reps; ++r) sample[i + r * per] = v;
+}
+
+// CFG always on, eta = 0.  The arithmetic is cfg_eps_at with scale[s], then ddim_update (phase 0) or plms_update (phases 1 to 3)
+// with row step[s][1] of coef[s]: an element gets the bits of seer_cfg_ddim_step / seer_cfg_plms_step.  x may alias x_prev.
+__global__ void slot_cfg_plms_kernel(const float* __restrict__ eps, int slots, int C, int Ft, int cond_f, int HW,
+                                     const float* __restrict__ scale, const float* __restrict__ coef, int nsched,
+                                     int* __restrict__ step, int* __restrict__ state, float* ring, const float* x, float* x_prov,
+                                     float* x_prev, float* __restrict__ pred_x0) {
+    const int64_t per_slot = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)slots * per_slot) return;
+    const int s = (int)(i / per_slot);
+    const int index = step[2 * s + 1];
+    if (index < 0 || index >= nsched) return;            // idle (or a counter outside the table): nothing of this slot is written
+    const int* fly = state + SLOT_STATE_WORDS * s + SLOT_IN_FLIGHT;
+    int* next = state + SLOT_STATE_WORDS * s;
+    const bool first = i == (int64_t)s * per_slot;
+    const float* cf = coef + (int64_t)s * nsched * 4;
+    const float e = cfg_eps_at(eps, 1, slots, C, Ft, cond_f, HW, scale[s], i);
+    // entry k of the slot's ring, based so that [i] (an index over all slots) is this element: (3 s + k) per_slot + (i - s per_slot)
+    float* const rs = ring + 2 * (int64_t)s * per_slot;
+    const int phase = fly[0];
+    if (phase == 1) {
+        if (first) next[0] = 2, next[1] = 1, next[2] = 0;
+        plms_update(e, 0, nullptr, nullptr, nullptr, i, cf, index, x, x_prov, nullptr, rs);
+    } else if (phase == 2) {
+        int newest = fly[2];
+        if (newest < 0 || newest > 2) newest = 0;        // never index outside the ring
+        if (first) step[2 * s] = index - 1, next[0] = 3;
+        plms_update(e, 1, rs + newest * per_slot, nullptr, nullptr, i, cf, index, x, x_prev, pred_x0, nullptr);
+    } else if (phase == 3) {
+        int valid = fly[1], newest = fly[2];
+        if (valid < 0 || valid > 3 || newest < 0 || newest > 2) valid = 0, newest = 2;
+        const int slot = newest == 2 ? 0 : newest + 1;
+        if (first) step[2 * s] = index - 1, next[1] = valid < 3 ? valid + 1 : 3, next[2] = slot;
+        plms_update(e, valid == 0 ? 0 : valid + 1, rs + newest * per_slot, rs + (newest == 0 ? 2 : newest - 1) * per_slot,
+                    rs + slot * per_slot, i, cf, index, x, x_prev, pred_x0, rs + slot * per_slot);
+    } else {
+        if (first) step[2 * s] = index - 1;
+        ddim_update(e, cf, index, x, nullptr, x_prev, pred_x0, i);
+    }
+}
+
 // pointwise channel mix on NCHW fp32 (VAE post_quant_conv, 4 -> 4): y[n,co,p] = sum_ci W[co,ci] x[n,ci,p] + b[co]
 __global__ void conv1x1_nchw_kernel(const float* __restrict__ x, int N, int Cin, int Cout, int HW,
                                     const float* __restrict__ Wt, const float* __restrict__ bias, float* __restrict__ y) {
@@ -756,6 +839,37 @@ extern "C" int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t 
     if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
     hipLaunchKernelGGL(slot_cfg_ddim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total, cond_f,
                        HW, scale, coef, nsched, step, x, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_slot_plms_step_begin(const float* x0_emb, const float* x, const float* x_prov, int32_t slots, int32_t reps,
+                                         int32_t C, int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched,
+                                         int32_t* step, int32_t* state, float* sample, int64_t* t_out, void* stream) {
+    if (!x || !x_prov || !t_table || !step || !state || !sample || !t_out || slots < 1 || nsched < 1 || (reps != 1 && reps != 2) ||
+        C <= 0 || f1 < 0 || F_pred <= 0 || HW <= 0 || (f1 > 0 && !x0_emb) || x_prov == x)
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({x0_emb, x, x_prov, t_table, step, state, sample, t_out})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * ((int64_t)f1 + F_pred) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_plms_assemble_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x0_emb, x, x_prov, slots,
+                       reps, C, f1, F_pred, HW, reinterpret_cast<const int*>(t_table), nsched, step, state, sample,
+                       reinterpret_cast<int*>(t_out));
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_slot_cfg_plms_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                       const float* scale, const float* coef, int32_t nsched, int32_t* step, int32_t* state,
+                                       float* ring, const float* x, float* x_prov, float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !scale || !coef || !step || !state || !ring || !x || !x_prov || !x_prev || slots < 1 || nsched < 1 || C <= 0 ||
+        cond_f < 0 || cond_f >= F_total || HW <= 0 || x_prov == x)
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({eps, scale, coef, step, state, ring, x, x_prov, x_prev, pred_x0})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * ((int64_t)F_total - cond_f) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_cfg_plms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total, cond_f,
+                       HW, scale, coef, nsched, step, state, ring, x, x_prov, x_prev, pred_x0);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

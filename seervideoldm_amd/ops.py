@@ -1025,6 +1025,63 @@ def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, 
                                               _p(x), _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
 
 
+SLOT_STATE_WORDS = 8    # int32 words of a slot's sampler state: (phase, valid, newest, -) of the next step, then of the step in flight
+
+
+def _req_slot_plms(x: torch.Tensor, state: torch.Tensor, x_prov: torch.Tensor, ring: Optional[torch.Tensor] = None) -> None:
+    _req(state, torch.int32, "state"); _req(x_prov, torch.float32, "x_prov")
+    assert state.is_contiguous() and tuple(state.shape) == (x.shape[0], SLOT_STATE_WORDS)
+    assert x_prov.is_contiguous() and x_prov.shape == x.shape and x_prov.data_ptr() != x.data_ptr()
+    if ring is not None:
+        _req(ring, torch.float32, "ring")
+        assert ring.is_contiguous() and tuple(ring.shape) == (x.shape[0], 3, *x.shape[1:])
+
+
+def slot_plms_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, x_prov: torch.Tensor, t_table: torch.Tensor,
+                         step: torch.Tensor, state: torch.Tensor, reps: int, sample: torch.Tensor, t_out: torch.Tensor) -> None:
+    """slot_step_begin with a sampler per slot: state int32 [slots, 8] holds (phase, valid, newest) of the next step in words 0..2
+    and receives them in words 4..6; a slot in phase 2 (the second evaluation of a PLMS clip's first step) takes its rows from
+    x_prov and the next timestep of its table (include/seer_hip.h, seer_slot_plms_step_begin)"""
+    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    slots, Cc, Fp, h, w = x.shape
+    f1 = 0 if x0_emb is None else x0_emb.shape[2]
+    if x0_emb is not None:
+        _req(x0_emb, torch.float32, "x0_emb")
+        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
+    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * slots, Cc, f1 + Fp, h, w)
+    assert t_table.is_contiguous() and t_table.dim() == 2 and t_table.shape[0] == slots
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
+    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.is_contiguous() and t_out.numel() == reps * slots
+    _req_slot_plms(x, state, x_prov)
+    check(_lib.load().seer_slot_plms_step_begin(_p(x0_emb), _p(x), _p(x_prov), slots, reps, Cc, f1, Fp, h * w, _p(t_table),
+                                                t_table.shape[1], _p(step), _p(state), _p(sample), _p(t_out), _stream()),
+          "seer_slot_plms_step_begin")
+
+
+def slot_cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
+                       state: torch.Tensor, ring: torch.Tensor, x_prov: torch.Tensor, *, cond_f: int, x_prev: torch.Tensor,
+                       pred_x0: Optional[torch.Tensor]) -> None:
+    """slot_cfg_ddim_step with a sampler per slot: by the in-flight phase of state[s] slot s runs the DDIM update (0), the
+    provisional update of a PLMS clip's first step into x_prov[s] (1), the first step's final update (2) or a later PLMS step of
+    order valid + 1 over ring[s] (3), and writes the slot's next state words.  ring fp32 [slots, 3, *x.shape[1:]]; x_prev may be
+    x, x_prov may not (include/seer_hip.h, seer_slot_cfg_plms_step)"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    _req(scale, torch.float32, "scale")
+    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
+    slots, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
+    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
+    _req_slot_plms(x, state, x_prov, ring)
+    if pred_x0 is not None:
+        _req(pred_x0, torch.float32, "pred_x0")
+        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
+    check(_lib.load().seer_slot_cfg_plms_step(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+                                              _p(state), _p(ring), _p(x), _p(x_prov), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_slot_cfg_plms_step")
+
+
 def cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, order: int, *, cfg: bool, scale: float,
                   cond_f: int, history=(), x_prev: Optional[torch.Tensor] = None, pred_x0: Optional[torch.Tensor] = None,
                   e_out: Optional[torch.Tensor] = None, want_pred_x0=True, want_e=True):

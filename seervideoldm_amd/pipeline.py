@@ -55,10 +55,13 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 
 @torch.no_grad()
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
-                   latent_generator: Optional[torch.Generator] = None, max_steps: int = 64) -> Iterator[Tuple[object, torch.Tensor]]:
+                   latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
+                   plms: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
-    empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag).  The VAE encode
+    empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
+    optionally sampler = "ddim" (the default) or "plms").  `plms=True` builds the SlotSampler with plms=True, so that one captured
+    step serves requests of either sampler; a request naming "plms" without it is a ValueError.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -69,6 +72,9 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
 
     def admitted():
         for r in requests:
+            method = r.get("sampler", "ddim")
+            if method not in ("ddim", "plms") or (method == "plms" and not plms):
+                raise ValueError(f"sampler = {method!r}: 'ddim', or 'plms' in a queue started with plms=True")
             x0_image = r["x0_image"]
             if x0_image.shape[2] == 1:
                 x0_image = x0_image.expand(-1, -1, f1, -1, -1)
@@ -81,9 +87,9 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
             if not sampler:
                 _, c_l, _, h_l, w_l = x0_emb.shape
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
-                                           max_steps=max_steps, device=x0_emb.device))
+                                           max_steps=max_steps, device=x0_emb.device, plms=plms))
             yield dict(x_T=r["noise"], x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
-                       tag=r.get("tag"))
+                       tag=r.get("tag"), method=method)
 
     reqs = admitted()
     first = next(reqs, None)

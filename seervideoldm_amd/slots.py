@@ -1,4 +1,4 @@
-"""SlotSampler -- continuous batching of clips in ONE captured DDIM step.
+"""SlotSampler -- continuous batching of clips in ONE captured sampler step.
 
 The engine is bound by fixed costs, not by its matrix units: a second clip in the same step costs a fraction of a step
 ("SlotSampler").  DDIMSampler cannot use that: it has one schedule index and one guidance scale for the whole batch,
@@ -6,20 +6,27 @@ the scale is frozen into the captured graph, and a batch starts and ends togethe
 
     seer_slot_step_begin  ->  the UNet over [uc rows | c rows] of all slots  ->  seer_slot_cfg_ddim_step
 
+With `plms=True` the sampler is chosen per request: the step is seer_slot_plms_step_begin -> the UNet -> seer_slot_cfg_plms_step, and
+every slot also has a phase word, a 3-entry ring of earlier eps and a provisional latent in device memory.  A DDIM clip (phase 0)
+runs as above.  A PLMS clip of n schedule entries occupies its slot for n + 1 steps: its first step evaluates twice -- phase 1 at
+(x, t) writes the provisional latent and keeps e, phase 2 evaluates at (x_prov, t_next) and applies the mean of the two to x --
+and every later step (phase 3) is one evaluation of order 2, 3, 4 over the ring.  The kernels walk the phases themselves: the
+host writes a slot's phase, like its counter, only when it fills the slot.
+
 Each slot has its own schedule tables, step counter, guidance scale, prompt and conditioning frames, all in static device buffers, so
 the step is captured ONCE per (slots, clip shape, context shape, engine mode) -- neither the scale nor a schedule is part of the key --
 and a slot is refilled as soon as its clip is done.  The kernels count every slot's schedule down themselves; the host writes a
 slot's counter only when it fills the slot, and it knows from its own count when the slot finishes: step() reads nothing back.
 
 What a slot promises (INTEGRATION.md has the full list): under `SeerUNet(layout_invariant=True)` and scale != 1 the latent of a clip
-is bit for bit the one DDIMSampler.sample returns for that clip alone (batch 1, eta = 0, the same scale and start code), whatever the
-other slots hold and whenever it was admitted.  At scale == 1 the solo sampler evaluates once without CFG, a slot evaluates the pair
+is bit for bit the one DDIMSampler.sample -- PLMSSampler.sample for a PLMS clip -- returns for that clip alone (batch 1, eta = 0, the
+same scale and start code), whatever the other slots hold, whichever sampler they run and whenever it was admitted.  At scale == 1 the solo sampler evaluates once without CFG, a slot evaluates the pair
 and combines it with scale 1: not the same bits.  Without the invariant mode a slot is a row of a batch of `slots` clips: the same
 kernels, results within the layout tolerance.  The captured step and the launch-by-launch step give the same bits in either mode.
 The reference's per-step RNG draw (ddim_video.py:234) has no counterpart here: slots are deterministic, nothing consumes the device
 RNG stream.
 
-Out of scope: PLMS, eta > 0, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
+Out of scope: eta > 0, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
 """
 from __future__ import annotations
@@ -39,10 +46,12 @@ class SlotSampler:
     in front of it (x0_emb), context_shape = (L, D) of one frame's text context.  `model_cond_frame` is the `cond_frame` the UNet is
     called with -- DDIMSampler.sample's `cond_frames` keyword, which ddim_sample leaves at 0.  `ops` is the backend of the two
     step-boundary kernels (tests inject a torch restatement to run the host logic on the CPU); a `unet` that is no SeerUNet is called
-    as `unet(sample, t, context, cond_frame=...)`."""
+    as `unet(sample, t, context, cond_frame=...)`.  `plms=True` lets a request choose PLMS (submit's `method`): the step then runs
+    the two kernels that carry a sampler per slot, over three more static buffers, and is captured under a key of its own; with
+    False everything is as it was before that keyword existed."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
-                 model_cond_frame: int = 0):
+                 model_cond_frame: int = 0, plms: bool = False):
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -69,6 +78,11 @@ class SlotSampler:
         self._ttab = torch.zeros((n, self.max_steps), device=dev, dtype=torch.long)
         self._scale = torch.ones((n,), device=dev, dtype=f32)
         self._context = torch.zeros((2 * n, f1 + Fp, L, D), device=dev, dtype=f32)    # uc rows, then c rows
+        self.plms = bool(plms)
+        if self.plms:
+            self._state = torch.zeros((n, hip_ops.SLOT_STATE_WORDS), device=dev, dtype=torch.int32)    # phase 0, nothing in the ring
+            self._ring = torch.zeros((n, 3, C, Fp, h, w), device=dev, dtype=f32)
+            self._xprov = torch.zeros_like(self._x)
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
         self._tables: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -99,20 +113,25 @@ class SlotSampler:
         return t.reshape(want).to(device=self.device, dtype=torch.float32)
 
     @torch.no_grad()
-    def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0.) -> int:
+    def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim") -> int:
         """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
         [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
         empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
-        scale the guidance scale.  The clip's tables, scale, start index, latents and its two context rows are written into the
+        scale the guidance scale, method "ddim" or "plms" (a sampler built with plms=True only; the same schedule, and a clip of n
+        entries then occupies its slot for n + 1 steps).  The clip's tables, scale, start index, latents and its two context rows are written into the
         slot's part of the static buffers; the engine's 16-bit context and the cross-attention K|V of the text blocks are then
         refreshed at the next step through the engine's own context path -- over ALL slots, not only the one that changed (1 + 16
         small launches per admission; a per-slot refresh is not built).
         Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
-        constructor's, eta != 0 and a frame-sharded model."""
+        constructor's, eta != 0, a frame-sharded model, an unknown method and "plms" on a sampler built without it."""
         C, Fp, h, w = self.shape
         F, (L, D) = self.f1 + Fp, self.context_shape
         if eta != 0:
             raise ValueError(f"eta = {eta}: slots run the deterministic update only (eta = 0)")
+        if method not in ("ddim", "plms"):
+            raise ValueError(f"method = {method!r}: 'ddim' or 'plms'")
+        if method == "plms" and not self.plms:
+            raise ValueError("method = 'plms' needs a sampler built with plms=True")
         if getattr(self.unet, "_shard", None) is not None:
             raise ValueError("a frame-sharded model cannot run slots: detach it (parallel.attach) first")
         x_T = self._clip(x_T, (C, Fp, h, w), "x_T")
@@ -139,6 +158,12 @@ class SlotSampler:
         self._context[self.slots + s].copy_(c)
         self._step[s, :1].fill_(n - 1)               # the one host-written counter of the clip: the kernels count it down
         self._left[s] = n
+        if self.plms:
+            # the slot's sampler: phase 1 opens a PLMS clip, phase 0 is DDIM; (valid, newest) = (0, 2), an empty ring.  The first PLMS
+            # step is two steps of the slot
+            first = 1 if method == "plms" else 0
+            self._state[s, :3].copy_(torch.tensor([first, 0, 2], dtype=torch.int32))
+            self._left[s] = n + first
         return s
 
     # ---- the step ------------------------------------------------------------------------------------------------------------
@@ -158,10 +183,12 @@ class SlotSampler:
                 self._x[s].zero_()                   # an idle slot's rows stay finite (its counter is -1 by now: the kernels saw to it)
                 if self.f1:
                     self._x0[s].zero_()
+                if self.plms:
+                    self._xprov[s].zero_()
         return done
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
-        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=): fills free slots in request order (a
+        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=]): fills free slots in request order (a
         request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
         finishing order."""
         it, tags, more = iter(requests), {}, True
@@ -180,6 +207,12 @@ class SlotSampler:
                 yield tags.pop(s), lat
 
     def _body(self, model) -> None:
+        if self.plms:
+            self.ops.slot_plms_step_begin(self._x0, self._x, self._xprov, self._ttab, self._step, self._state, 2, self._sample, self._t)
+            eps = model()
+            self.ops.slot_cfg_plms_step(eps, self._x, self._scale, self._coef, self._step, self._state, self._ring, self._xprov,
+                                        cond_f=self.f1, x_prev=self._x, pred_x0=self._pred)
+            return
         self.ops.slot_step_begin(self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t)
         eps = model()
         self.ops.slot_cfg_ddim_step(eps, self._x, self._scale, self._coef, self._step, cond_f=self.f1, x_prev=self._x,
@@ -203,7 +236,7 @@ class SlotSampler:
         G = None
         if (unet.use_graph and self.ops is hip_ops and unet._ops_backend is hip_ops and self._x.is_cuda
                 and not self._capture_refused and not getattr(eng, "_graph_broken", False)):
-            key = ("slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+            key = ("slots-plms" if self.plms else "slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)
@@ -215,11 +248,14 @@ class SlotSampler:
     def _capture(self, eng, key, model):
         """the step as one hipGraph (ddim.capture_step: warm-up, capture, the engine's graph cache).  Warm-up and capture run with every
         slot idle -- the update kernel then writes nothing and the begin kernel only what the next step rewrites -- so admitted clips
-        are where they were afterwards; the counters are put back on the device, nothing is read back."""
+        are where they were afterwards; the counters (and the sampler state words) are put back on the device, nothing is read back."""
         saved = self._step.clone()
+        state = self._state.clone() if self.plms else None
         self._step.fill_(-1)
         G = capture_step(eng, key, dict(x=self._x, owner=self), lambda: self._body(model))
         self._step.copy_(saved)
+        if state is not None:
+            self._state.copy_(state)
         if G is None:
             self._capture_refused = True
         return G
