@@ -541,6 +541,47 @@ int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t 
                             const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x, float* x_prev,
                             float* pred_x0, void* stream);
 
+/* ---- seeded noise: the DDIM step with eta > 0 and no noise tensor ------------------------------------------------------------
+ * A counter-based generator, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), runs
+ * inside the kernels: a clip's noise is a pure function of (seed, schedule index, element), whatever batch row or slot holds it.
+ *   key      (seed & 0xffffffff, seed >> 32), one uint64 seed per clip; in device memory uint32 [rows][2] = (lo, hi), 4-byte aligned
+ *   counter  (block, index, stream, 0); block = e >> 2 with e the element's linear index inside the clip's own [C, F_pred, HW]
+ *            latent, and element e takes normal e & 3 of its block.  stream 0 = the start code (index 0), stream 1 = the noise of
+ *            the step at schedule index `index`, streams >= 2 reserved
+ *   uniform  u = float(2 * (w >> 9) + 1) * 2^-24, exact in fp32 and strictly inside (0, 1)
+ *   normals  Box-Muller on the word pairs (w0, w1), (w2, w3): r = sqrtf(-2 logf(u_a)), (s, c) = sincospif(2 u_b), n_even = r c,
+ *            n_odd = r s; |n| <= 5.7682
+ * and the noise term of the update is sigma * (temperature * n), two rounded fp32 products.
+ *   seer_philox_u32     diagnostic: out[4 (j - first_block) ..] = the four words of block j for first_block <= j < first_block +
+ *                       n_blocks <= 2^32.  Its `stream` is 64 bits wide -- low word = counter word 2, high word = counter word 3 -- so
+ *                       that any counter can be asked for; the samplers' streams have a zero high word.
+ *   seer_philox_normal  out[0 .. n-1] = the first n normals of (seed, stream, index), 0 < n < 2^31; nothing is written past
+ *                       out[n-1].  The start code of a seeded clip is stream 0, index 0.
+ *   seer_cfg_ddim_step_rng / seer_cfg_ddim_step_rng_dev
+ *                       seer_cfg_ddim_step / seer_cfg_ddim_step_dev with seeds (one pair per batch row) and temperature in the place
+ *                       of noise: where row `index` of coef has sigma != 0, element e of row bi gets stream-1 noise of seeds[bi] at
+ *                       that index -- the bits of seer_cfg_ddim_step given noise = temperature * seer_philox_normal(seed, 1, index);
+ *                       where sigma == 0 nothing is drawn and the bits are seer_cfg_ddim_step's with noise = NULL.  _dev: index =
+ *                       step[1], then step[0] = index - 1; an index < 0 writes no latent.  x_prev may be x; pred_x0 may be NULL.
+ *   seer_slot_cfg_ddim_step_rng
+ *                       seer_slot_cfg_ddim_step with seeds uint32 [slots][2] and temperature fp32 [slots] in device memory; sigma is
+ *                       column 2 of the slot's own coef rows.  An idle slot (index < 0 or >= nsched) writes nothing.  Its first
+ *                       kernel is seer_slot_step_begin, unchanged.
+ * SEER_EINVAL as in the entry points they restate (NULL required pointers, non-positive extents, cond_f >= F_total, a pointer that
+ * is not 4-byte aligned), and for a clip of C * F_pred * HW >= 2^31 elements. */
+int seer_philox_u32(uint64_t seed, uint64_t stream, uint32_t index, uint64_t first_block, int64_t n_blocks, uint32_t* out,
+                    void* hip_stream);
+int seer_philox_normal(uint64_t seed, uint32_t stream, uint32_t index, int64_t n, float* out, void* hip_stream);
+int seer_cfg_ddim_step_rng(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                           float scale, const float* coef, int32_t index, const float* x, const uint32_t* seeds, float temperature,
+                           float* x_prev, float* pred_x0, void* stream);
+int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                               float scale, const float* coef, int32_t* step, const float* x, const uint32_t* seeds,
+                               float temperature, float* x_prev, float* pred_x0, void* stream);
+int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
+                                const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0, void* stream);
+
 /* CFG combine + PLMS update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:199-236; eta = 0, so no noise term), fp32.
  * e is the CFG-combined eps of this evaluation as in seer_cfg_ddim_step (frames >= cond_f only); h1, h2, h3 are earlier e,
  * newest first, each [b, C, F_pred, HW].  e' by `order`:

@@ -114,6 +114,7 @@ class AttnBwdDesc(C.Structure):
 
 
 _vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
+_u32, _u64 = C.c_uint32, C.c_uint64
 
 # name -> argtypes; every symbol include/seer_hip.h declares (tests/test_abi.py checks the list against the header)
 SIGNATURES = {
@@ -163,6 +164,11 @@ SIGNATURES = {
     "seer_cfg_ddim_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_step_begin": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_cfg_ddim_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_philox_u32": ([_u64, _u64, _u32, _u64, _i64, _vp, _vp], C.c_int),
+    "seer_philox_normal": ([_u64, _u32, _u32, _i64, _vp, _vp], C.c_int),
+    "seer_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_ddim_step_rng_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
+    "seer_slot_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_plms_step_begin": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_cfg_plms_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                                 C.c_int),

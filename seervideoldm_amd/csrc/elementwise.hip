@@ -1,6 +1,7 @@
 // Small / boundary kernels of the Seer hot path on gfx950: rotary embedding, timestep embedding, small-M linear,
 // conv_in / conv_out (layout change fused), casts, CFG + DDIM / PLMS update.
 #include "seer_common.h"
+#include "seer_philox.h"
 #include <atomic>
 #include <cstdint>
 #include <initializer_list>
@@ -511,6 +512,61 @@ __global__ void slot_cfg_ddim_kernel(const float* __restrict__ eps, int slots, i
                 pred_x0, i);
 }
 
+// ---- the three forms of the DDIM step above with SEEDED noise (eta > 0): the noise of element el of a clip at schedule index
+// `index` is normal number el of Philox stream 1 of the clip's seed (seer_philox.h), drawn here instead of read from a tensor, so a
+// captured step has nothing to draw between its launches and a clip's noise does not depend on its batch row or slot.  The update
+// is ddim_update's expression with n in the place of noise[i]: sigma * (temperature * n), two rounded fp32 products, then the add.
+// sigma == 0 (uniform over a clip's threads) draws nothing and gives ddim_update's bits with noise == nullptr.
+__device__ __forceinline__ void ddim_update_rng(float e, const float* __restrict__ coef, int index, const float* x,
+                                                const uint32_t* __restrict__ seed, float temperature, uint32_t el, float* x_prev,
+                                                float* __restrict__ pred_x0, int64_t i) {
+    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], sigma = coef[4 * index + 2], s1m = coef[4 * index + 3];
+    const float xv = x[i];
+    const float x0 = (xv - s1m * e) / sqrtf(a_t);
+    const float dir = sqrtf(1.f - a_prev - sigma * sigma) * e;
+    float nz = 0.f;
+    if (sigma != 0.f) {
+        const float tn = temperature * seer_philox::normal_at(seed[0], seed[1], seer_philox::STREAM_STEP, (uint32_t)index, el);
+        nz = sigma * tn;
+    }
+    x_prev[i] = sqrtf(a_prev) * x0 + dir + nz;
+    if (pred_x0) pred_x0[i] = x0;
+}
+
+// seeds uint32 [b][2] (lo, hi): one pair per batch row.  step == nullptr: the host's `index`; else index = step[1] and one thread
+// writes step[0] = index - 1, as cfg_ddim_dev_kernel.  x may alias x_prev.
+__global__ void cfg_ddim_rng_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
+                                    const float* __restrict__ coef, int index, int* __restrict__ step, const float* x,
+                                    const uint32_t* __restrict__ seeds, float temperature, float* x_prev,
+                                    float* __restrict__ pred_x0) {
+    const int64_t per_clip = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step) {
+        index = step[1];
+        if (i == 0) step[0] = index - 1;
+    }
+    if (index < 0 || i >= (int64_t)b * per_clip) return;     // (a counter that ran past the schedule's end reads no coefficient row)
+    const int64_t bi = i / per_clip;
+    ddim_update_rng(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), coef, index, x, seeds + 2 * bi, temperature,
+                    (uint32_t)(i - bi * per_clip), x_prev, pred_x0, i);
+}
+
+// slot_cfg_ddim_kernel with a seed pair and a temperature per slot; sigma is column 2 of the slot's own coef rows
+__global__ void slot_cfg_ddim_rng_kernel(const float* __restrict__ eps, int slots, int C, int Ft, int cond_f, int HW,
+                                         const float* __restrict__ scale, const float* __restrict__ coef, int nsched,
+                                         int* __restrict__ step, const float* x, const uint32_t* __restrict__ seeds,
+                                         const float* __restrict__ temperature, float* x_prev, float* __restrict__ pred_x0) {
+    const int64_t per_slot = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)slots * per_slot) return;
+    const int s = (int)(i / per_slot);
+    const int index = step[2 * s + 1];
+    if (index < 0 || index >= nsched) return;            // idle (or a counter outside the table): nothing of this slot is written
+    if (i == (int64_t)s * per_slot) step[2 * s] = index - 1;
+    ddim_update_rng(cfg_eps_at(eps, 1, slots, C, Ft, cond_f, HW, scale[s], i), coef + (int64_t)s * nsched * 4, index, x, seeds + 2 * s,
+                    temperature[s], (uint32_t)(i - (int64_t)s * per_slot), x_prev, pred_x0, i);
+}
+
 // ---- the same step with a SAMPLER per slot: DDIM and PLMS clips side by side.  state int32 [slots][8] = (phase, valid, newest, -)
 // of the NEXT step, then the same three words of the step IN FLIGHT; ring fp32 [slots][3][C*Fp*HW] = the slot's earlier e, x_prov
 // [slots][C*Fp*HW] its provisional latent.  The begin kernel reads next words and writes in-flight words, the update kernel reads
@@ -839,6 +895,56 @@ extern "C" int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t 
     if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
     hipLaunchKernelGGL(slot_cfg_ddim_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total, cond_f,
                        HW, scale, coef, nsched, step, x, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+// the *_rng entry points: a clip's element index is a 32-bit Philox counter word times four, so a clip stays below 2^31 elements
+static inline bool rng_clip_ok(int32_t C, int32_t F_total, int32_t cond_f, int32_t HW) {
+    return C > 0 && HW > 0 && cond_f >= 0 && cond_f < F_total && (int64_t)C * ((int64_t)F_total - cond_f) * HW < ((int64_t)1 << 31);
+}
+
+static int launch_cfg_ddim_rng(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                               float scale, const float* coef, int32_t index, int32_t* step, const float* x, const uint32_t* seeds,
+                               float temperature, float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !coef || !x || !seeds || !x_prev || b <= 0 || !rng_clip_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
+    if (!slot_ptrs_ok({eps, coef, step, x, seeds, x_prev, pred_x0})) return SEER_EINVAL;
+    const int64_t n = (int64_t)b * C * ((int64_t)F_total - cond_f) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(cfg_ddim_rng_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, cfg, b, C, F_total, cond_f,
+                       HW, scale, coef, index, step, x, seeds, temperature, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_cfg_ddim_step_rng(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                      int32_t HW, float scale, const float* coef, int32_t index, const float* x,
+                                      const uint32_t* seeds, float temperature, float* x_prev, float* pred_x0, void* stream) {
+    if (index < 0) return SEER_EINVAL;
+    return launch_cfg_ddim_rng(eps, cfg, b, C, F_total, cond_f, HW, scale, coef, index, nullptr, x, seeds, temperature, x_prev, pred_x0,
+                               stream);
+}
+
+extern "C" int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                          int32_t HW, float scale, const float* coef, int32_t* step, const float* x,
+                                          const uint32_t* seeds, float temperature, float* x_prev, float* pred_x0, void* stream) {
+    if (!step) return SEER_EINVAL;
+    return launch_cfg_ddim_rng(eps, cfg, b, C, F_total, cond_f, HW, scale, coef, 0, step, x, seeds, temperature, x_prev, pred_x0,
+                               stream);
+}
+
+extern "C" int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                           const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
+                                           const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0,
+                                           void* stream) {
+    if (!eps || !scale || !coef || !step || !x || !seeds || !temperature || !x_prev || slots < 1 || nsched < 1 ||
+        !rng_clip_ok(C, F_total, cond_f, HW))
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({eps, scale, coef, step, x, seeds, temperature, x_prev, pred_x0})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * ((int64_t)F_total - cond_f) * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_cfg_ddim_rng_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total,
+                       cond_f, HW, scale, coef, nsched, step, x, seeds, temperature, x_prev, pred_x0);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

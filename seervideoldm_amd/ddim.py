@@ -10,6 +10,11 @@ Same names, keyword arguments and return values.  Differences that are not seman
   * the batched-CFG inputs [uc, c] are concatenated once per `sample()` call, not once per step.
 The reference draws `torch.randn(x.shape)` every step even when sigma == 0 (ddim_video.py:234); we keep the draw so a seeded
 multi-sample run consumes the device RNG stream identically.
+
+`sample(..., seed=)` (an int, or one int per batch row) replaces every draw by a counter-based generator inside the kernels (DESIGN.md,
+"Seeded noise"): the start code is seer_philox_normal of the row's seed, the noise of a step is drawn by seer_cfg_ddim_step_rng from
+(seed, schedule index, element).  Nothing comes from torch's generator, the captured step is taken for eta > 0 too, and a row's
+noise does not depend on the batch it is in.
 """
 from __future__ import annotations
 
@@ -90,6 +95,9 @@ class DDIMSampler(object):
         if conditioning is not None and not isinstance(conditioning, dict):
             if conditioning.shape[0] != batch_size:
                 print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        seeds = _row_seeds(kwargs.get("seed"), batch_size)
+        if seeds is not None and getattr(unet, "_shard", None) is not None:
+            raise ValueError("seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)")
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         if is_3d:
             C, Fr, H, W = shape
@@ -100,14 +108,25 @@ class DDIMSampler(object):
                                   img_callback=img_callback, cond_frames=cond_frames, temperature=temperature,
                                   noise_dropout=noise_dropout, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds)
 
     @torch.no_grad()
     def ddim_sampling(self, unet, cond, shape, is_3d, x0_emb=None, cond_frames=0, x_T=None, callback=None,
                       img_callback=None, log_every_t=100, temperature=1., noise_dropout=0.,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, **kwargs):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, seeds=None, **kwargs):
+        """`seeds`: None, or one uint64 per batch row (sample's `seed`): the start code (when x_T is None) and the noise of every step
+        then come from the rows' Philox streams, nothing from torch's generator"""
         device = self.device
         b = shape[0]
+        if seeds is not None:
+            seeds = list(seeds)
+            if len(seeds) != b:
+                raise ValueError(f"seeds: {len(seeds)} for a batch of {b}")
+            if x_T is None:
+                x_T = torch.empty(shape, device=device, dtype=torch.float32)
+                for row, s in zip(x_T, seeds):           # a row's start code: stream 0 of its own seed
+                    ops.philox_normal(s, ops.PHILOX_STREAM_START, 0, row.numel(), out=row)
+            seeds = ops.seed_words(seeds).to(device)
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
         # one clip sharded over several ranks (parallel.attach): every rank must denoise the SAME latent.  The start code,
         # the conditioning latents (a per-rank posterior sample) and any per-step noise come from rank 0.
@@ -128,7 +147,7 @@ class DDIMSampler(object):
                                                   cond_frames=cond_frames, temperature=temperature,
                                                   noise_dropout=noise_dropout,
                                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                                  unconditional_conditioning=unconditional_conditioning)
+                                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds)
                 if callback:
                     callback(i)
                 if img_callback:
@@ -144,8 +163,9 @@ class DDIMSampler(object):
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                       use_original_steps=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      null_cond_prob=None):
-        """ddim_video.py:183-238."""
+                      null_cond_prob=None, seeds=None):
+        """ddim_video.py:183-238.  `seeds` (int32 [b, 2] on x's device, ops.seed_words; not in the reference): the step's noise is
+        drawn inside its last kernel from the rows' seeds and `index`, and torch's generator is left alone."""
         if use_original_steps or noise_dropout > 0. or repeat_noise:
             raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
         x = x.to(torch.float32).contiguous()
@@ -154,13 +174,17 @@ class DDIMSampler(object):
         # the whole step -- input assembly, CFG-batched UNet, CFG combine, DDIM update -- as ONE replayed hipGraph when the model
         # replays graphs anyway (unet.use_graph) and the step is the one ddim_sample drives: batched CFG or none, eta = 0, and
         # t = the schedule's own timestep of `index` (recognised by its address: a view of the device timestep table)
-        if (sigma == 0. and getattr(unet, "use_graph", False) and x.is_cuda and (uc is None or scale == 1. or uc.shape[2] == c.shape[2])
+        if ((sigma == 0. or seeds is not None) and getattr(unet, "use_graph", False) and x.is_cuda and (uc is None or scale == 1. or uc.shape[2] == c.shape[2])
                 and torch.is_tensor(t) and t.dtype == torch.long and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
             plain = uc is None or scale == 1.
-            done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale)
+            done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale,
+                                    seeds=seeds, temperature=temperature)
             if done is not None:
                 return done
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        if seeds is not None:
+            return ops.cfg_ddim_step_rng(eps.float().contiguous(), x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale, cond_f=cond_f,
+                                         temperature=temperature)
         noise = None
         if sigma != 0. or self.consume_rng_when_deterministic:
             noise = torch.randn(x.shape, device=x.device) * temperature
@@ -199,22 +223,28 @@ class DDIMSampler(object):
         return eps, cfg, cond_f
 
     # ---- the captured step -----------------------------------------------------------------------------------------
-    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale):
+    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1.):
         """One p_sample_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_step_dev):
         no torch kernel between two UNet evaluations except the reference's per-step RNG draw, no host-written scalars -- the
         schedule index lives in device memory and the captured step counts it down itself.  Returns None when this step cannot
-        take the path (sharded model, capture refused): the caller then runs the launches one by one."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale)
+        take the path (sharded model, capture refused): the caller then runs the launches one by one.  With `seeds` the last kernel
+        is seer_cfg_ddim_step_rng_dev and the step draws nothing, at any eta."""
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, rng=None if seeds is None else float(temperature))
         if G is None:
             return None
+        if seeds is not None:
+            k = (seeds.data_ptr(), seeds._version)
+            if G["seeds_key"] != k or G["seeds_ref"] is not seeds:
+                G["seeds"].copy_(seeds)
+                G["seeds_key"], G["seeds_ref"] = k, seeds
         if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
             G["x"].copy_(x)
         if G["expect"] != index:
             G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
-        return self._replay_step(G, x, index)
+        return self._replay_step(G, x, index, draw=seeds is None)
 
-    def _replay_step(self, G, x, index):
-        if self.consume_rng_when_deterministic:
+    def _replay_step(self, G, x, index, draw=True):
+        if draw and self.consume_rng_when_deterministic:
             torch.randn(x.shape, device=x.device)   # ddim_video.py:234 draws every step, also at sigma = 0: keep the RNG stream
         G["graph"].replay()
         G["expect"] = index - 1
@@ -233,9 +263,11 @@ class DDIMSampler(object):
         ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], cfg=cfg, scale=scale, cond_f=cond_f, x_prev=G["x"],
                               pred_x0=G["pred"])
 
-    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale):
+    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, rng=None):
         """the captured step of this shape / CFG / scale (captured on first use) with its read-by-address inputs refreshed; None
-        when the step cannot be captured"""
+        when the step cannot be captured.  rng = the temperature of a seeded step (None: the sampler's own step): a kind of its own in
+        the key -- "step-rng" -- with the temperature, which like the guidance scale is an argument of the last kernel and frozen into
+        the capture; the seeds live in a static buffer and are no part of the key."""
         from .unet import SeerUNet
         if not isinstance(unet, SeerUNet) or unet._shard is not None or unet._ops_backend is not ops \
                 or unet.config.center_input_sample or getattr(self, "_step_graph_broken", False):
@@ -264,9 +296,11 @@ class DDIMSampler(object):
         ctx, L = eng._context(context)          # new prompt: the static context / K|V buffers are refreshed in place
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
         key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv)
+        if rng is not None:
+            key = ("step-rng", *key[1:], float(rng))
         G = eng.graph_get(key)
         if G is None:
-            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L)
+            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L, rng)
             if G is None:
                 return None
         # inputs that are read by address: refreshed in place when the caller brings new ones (once per sample / per schedule)
@@ -288,7 +322,7 @@ class DDIMSampler(object):
             G["expect"] = None
         return G
 
-    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L):
+    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L, rng=None):
         dev = x.device
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
@@ -299,7 +333,8 @@ class DDIMSampler(object):
                  t=torch.empty((reps * b,), device=dev, dtype=torch.long), step=torch.zeros((2,), device=dev, dtype=torch.int32),
                  coef=torch.zeros((nsched, 4), device=dev, dtype=torch.float32),
                  ttab=torch.zeros((nsched,), device=dev, dtype=torch.long), sched_key=None, sched_ref=(None, None), x0_ref=None,
-                 expect=None, **self._graph_buffers(x))
+                 expect=None, **(self._graph_buffers(x) if rng is None else
+                                 dict(seeds=torch.zeros((b, 2), device=dev, dtype=torch.int32), seeds_key=None, seeds_ref=None)))
         G["coef"][:, 0] = 1.0                        # a_t = 1 in the unused rows: the warm-up below must stay finite
         G["x"].copy_(x)
         if x0_emb is not None:
@@ -308,7 +343,11 @@ class DDIMSampler(object):
         def body():
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
-            self._graph_update(G, eps, cfg, scale, f1)
+            if rng is None:
+                self._graph_update(G, eps, cfg, scale, f1)
+            else:
+                ops.cfg_ddim_step_rng_dev(eps, G["x"], G["coef"], G["step"], G["seeds"], cfg=cfg, scale=scale, cond_f=f1,
+                                          temperature=rng, x_prev=G["x"], pred_x0=G["pred"])
         if capture_step(eng, key, G, body) is None:
             self._step_graph_broken = True
             return None
@@ -332,6 +371,23 @@ def capture_step(eng, key, G, body):
     G["graph"] = g
     eng.graph_put(key, G)
     return G
+
+
+def _row_seeds(seed, batch_size: int):
+    """sample()'s `seed` -> one uint64 per batch row, or None: an int s gives row i the seed s + i, a sequence is taken as it is"""
+    if seed is None:
+        return None
+    if isinstance(seed, (int, np.integer)):
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed: {seed!r}: a seed is an unsigned 64-bit integer")
+        seeds = [(int(seed) + i) & 0xffffffffffffffff for i in range(int(batch_size))]
+    else:
+        seeds = [int(s) for s in seed]
+        if len(seeds) != int(batch_size):
+            raise ValueError(f"seed: {len(seeds)} seeds for batch_size = {batch_size}")
+    if any(not 0 <= s < 1 << 64 for s in seeds):
+        raise ValueError(f"seed: {seed!r}: a seed is an unsigned 64-bit integer")
+    return seeds
 
 
 def _from_rank0(unet, t: torch.Tensor) -> torch.Tensor:

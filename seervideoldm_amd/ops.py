@@ -1025,6 +1025,103 @@ def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, 
                                               _p(x), _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
 
 
+# ---- seeded noise (include/seer_hip.h, "seeded noise"): Philox4x32-10 inside the kernels ------------------------------------------
+PHILOX_STREAM_START, PHILOX_STREAM_STEP = 0, 1      # stream 0 = the start code (index 0), stream 1 = the noise of a step
+
+
+def seed_words(seeds) -> torch.Tensor:
+    """uint64 seeds -> the int32 [n, 2] (lo, hi) words the kernels read (a CPU tensor: the caller copies it into its buffer)"""
+    words = []
+    for s in seeds:
+        s = int(s)
+        if not 0 <= s < 1 << 64:
+            raise ValueError(f"seed {s}: a seed is an unsigned 64-bit integer")
+        words.append([w - (1 << 32) if w >= 1 << 31 else w for w in (s & 0xffffffff, s >> 32)])
+    return torch.tensor(words, dtype=torch.int32).reshape(-1, 2)
+
+
+def philox_u32(seed: int, stream: int, index: int, first_block: int, n_blocks: int, device) -> torch.Tensor:
+    """diagnostic: the raw words of blocks first_block .. first_block + n_blocks - 1 as int32 [n_blocks, 4] (bit patterns); the low
+    word of `stream` is counter word 2, its high word counter word 3"""
+    out = torch.empty((int(n_blocks), 4), device=device, dtype=torch.int32)
+    check(_lib.load().seer_philox_u32(int(seed), int(stream), int(index), int(first_block), int(n_blocks), _p(out), _stream()),
+          "seer_philox_u32")
+    return out
+
+
+def philox_normal(seed: int, stream: int, index: int, n: int, device=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the first n normals of (seed, stream, index), fp32 [n]; into the first n elements of `out` (contiguous fp32) when given"""
+    if out is None:
+        out = torch.empty((int(n),), device=device, dtype=torch.float32)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.numel() >= n
+    check(_lib.load().seer_philox_normal(int(seed), int(stream), int(index), int(n), _p(out), _stream()), "seer_philox_normal")
+    return out
+
+
+def _req_seeds(seeds: torch.Tensor, rows: int) -> None:
+    _req(seeds, torch.int32, "seeds")
+    assert seeds.is_contiguous() and tuple(seeds.shape) == (rows, 2)
+
+
+def cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, seeds: torch.Tensor, *, cfg: bool,
+                      scale: float, cond_f: int, temperature: float = 1., x_prev: Optional[torch.Tensor] = None,
+                      want_pred_x0=True):
+    """cfg_ddim_step with seeded noise: seeds int32 [b, 2] (seed_words) and temperature in the place of the noise tensor; row bi gets
+    sigma * (temperature * normal e of (seeds[bi], stream 1, index)).  x_prev may be x.  -> (x_prev, pred_x0)"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
+    assert eps.is_contiguous() and x.is_contiguous()
+    b, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
+    _req_seeds(seeds, b)
+    if x_prev is None:
+        x_prev = torch.empty_like(x)
+    assert x_prev.is_contiguous() and x_prev.shape == x.shape and x_prev.dtype == torch.float32
+    pred = torch.empty_like(x) if want_pred_x0 else None
+    check(_lib.load().seer_cfg_ddim_step_rng(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), int(index), _p(x),
+                                             _p(seeds), float(temperature), _p(x_prev), _p(pred), _stream()), "seer_cfg_ddim_step_rng")
+    return x_prev, pred
+
+
+def cfg_ddim_step_rng_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, seeds: torch.Tensor, *,
+                          cfg: bool, scale: float, cond_f: int, temperature: float, x_prev: torch.Tensor,
+                          pred_x0: Optional[torch.Tensor]) -> None:
+    """last kernel of a captured seeded step: cfg_ddim_step_rng with index = step[1], then step[0] = index - 1; x_prev may be x"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
+    b, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b) and step.numel() >= 2
+    _req_seeds(seeds, b)
+    check(_lib.load().seer_cfg_ddim_step_rng_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), _p(step), _p(x),
+                                                 _p(seeds), float(temperature), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_cfg_ddim_step_rng_dev")
+
+
+def slot_cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
+                           seeds: torch.Tensor, temperature: torch.Tensor, *, cond_f: int, x_prev: torch.Tensor,
+                           pred_x0: Optional[torch.Tensor]) -> None:
+    """slot_cfg_ddim_step with seeded noise: seeds int32 [slots, 2] and temperature fp32 [slots] in device memory; a slot whose coef
+    row has sigma == 0 runs the deterministic update (include/seer_hip.h, seer_slot_cfg_ddim_step_rng)"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    _req(scale, torch.float32, "scale"); _req(temperature, torch.float32, "temperature")
+    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
+    slots, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
+    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
+    assert temperature.is_contiguous() and temperature.numel() == slots
+    _req_seeds(seeds, slots)
+    if pred_x0 is not None:
+        _req(pred_x0, torch.float32, "pred_x0")
+        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
+    check(_lib.load().seer_slot_cfg_ddim_step_rng(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+                                                  _p(x), _p(seeds), _p(temperature), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_slot_cfg_ddim_step_rng")
+
+
 SLOT_STATE_WORDS = 8    # int32 words of a slot's sampler state: (phase, valid, newest, -) of the next step, then of the step in flight
 
 

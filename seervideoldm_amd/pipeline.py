@@ -56,12 +56,14 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 @torch.no_grad()
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
                    latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
-                   plms: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
+                   plms: bool = False, stochastic: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
     empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
     optionally sampler = "ddim" (the default) or "plms").  `plms=True` builds the SlotSampler with plms=True, so that one captured
-    step serves requests of either sampler; a request naming "plms" without it is a ValueError.  The VAE encode
+    step serves requests of either sampler; a request naming "plms" without it is a ValueError.  `stochastic=True` builds it with
+    stochastic=True: a request may then carry seed, eta and temperature (SlotSampler.submit), and `noise` is optional when it has a
+    seed -- the start code is then drawn from the seed; in a queue started without it those keys are a ValueError.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -87,9 +89,14 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
             if not sampler:
                 _, c_l, _, h_l, w_l = x0_emb.shape
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
-                                           max_steps=max_steps, device=x0_emb.device, plms=plms))
-            yield dict(x_T=r["noise"], x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
-                       tag=r.get("tag"), method=method)
+                                           max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic))
+            seeded = {k: r[k] for k in ("seed", "eta", "temperature") if k in r}
+            if seeded and not stochastic:
+                raise ValueError(f"{sorted(seeded)}: a request carries these only in a queue started with stochastic=True")
+            if r.get("noise") is None and seeded.get("seed") is None:
+                raise ValueError("a request needs `noise` (its start code) or, in a queue started with stochastic=True, a `seed`")
+            yield dict(x_T=r.get("noise"), x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
+                       tag=r.get("tag"), method=method, **seeded)
 
     reqs = admitted()
     first = next(reqs, None)

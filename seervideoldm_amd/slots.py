@@ -23,10 +23,15 @@ is bit for bit the one DDIMSampler.sample -- PLMSSampler.sample for a PLMS clip 
 same scale and start code), whatever the other slots hold, whichever sampler they run and whenever it was admitted.  At scale == 1 the solo sampler evaluates once without CFG, a slot evaluates the pair
 and combines it with scale 1: not the same bits.  Without the invariant mode a slot is a row of a batch of `slots` clips: the same
 kernels, results within the layout tolerance.  The captured step and the launch-by-launch step give the same bits in either mode.
-The reference's per-step RNG draw (ddim_video.py:234) has no counterpart here: slots are deterministic, nothing consumes the device
-RNG stream.
+The reference's per-step RNG draw (ddim_video.py:234) has no counterpart here: nothing consumes the device RNG stream.
 
-Out of scope: eta > 0, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
+With `stochastic=True` a request may carry eta > 0, a seed and a temperature: the step's last kernel is seer_slot_cfg_ddim_step_rng,
+which draws a slot's noise itself from (the slot's seed, its schedule index, the element) -- a counter-based generator (DESIGN.md,
+"Seeded noise"), so nothing is drawn between launches, nothing is frozen into the graph and the noise of a clip does not depend on
+its slot or its neighbours.  Each slot also has a seed pair and a temperature in device memory, and its coefficient rows carry the
+sigma of its own eta.  The promise above then holds for a seeded clip against DDIMSampler.sample(..., eta=, seed=, x_T=None).
+
+Out of scope: PLMS with noise, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
 """
 from __future__ import annotations
@@ -48,10 +53,12 @@ class SlotSampler:
     step-boundary kernels (tests inject a torch restatement to run the host logic on the CPU); a `unet` that is no SeerUNet is called
     as `unet(sample, t, context, cond_frame=...)`.  `plms=True` lets a request choose PLMS (submit's `method`): the step then runs
     the two kernels that carry a sampler per slot, over three more static buffers, and is captured under a key of its own; with
-    False everything is as it was before that keyword existed."""
+    False everything is as it was before that keyword existed.  `stochastic=True` lets a request carry eta, seed and temperature
+    (submit): the step's last kernel then draws the noise per slot, over two more static buffers, again under a key of its own; it
+    excludes plms=True (PLMS has no noise term)."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
-                 model_cond_frame: int = 0, plms: bool = False):
+                 model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False):
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -59,6 +66,10 @@ class SlotSampler:
             raise ValueError(f"slots = {slots}: 1 .. {MAX_SLOTS} (the [uc | c] rows of all slots go through the 8-row time embedding)")
         if min(C, Fp, h, w, L, D) < 1 or f1 < 0 or int(max_steps) < 1:
             raise ValueError(f"shape {tuple(shape)}, cond_frames {cond_frames}, context_shape {tuple(context_shape)}, max_steps {max_steps}")
+        if stochastic and plms:
+            raise ValueError("stochastic=True with plms=True: PLMS is deterministic only, build one sampler for each")
+        if stochastic and C * Fp * h * w >= 1 << 31:
+            raise ValueError(f"shape {tuple(shape)}: a seeded clip has fewer than 2^31 elements")
         if device is None:
             p0 = next(unet.parameters(), None) if hasattr(unet, "parameters") else None
             device = p0.device if p0 is not None else "cpu"
@@ -83,9 +94,13 @@ class SlotSampler:
             self._state = torch.zeros((n, hip_ops.SLOT_STATE_WORDS), device=dev, dtype=torch.int32)    # phase 0, nothing in the ring
             self._ring = torch.zeros((n, 3, C, Fp, h, w), device=dev, dtype=f32)
             self._xprov = torch.zeros_like(self._x)
+        self.stochastic = bool(stochastic)
+        if self.stochastic:
+            self._seeds = torch.zeros((n, 2), device=dev, dtype=torch.int32)          # (lo, hi) words of a slot's uint64 seed
+            self._temp = torch.ones((n,), device=dev, dtype=f32)
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
-        self._tables: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._tables: Dict[Tuple[int, float], Tuple[torch.Tensor, torch.Tensor]] = {}
         self._capture_refused = False
 
     # ---- the queue's host side -----------------------------------------------------------------------------------------------
@@ -99,12 +114,13 @@ class SlotSampler:
         """a copy of the slot's pred_x0 of its last step (it stays readable after the slot retired, until the slot is refilled)"""
         return self._pred[slot:slot + 1].clone()
 
-    def _schedule(self, S: int):
-        """DDIMSampler.make_schedule(S): the same tables bit for bit, made once per S"""
-        if S not in self._tables:
-            self._sched.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=False)
-            self._tables[S] = (self._sched.ddim_coef, self._sched._t_table)
-        return self._tables[S]
+    def _schedule(self, S: int, eta: float = 0.):
+        """DDIMSampler.make_schedule(S, ddim_eta=eta): the same tables bit for bit, made once per (S, eta)"""
+        key = (S, float(eta))
+        if key not in self._tables:
+            self._sched.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=False)
+            self._tables[key] = (self._sched.ddim_coef, self._sched._t_table)
+        return self._tables[key]
 
     def _clip(self, t: Optional[torch.Tensor], want, what: str) -> torch.Tensor:
         if t is None or tuple(t.shape) not in (tuple(want), (1, *want)):
@@ -113,7 +129,8 @@ class SlotSampler:
         return t.reshape(want).to(device=self.device, dtype=torch.float32)
 
     @torch.no_grad()
-    def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim") -> int:
+    def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim", seed: Optional[int] = None,
+               temperature: float = 1.) -> int:
         """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
         [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
         empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
@@ -122,25 +139,36 @@ class SlotSampler:
         slot's part of the static buffers; the engine's 16-bit context and the cross-attention K|V of the text blocks are then
         refreshed at the next step through the engine's own context path -- over ALL slots, not only the one that changed (1 + 16
         small launches per admission; a per-slot refresh is not built).
+        A sampler built with stochastic=True also takes eta (the clip's tables then carry its sigma), seed (an unsigned 64-bit
+        integer: the clip's noise is Philox stream 1 of it, and with x_T = None its start code is stream 0) and temperature; eta > 0
+        needs a seed.  Without stochastic=True any of the three is a ValueError.
         Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
         constructor's, eta != 0, a frame-sharded model, an unknown method and "plms" on a sampler built without it."""
         C, Fp, h, w = self.shape
         F, (L, D) = self.f1 + Fp, self.context_shape
-        if eta != 0:
-            raise ValueError(f"eta = {eta}: slots run the deterministic update only (eta = 0)")
+        if not self.stochastic:
+            if eta != 0:
+                raise ValueError(f"eta = {eta}: slots run the deterministic update only (eta = 0) unless built with stochastic=True")
+            if seed is not None or temperature != 1.:
+                raise ValueError("seed / temperature need a sampler built with stochastic=True")
+        elif eta < 0 or (eta != 0 and seed is None):
+            raise ValueError(f"eta = {eta} needs a seed: a slot draws its noise from the clip's own seed, not from torch's generator")
+        if seed is not None and not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed = {seed}: a seed is an unsigned 64-bit integer")
         if method not in ("ddim", "plms"):
             raise ValueError(f"method = {method!r}: 'ddim' or 'plms'")
         if method == "plms" and not self.plms:
             raise ValueError("method = 'plms' needs a sampler built with plms=True")
         if getattr(self.unet, "_shard", None) is not None:
             raise ValueError("a frame-sharded model cannot run slots: detach it (parallel.attach) first")
-        x_T = self._clip(x_T, (C, Fp, h, w), "x_T")
+        if x_T is not None or seed is None:
+            x_T = self._clip(x_T, (C, Fp, h, w), "x_T")
         if self.f1:
             x0_emb = self._clip(x0_emb, (C, self.f1, h, w), "x0_emb")
         elif x0_emb is not None:
             raise ValueError("x0_emb given to a sampler built with cond_frames = 0")
         c, uc = self._clip(c, (F, L, D), "c"), self._clip(uc, (F, L, D), "uc")
-        coef, ttab = self._schedule(int(S))
+        coef, ttab = self._schedule(int(S), eta)
         n = int(coef.shape[0])
         if n > self.max_steps:
             raise ValueError(f"S = {S} makes a schedule of {n} entries, this sampler was built for max_steps = {self.max_steps}")
@@ -151,7 +179,13 @@ class SlotSampler:
         self._coef[s, :n].copy_(coef)
         self._ttab[s, :n].copy_(ttab)
         self._scale[s:s + 1].fill_(float(scale))
-        self._x[s].copy_(x_T)
+        if x_T is None:                              # the start code of a seeded clip: stream 0 of its seed
+            self.ops.philox_normal(int(seed), hip_ops.PHILOX_STREAM_START, 0, self._x[s].numel(), out=self._x[s])
+        else:
+            self._x[s].copy_(x_T)
+        if self.stochastic:
+            self._seeds[s].copy_(hip_ops.seed_words([0 if seed is None else seed])[0])
+            self._temp[s:s + 1].fill_(float(temperature))
         if self.f1:
             self._x0[s].copy_(x0_emb)
         self._context[s].copy_(uc)
@@ -188,7 +222,7 @@ class SlotSampler:
         return done
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
-        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=]): fills free slots in request order (a
+        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=]): fills free slots in request order (a
         request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
         finishing order."""
         it, tags, more = iter(requests), {}, True
@@ -215,6 +249,10 @@ class SlotSampler:
             return
         self.ops.slot_step_begin(self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t)
         eps = model()
+        if self.stochastic:
+            self.ops.slot_cfg_ddim_step_rng(eps, self._x, self._scale, self._coef, self._step, self._seeds, self._temp, cond_f=self.f1,
+                                            x_prev=self._x, pred_x0=self._pred)
+            return
         self.ops.slot_cfg_ddim_step(eps, self._x, self._scale, self._coef, self._step, cond_f=self.f1, x_prev=self._x,
                                     pred_x0=self._pred)
 
@@ -236,7 +274,7 @@ class SlotSampler:
         G = None
         if (unet.use_graph and self.ops is hip_ops and unet._ops_backend is hip_ops and self._x.is_cuda
                 and not self._capture_refused and not getattr(eng, "_graph_broken", False)):
-            key = ("slots-plms" if self.plms else "slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+            key = ("slots-plms" if self.plms else "slots-rng" if self.stochastic else "slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)
