@@ -547,7 +547,8 @@ int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t 
  *   key      (seed & 0xffffffff, seed >> 32), one uint64 seed per clip; in device memory uint32 [rows][2] = (lo, hi), 4-byte aligned
  *   counter  (block, index, stream, 0); block = e >> 2 with e the element's linear index inside the clip's own [C, F_pred, HW]
  *            latent, and element e takes normal e & 3 of its block.  stream 0 = the start code (index 0), stream 1 = the noise of
- *            the step at schedule index `index`, streams >= 2 reserved
+ *            the step at schedule index `index`, stream 2 = the noise that re-noises given latents to the level of schedule index
+ *            `index` ("given latents" below), streams >= 3 reserved
  *   uniform  u = float(2 * (w >> 9) + 1) * 2^-24, exact in fp32 and strictly inside (0, 1)
  *   normals  Box-Muller on the word pairs (w0, w1), (w2, w3): r = sqrtf(-2 logf(u_a)), (s, c) = sincospif(2 u_b), n_even = r c,
  *            n_odd = r s; |n| <= 5.7682
@@ -581,6 +582,30 @@ int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t b, int32_t
 int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                                 const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
                                 const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0, void* stream);
+
+/* ---- given latents: masked sampling and stochastic_encode (CompVis ldm/models/diffusion/ddim.py:144-147, 207-221) --------------
+ * q(e) = sqrtf(a_t) * x0[e] + s1m * n[e]: the given latent x0 noised to the level of coefficient row `index` (a_t = column 0, s1m =
+ * column 3).  n is a noise tensor shaped like x0, or -- with seeds uint32 [rows][2] as above -- normal e of Philox stream 2 of the
+ * row's seed at that index, e counted in the clip's own [C, F_pred, HW] latent.  Exactly one of `noise` and `seeds` is non-NULL; the
+ * seeded form gives the bits of the noise-tensor form fed seer_philox_normal(seed, 2, index).
+ *   seer_q_sample          out[bi][e] = q with row index[bi] of coef (fp32 [nsched][4]); x0, noise, out fp32 [b][per_row], index int32
+ *                          [b] in device memory.  A row whose index is outside 0 .. nsched - 1 is not written.
+ *   seer_known_blend       the mask blend in front of one sampler step, on x [b, C, F_pred, HW] in place.  mask fp32 [b, F_pred, HW]
+ *                          (broadcast over channels, values in [0, 1]), known fp32 shaped like x.  index = step[0] when `step` is
+ *                          non-NULL (device memory, only read: the kernel runs in front of seer_ddim_step_begin), else the host's
+ *                          `index`.  Per element: mask == 0 writes nothing and draws nothing (x keeps its bits); mask == 1 stores q,
+ *                          whatever x holds; otherwise x = q * m + (1 - m) * x.  An index < 0 writes nothing.
+ *   seer_slot_known_blend  the same over slots, seeded: mask [slots, F_pred, HW], known [slots, C, F_pred, HW], coef fp32
+ *                          [slots][nsched][4], index = step[s][0], seeds [slots][2].  A slot whose index is < 0 or >= nsched, or
+ *                          whose mask is all zero, is untouched.  It runs in front of seer_slot_step_begin.
+ * None of the three writes a step word.  SEER_EINVAL for a NULL required pointer, both or neither of noise and seeds, non-positive
+ * extents, a clip (a row of seer_q_sample) of >= 2^31 elements, a pointer that is not 4-byte aligned, a grid beyond one dimension. */
+int seer_q_sample(const float* x0, int32_t b, int64_t per_row, const float* coef, int32_t nsched, const int32_t* index,
+                  const float* noise, const uint32_t* seeds, float* out, void* stream);
+int seer_known_blend(float* x, const float* mask, const float* known, int32_t b, int32_t C, int32_t F_pred, int32_t HW,
+                     const float* coef, int32_t index, const int32_t* step, const float* noise, const uint32_t* seeds, void* stream);
+int seer_slot_known_blend(float* x, const float* mask, const float* known, int32_t slots, int32_t C, int32_t F_pred, int32_t HW,
+                          const float* coef, int32_t nsched, const int32_t* step, const uint32_t* seeds, void* stream);
 
 /* CFG combine + PLMS update of PLMSSampler.p_sample_plms (ldm/models/diffusion/plms.py:199-236; eta = 0, so no noise term), fp32.
  * e is the CFG-combined eps of this evaluation as in seer_cfg_ddim_step (frames >= cond_f only); h1, h2, h3 are earlier e,

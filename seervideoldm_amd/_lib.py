@@ -169,6 +169,9 @@ SIGNATURES = {
     "seer_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
     "seer_cfg_ddim_step_rng_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
     "seer_slot_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_q_sample": ([_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_known_blend": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_slot_known_blend": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp], C.c_int),
     "seer_slot_plms_step_begin": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_cfg_plms_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                                 C.c_int),

@@ -567,6 +567,70 @@ __global__ void slot_cfg_ddim_rng_kernel(const float* __restrict__ eps, int slot
                     temperature[s], (uint32_t)(i - (int64_t)s * per_slot), x_prev, pred_x0, i);
 }
 
+// ---- GIVEN latents (masked sampling, stochastic_encode; CompVis ldm/models/diffusion/ddim.py:144-147, 207-221): q(e) is the given
+// latent x0 noised to the level of coefficient row `index`, its noise n either read from a tensor or normal e of Philox stream 2 of
+// the clip's seed at that index.  One expression for the three kernels below, so the seeded form gets the bits of the noise-tensor
+// form fed seer_philox_normal(seed, 2, index).
+__device__ __forceinline__ float q_known(const float* __restrict__ coef, int index, float x0v, float n) {
+    return sqrtf(coef[4 * index]) * x0v + coef[4 * index + 3] * n;
+}
+
+__device__ __forceinline__ float known_noise(const float* __restrict__ noise, int64_t i, const uint32_t* __restrict__ seed, int index,
+                                             uint32_t el) {
+    return noise ? noise[i] : seer_philox::normal_at(seed[0], seed[1], seer_philox::STREAM_KNOWN, (uint32_t)index, el);
+}
+
+// the blend of one element: m == 0 leaves the word alone (nothing is read but the mask, nothing drawn), m == 1 selects q whatever
+// x holds, anything else is CompVis's img_orig * mask + (1. - mask) * img
+__device__ __forceinline__ void known_blend_at(float* x, float m, const float* __restrict__ known, const float* __restrict__ coef,
+                                               int index, const float* __restrict__ noise, const uint32_t* __restrict__ seed,
+                                               uint32_t el, int64_t i) {
+    if (m == 0.f) return;
+    const float q = q_known(coef, index, known[i], known_noise(noise, i, seed, index, el));
+    x[i] = m == 1.f ? q : q * m + (1.f - m) * x[i];
+}
+
+// out[bi][e] = q with row index[bi] of coef; a row whose index is outside 0 .. nsched - 1 is not written
+__global__ void q_sample_kernel(const float* __restrict__ x0, int b, int64_t per_row, const float* __restrict__ coef, int nsched,
+                                const int* __restrict__ index, const float* __restrict__ noise, const uint32_t* __restrict__ seeds,
+                                float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)b * per_row) return;
+    const int64_t bi = i / per_row;
+    const int idx = index[bi];
+    if (idx < 0 || idx >= nsched) return;
+    out[i] = q_known(coef, idx, x0[i], known_noise(noise, i, seeds + 2 * bi, idx, (uint32_t)(i - bi * per_row)));
+}
+
+// x [b, C, Fp, HW] in place; mask [b, Fp, HW] is broadcast over channels.  step != nullptr: index = step[0], the NEXT step's index
+// (this kernel runs in front of seer_ddim_step_begin); it is only read.
+__global__ void known_blend_kernel(float* x, const float* __restrict__ mask, const float* __restrict__ known, int b, int C, int Fp,
+                                   int HW, const float* __restrict__ coef, int index, const int* __restrict__ step,
+                                   const float* __restrict__ noise, const uint32_t* __restrict__ seeds) {
+    const int64_t per_frames = (int64_t)Fp * HW, per_clip = per_frames * C;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step) index = step[0];
+    if (index < 0 || i >= (int64_t)b * per_clip) return;
+    const int64_t bi = i / per_clip;
+    const int64_t el = i - bi * per_clip;
+    known_blend_at(x, mask[bi * per_frames + el % per_frames], known, coef, index, noise, seeds + 2 * bi, (uint32_t)el, i);
+}
+
+// the same over slots, seeded: index = step[s][0] and coef[s]; an idle slot (index < 0 or >= nsched) writes nothing
+__global__ void slot_known_blend_kernel(float* x, const float* __restrict__ mask, const float* __restrict__ known, int slots, int C,
+                                        int Fp, int HW, const float* __restrict__ coef, int nsched, const int* __restrict__ step,
+                                        const uint32_t* __restrict__ seeds) {
+    const int64_t per_frames = (int64_t)Fp * HW, per_slot = per_frames * C;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)slots * per_slot) return;
+    const int64_t s = i / per_slot;
+    const int index = step[2 * s];
+    if (index < 0 || index >= nsched) return;
+    const int64_t el = i - s * per_slot;
+    known_blend_at(x, mask[s * per_frames + el % per_frames], known, coef + s * nsched * 4, index, nullptr, seeds + 2 * s, (uint32_t)el,
+                   i);
+}
+
 // ---- the same step with a SAMPLER per slot: DDIM and PLMS clips side by side.  state int32 [slots][8] = (phase, valid, newest, -)
 // of the NEXT step, then the same three words of the step IN FLIGHT; ring fp32 [slots][3][C*Fp*HW] = the slot's earlier e, x_prov
 // [slots][C*Fp*HW] its provisional latent.  The begin kernel reads next words and writes in-flight words, the update kernel reads
@@ -945,6 +1009,52 @@ extern "C" int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int3
     if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
     hipLaunchKernelGGL(slot_cfg_ddim_rng_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), eps, slots, C, F_total,
                        cond_f, HW, scale, coef, nsched, step, x, seeds, temperature, x_prev, pred_x0);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+// given latents: exactly one of noise and seeds; a clip's element index is a Philox counter word, as in the *_rng entry points
+static inline bool known_clip_ok(int32_t C, int32_t F_pred, int32_t HW) {
+    return C > 0 && F_pred > 0 && HW > 0 && (int64_t)C * F_pred * HW < ((int64_t)1 << 31);
+}
+
+extern "C" int seer_q_sample(const float* x0, int32_t b, int64_t per_row, const float* coef, int32_t nsched, const int32_t* index,
+                             const float* noise, const uint32_t* seeds, float* out, void* stream) {
+    if (!x0 || !coef || !index || !out || (noise != nullptr) == (seeds != nullptr) || b <= 0 || nsched < 1 || per_row <= 0 ||
+        per_row >= ((int64_t)1 << 31))
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({x0, coef, index, noise, seeds, out})) return SEER_EINVAL;
+    const int64_t n = (int64_t)b * per_row;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(q_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x0, b, per_row, coef, nsched, index,
+                       noise, seeds, out);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_known_blend(float* x, const float* mask, const float* known, int32_t b, int32_t C, int32_t F_pred, int32_t HW,
+                                const float* coef, int32_t index, const int32_t* step, const float* noise, const uint32_t* seeds,
+                                void* stream) {
+    if (!x || !mask || !known || !coef || (noise != nullptr) == (seeds != nullptr) || b <= 0 || !known_clip_ok(C, F_pred, HW))
+        return SEER_EINVAL;
+    if (!slot_ptrs_ok({x, mask, known, coef, step, noise, seeds})) return SEER_EINVAL;
+    const int64_t n = (int64_t)b * C * F_pred * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(known_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x, mask, known, b, C, F_pred, HW,
+                       coef, index, step, noise, seeds);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_slot_known_blend(float* x, const float* mask, const float* known, int32_t slots, int32_t C, int32_t F_pred,
+                                     int32_t HW, const float* coef, int32_t nsched, const int32_t* step, const uint32_t* seeds,
+                                     void* stream) {
+    if (!x || !mask || !known || !coef || !step || !seeds || slots < 1 || nsched < 1 || !known_clip_ok(C, F_pred, HW)) return SEER_EINVAL;
+    if (!slot_ptrs_ok({x, mask, known, coef, step, seeds})) return SEER_EINVAL;
+    const int64_t n = (int64_t)slots * C * F_pred * HW;
+    if ((n + 255) / 256 > 0x7fffffff) return SEER_EINVAL;
+    hipLaunchKernelGGL(slot_known_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S(stream), x, mask, known, slots, C,
+                       F_pred, HW, coef, nsched, step, seeds);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

@@ -5,7 +5,8 @@
 //
 //   key      (seed & 0xffffffff, seed >> 32): one 64-bit seed per clip
 //   counter  (block, index, stream, 0); block = e >> 2 for element e of the clip's own [C, F_pred, HW] latent; element e takes normal
-//            e & 3 of its block.  stream 0 = the start code (index 0), stream 1 = the step noise (index = schedule index), >= 2 reserved
+//            e & 3 of its block.  stream 0 = the start code (index 0), stream 1 = the step noise (index = schedule index), stream 2 = the
+//            noise that re-noises GIVEN latents to the level of schedule index `index` (seer_q_sample, seer_known_blend), >= 3 reserved
 //   uniform  u = float(2 * (w >> 9) + 1) * 2^-24: exact in fp32, strictly inside (0, 1)
 //   normals  Box-Muller on (w0, w1) and (w2, w3): r = sqrtf(-2 logf(u_a)), (s, c) = sincospif(2 u_b) -- the argument is exact, no
 //            2 pi rounding -- n_even = r c, n_odd = r s.  |n| <= 5.7682 (u_a = 2^-24).
@@ -18,7 +19,7 @@ namespace seer_philox {
 
 constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;      // round multipliers
 constexpr uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;      // key increments
-enum : uint32_t { STREAM_START = 0, STREAM_STEP = 1 };
+enum : uint32_t { STREAM_START = 0, STREAM_STEP = 1, STREAM_KNOWN = 2 };
 
 // ten rounds of (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), the key bumped between rounds
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,

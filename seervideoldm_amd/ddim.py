@@ -15,6 +15,11 @@ multi-sample run consumes the device RNG stream identically.
 "Seeded noise"): the start code is seer_philox_normal of the row's seed, the noise of a step is drawn by seer_cfg_ddim_step_rng from
 (seed, schedule index, element).  Nothing comes from torch's generator, the captured step is taken for eta > 0 too, and a row's
 noise does not depend on the batch it is in.
+
+`sample(..., mask=, x0=)`, `stochastic_encode` and `decode` follow the vendored CompVis sampler (ldm/models/diffusion/ddim.py:144-147,
+207-241), whose mask blend ddim_video.py lost: kept regions are re-noised to each step's level and blended in in front of the step
+(seer_known_blend; with a seed a node of the captured step, DESIGN.md "Editing"), a clip can be noised to a level of the schedule
+(seer_q_sample) and denoised from there.
 """
 from __future__ import annotations
 
@@ -48,6 +53,9 @@ class DDIMSampler(object):
         self.ddpm_num_timesteps = timesteps
         self.schedule = schedule
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
+        # the backend of the step's own kernels outside the captured step (tests inject a torch restatement to run this class on the
+        # CPU; the captured step is taken with the HIP backend only)
+        self.ops = kwargs.get("ops") or ops
         self.consume_rng_when_deterministic = True
         # p_sample_ddim under graph replay hands out its static latent buffers instead of copies of them: the next step
         # overwrites what the previous one returned.  ddim_sampling sets it for its own loop (and copies what it keeps).
@@ -108,16 +116,20 @@ class DDIMSampler(object):
                                   img_callback=img_callback, cond_frames=cond_frames, temperature=temperature,
                                   noise_dropout=noise_dropout, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds)
+                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds, mask=mask, x0=x0)
 
     @torch.no_grad()
     def ddim_sampling(self, unet, cond, shape, is_3d, x0_emb=None, cond_frames=0, x_T=None, callback=None,
                       img_callback=None, log_every_t=100, temperature=1., noise_dropout=0.,
-                      unconditional_guidance_scale=1., unconditional_conditioning=None, seeds=None, **kwargs):
+                      unconditional_guidance_scale=1., unconditional_conditioning=None, seeds=None, mask=None, x0=None,
+                      **kwargs):
         """`seeds`: None, or one uint64 per batch row (sample's `seed`): the start code (when x_T is None) and the noise of every step
-        then come from the rows' Philox streams, nothing from torch's generator"""
+        then come from the rows' Philox streams, nothing from torch's generator.  `mask` (broadcastable to [b, 1, F_pred, h, w], values
+        in [0, 1]) with `x0` [b, C, F_pred, h, w]: in front of every step the latent becomes q * mask + (1 - mask) * latent, q = x0
+        noised to that step's level (CompVis ddim.py:144-147); the final latent is not blended again."""
         device = self.device
         b = shape[0]
+        known = self._known_pair(unet, mask, x0, shape)
         if seeds is not None:
             seeds = list(seeds)
             if len(seeds) != b:
@@ -125,7 +137,7 @@ class DDIMSampler(object):
             if x_T is None:
                 x_T = torch.empty(shape, device=device, dtype=torch.float32)
                 for row, s in zip(x_T, seeds):           # a row's start code: stream 0 of its own seed
-                    ops.philox_normal(s, ops.PHILOX_STREAM_START, 0, row.numel(), out=row)
+                    self.ops.philox_normal(s, ops.PHILOX_STREAM_START, 0, row.numel(), out=row)
             seeds = ops.seed_words(seeds).to(device)
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
         # one clip sharded over several ranks (parallel.attach): every rank must denoise the SAME latent.  The start code,
@@ -133,65 +145,149 @@ class DDIMSampler(object):
         img = _from_rank0(unet, img)
         if x0_emb is not None:
             x0_emb = _from_rank0(unet, x0_emb.to(device))
-        timesteps = self.ddim_timesteps
         intermediates = {"x_inter": [img], "pred_x0": [img]}
-        total_steps = timesteps.shape[0]
+        img = self._run_chain(unet, img, cond, self.ddim_timesteps.shape[0], is_3d=is_3d, x0_emb=x0_emb, cond_frames=cond_frames,
+                              temperature=temperature, noise_dropout=noise_dropout, scale=unconditional_guidance_scale,
+                              uc=unconditional_conditioning, seeds=seeds, known=known, callback=callback, img_callback=img_callback,
+                              log_every_t=log_every_t, intermediates=intermediates)
+        return img, intermediates
+
+    def _run_chain(self, unet, img, cond, n_steps, *, is_3d=True, x0_emb=None, cond_frames=0, temperature=1., noise_dropout=0., scale=1.,
+                   uc=None, seeds=None, known=None, callback=None, img_callback=None, log_every_t=100, intermediates=None):
+        """schedule indices n_steps - 1 ... 0 through p_sample_ddim, starting from `img`; returns a copy of the last latent"""
+        b = img.shape[0]
+        total_steps = self.ddim_timesteps.shape[0]
         # inside this loop a captured step may hand out its static buffers (nothing here keeps a step's output past the next
         # step without copying it)
         static_before, self.static_step_outputs = self.static_step_outputs, True
         try:
-            for i, step in enumerate(np.flip(timesteps)):
-                index = total_steps - i - 1
+            for i, index in enumerate(reversed(range(n_steps))):
                 ts = self._t_table[index].expand(b)
                 img, pred_x0 = self.p_sample_ddim(unet, img, cond, ts, index=index, is_3d=is_3d, x0_emb=x0_emb,
                                                   cond_frames=cond_frames, temperature=temperature,
                                                   noise_dropout=noise_dropout,
-                                                  unconditional_guidance_scale=unconditional_guidance_scale,
-                                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds)
+                                                  unconditional_guidance_scale=scale,
+                                                  unconditional_conditioning=uc, seeds=seeds, known=known)
                 if callback:
                     callback(i)
                 if img_callback:
                     img_callback(pred_x0.clone(), i)
-                if index % log_every_t == 0 or index == total_steps - 1:
+                if intermediates is not None and (index % log_every_t == 0 or index == total_steps - 1):
                     intermediates["x_inter"].append(img.clone())
                     intermediates["pred_x0"].append(pred_x0.clone())
         finally:
             self.static_step_outputs = static_before
-        return img.clone(), intermediates
+        return img.clone()
+
+    def _known_pair(self, unet, mask, x0, shape):
+        """sample's `mask` / `x0` -> None, or (mask fp32 [b, F_pred, h, w], x0 fp32 [b, C, F_pred, h, w]) on the sampler's device, made
+        once per call: the captured step keys its static copies on these two tensors"""
+        if mask is None and x0 is None:
+            return None
+        if mask is None or x0 is None:
+            raise ValueError("mask and x0 go together: the mask says where the latent is given, x0 what it is there")
+        if getattr(unet, "_shard", None) is not None:
+            raise ValueError("mask: a frame-sharded model cannot blend given latents (detach it, parallel.attach)")
+        b, Cc, Fp, h, w = shape
+        mask = torch.as_tensor(mask)
+        if mask.dim() > 5 or (mask.dim() == 5 and mask.shape[1] != 1):
+            raise ValueError(f"mask {tuple(mask.shape)}: a mask is shared by a clip's channels, [b, 1, F_pred, h, w] (per-channel masks "
+                             "are not built)")
+        try:
+            mask = torch.broadcast_to(mask, (b, 1, Fp, h, w))
+        except RuntimeError:
+            raise ValueError(f"mask {tuple(mask.shape)} does not broadcast to {(b, 1, Fp, h, w)}") from None
+        if tuple(x0.shape) != tuple(shape):
+            raise ValueError(f"x0 {tuple(x0.shape)}: the given latents have the clip's shape {tuple(shape)}")
+        return (mask.to(device=self.device, dtype=torch.float32).reshape(b, Fp, h, w).contiguous(),
+                x0.to(device=self.device, dtype=torch.float32).contiguous())
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, seed=None):
+        """CompVis ddim.py:207-221 on the current schedule: sqrt(a_t) x0 + sqrt(1 - a_t) noise with t (an int, or an integer tensor
+        [b]) indexing the DDIM tables.  `noise` as given; with `seed` (an int: row i takes seed + i, or one per row) Philox stream 2 of
+        the row's seed at index t; with neither torch.randn_like(x0)."""
+        if use_original_steps:
+            raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
+        if noise is not None and seed is not None:
+            raise ValueError("stochastic_encode: `noise` or `seed`, not both")
+        x0 = x0.to(device=self.device, dtype=torch.float32).contiguous()
+        b, n = x0.shape[0], int(self.ddim_coef.shape[0])
+        rows = [int(v) for v in t.reshape(-1).tolist()] if torch.is_tensor(t) else [int(t)]
+        if len(rows) == 1:
+            rows = rows * b
+        if len(rows) != b or any(not 0 <= v < n for v in rows):
+            raise ValueError(f"t = {t!r}: one index into the {n} entries of the current schedule, or one per row of {b}")
+        index = torch.tensor(rows, dtype=torch.int32, device=self.device)
+        if seed is not None:
+            return self.ops.q_sample(x0, self.ddim_coef, index, seeds=ops.seed_words(_row_seeds(seed, b)).to(self.device))
+        noise = torch.randn_like(x0) if noise is None else noise.to(device=self.device, dtype=torch.float32).contiguous()
+        return self.ops.q_sample(x0, self.ddim_coef, index, noise=noise)
+
+    @torch.no_grad()
+    def decode(self, unet, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
+               use_original_steps=False, *, x0_emb=None, cond_frames=0, seed=None, temperature=1., mask=None, x0=None):
+        """CompVis ddim.py:223-241 with the UNet first, as in sample: indices t_start - 1 ... 0 of the current schedule through
+        p_sample_ddim, from x_latent taken as the latent at level t_start.  seed, mask and x0 as in sample."""
+        if use_original_steps:
+            raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
+        n = int(self.ddim_timesteps.shape[0])
+        if not 1 <= int(t_start) <= n:
+            raise ValueError(f"t_start = {t_start}: 1 .. {n}, the entries of the current schedule")
+        b = x_latent.shape[0]
+        seeds = _row_seeds(seed, b)
+        if seeds is not None and getattr(unet, "_shard", None) is not None:
+            raise ValueError("seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)")
+        known = self._known_pair(unet, mask, x0, tuple(x_latent.shape))
+        if seeds is not None:
+            seeds = ops.seed_words(seeds).to(self.device)
+        img = _from_rank0(unet, x_latent.to(device=self.device, dtype=torch.float32))
+        if x0_emb is not None:
+            x0_emb = _from_rank0(unet, x0_emb.to(self.device))
+        return self._run_chain(unet, img, cond, int(t_start), x0_emb=x0_emb, cond_frames=cond_frames, temperature=temperature,
+                               scale=unconditional_guidance_scale, uc=unconditional_conditioning, seeds=seeds, known=known)
 
     @torch.no_grad()
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                       use_original_steps=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      null_cond_prob=None, seeds=None):
+                      null_cond_prob=None, seeds=None, known=None):
         """ddim_video.py:183-238.  `seeds` (int32 [b, 2] on x's device, ops.seed_words; not in the reference): the step's noise is
-        drawn inside its last kernel from the rows' seeds and `index`, and torch's generator is left alone."""
+        drawn inside its last kernel from the rows' seeds and `index`, and torch's generator is left alone.  `known` (_known_pair's
+        mask and given latents; not in the reference either): the mask blend of CompVis ddim.py:144-147 in front of the step, on a
+        copy of x -- with seeds a node of the captured step, its noise stream 2 of the rows' seeds; without, a torch.randn drawn
+        before the step's own draw, as CompVis orders them."""
         if use_original_steps or noise_dropout > 0. or repeat_noise:
             raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
         x = x.to(torch.float32).contiguous()
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         sigma = float(self.ddim_sigmas[index])
+        if known is not None and seeds is None:
+            x = self.ops.known_blend(x.clone(), known[0], known[1], self.ddim_coef, index, noise=torch.randn(x.shape, device=x.device))
+            known = None
         # the whole step -- input assembly, CFG-batched UNet, CFG combine, DDIM update -- as ONE replayed hipGraph when the model
         # replays graphs anyway (unet.use_graph) and the step is the one ddim_sample drives: batched CFG or none, eta = 0, and
         # t = the schedule's own timestep of `index` (recognised by its address: a view of the device timestep table)
-        if ((sigma == 0. or seeds is not None) and getattr(unet, "use_graph", False) and x.is_cuda and (uc is None or scale == 1. or uc.shape[2] == c.shape[2])
+        if ((sigma == 0. or seeds is not None) and getattr(unet, "use_graph", False) and x.is_cuda and self.ops is ops and (uc is None or scale == 1. or uc.shape[2] == c.shape[2])
                 and torch.is_tensor(t) and t.dtype == torch.long and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
             plain = uc is None or scale == 1.
             done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale,
-                                    seeds=seeds, temperature=temperature)
+                                    seeds=seeds, temperature=temperature, known=known)
             if done is not None:
                 return done
+        if known is not None:
+            x = self.ops.known_blend(x.clone(), known[0], known[1], self.ddim_coef, index, seeds=seeds)
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
         if seeds is not None:
-            return ops.cfg_ddim_step_rng(eps.float().contiguous(), x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale, cond_f=cond_f,
-                                         temperature=temperature)
+            return self.ops.cfg_ddim_step_rng(eps.float().contiguous(), x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale,
+                                              cond_f=cond_f, temperature=temperature)
         noise = None
         if sigma != 0. or self.consume_rng_when_deterministic:
             noise = torch.randn(x.shape, device=x.device) * temperature
             if sigma != 0.:
                 noise = _from_rank0(unet, noise)
-        x_prev, pred_x0 = ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale,
-                                            cond_f=cond_f, noise=noise if sigma != 0. else None)
+        x_prev, pred_x0 = self.ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale,
+                                                 cond_f=cond_f, noise=noise if sigma != 0. else None)
         return x_prev, pred_x0
 
     def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale):
@@ -223,13 +319,15 @@ class DDIMSampler(object):
         return eps, cfg, cond_f
 
     # ---- the captured step -----------------------------------------------------------------------------------------
-    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1.):
+    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1., known=None):
         """One p_sample_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_step_dev):
         no torch kernel between two UNet evaluations except the reference's per-step RNG draw, no host-written scalars -- the
         schedule index lives in device memory and the captured step counts it down itself.  Returns None when this step cannot
         take the path (sharded model, capture refused): the caller then runs the launches one by one.  With `seeds` the last kernel
-        is seer_cfg_ddim_step_rng_dev and the step draws nothing, at any eta."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, rng=None if seeds is None else float(temperature))
+        is seer_cfg_ddim_step_rng_dev and the step draws nothing, at any eta.  With `known` (seeded only) seer_known_blend is the
+        step's first node, over static copies of the mask and the given latents."""
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, rng=None if seeds is None else float(temperature),
+                             masked=known is not None)
         if G is None:
             return None
         if seeds is not None:
@@ -237,6 +335,12 @@ class DDIMSampler(object):
             if G["seeds_key"] != k or G["seeds_ref"] is not seeds:
                 G["seeds"].copy_(seeds)
                 G["seeds_key"], G["seeds_ref"] = k, seeds
+        if known is not None:
+            k = tuple((t.data_ptr(), t._version) for t in known)
+            if G["known_key"] != k or G["known_ref"][0] is not known[0] or G["known_ref"][1] is not known[1]:
+                G["mask"].copy_(known[0])
+                G["known"].copy_(known[1])
+                G["known_key"], G["known_ref"] = k, known
         if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
             G["x"].copy_(x)
         if G["expect"] != index:
@@ -263,11 +367,12 @@ class DDIMSampler(object):
         ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], cfg=cfg, scale=scale, cond_f=cond_f, x_prev=G["x"],
                               pred_x0=G["pred"])
 
-    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, rng=None):
+    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, rng=None, masked=False):
         """the captured step of this shape / CFG / scale (captured on first use) with its read-by-address inputs refreshed; None
         when the step cannot be captured.  rng = the temperature of a seeded step (None: the sampler's own step): a kind of its own in
         the key -- "step-rng" -- with the temperature, which like the guidance scale is an argument of the last kernel and frozen into
-        the capture; the seeds live in a static buffer and are no part of the key."""
+        the capture; the seeds live in a static buffer and are no part of the key.  masked (with rng only): the kind "step-mask", the
+        seeded step with seer_known_blend in front; mask and given latents are static buffers too."""
         from .unet import SeerUNet
         if not isinstance(unet, SeerUNet) or unet._shard is not None or unet._ops_backend is not ops \
                 or unet.config.center_input_sample or getattr(self, "_step_graph_broken", False):
@@ -297,10 +402,10 @@ class DDIMSampler(object):
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
         key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv)
         if rng is not None:
-            key = ("step-rng", *key[1:], float(rng))
+            key = ("step-mask" if masked else "step-rng", *key[1:], float(rng))
         G = eng.graph_get(key)
         if G is None:
-            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L, rng)
+            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L, rng, masked)
             if G is None:
                 return None
         # inputs that are read by address: refreshed in place when the caller brings new ones (once per sample / per schedule)
@@ -322,7 +427,7 @@ class DDIMSampler(object):
             G["expect"] = None
         return G
 
-    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L, rng=None):
+    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L, rng=None, masked=False):
         dev = x.device
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
@@ -339,8 +444,15 @@ class DDIMSampler(object):
         G["x"].copy_(x)
         if x0_emb is not None:
             G["x0"].copy_(x0_emb)
+        if masked:
+            # an all-zero mask through warm-up and capture: the blend writes nothing there, whatever the step words hold; the caller's
+            # mask and latents are copied in by _graph_step afterwards
+            G.update(mask=torch.zeros((b, Fp, h, w), device=dev, dtype=torch.float32), known=torch.zeros_like(x), known_key=None,
+                     known_ref=(None, None))
 
         def body():
+            if masked:
+                ops.known_blend(G["x"], G["mask"], G["known"], G["coef"], step=G["step"], seeds=G["seeds"])
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
             if rng is None:

@@ -1122,6 +1122,79 @@ def slot_cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tens
           "seer_slot_cfg_ddim_step_rng")
 
 
+# ---- given latents (include/seer_hip.h, "given latents"): masked sampling and stochastic_encode ------------------------------------
+PHILOX_STREAM_KNOWN = 2     # the noise that re-noises given latents to the level of a schedule index
+
+
+def _noise_or_seeds(noise: Optional[torch.Tensor], seeds: Optional[torch.Tensor], like: torch.Tensor) -> None:
+    if (noise is None) == (seeds is None):
+        raise ValueError("exactly one of `noise` and `seeds`")
+    if noise is not None:
+        _req(noise, torch.float32, "noise")
+        assert noise.is_contiguous() and noise.shape == like.shape
+    else:
+        _req_seeds(seeds, like.shape[0])
+
+
+def q_sample(x0: torch.Tensor, coef: torch.Tensor, index: torch.Tensor, *, noise: Optional[torch.Tensor] = None,
+             seeds: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """stochastic_encode: out[bi] = sqrt(a_t) x0[bi] + sqrt(1 - a_t) n[bi] with row index[bi] (int32 [b], on the device) of coef
+    [nsched, 4]; n = `noise` (shaped like x0) or stream 2 of seeds[bi] (int32 [b, 2], seed_words) at that index"""
+    _req(x0, torch.float32, "x0"); _req(coef, torch.float32, "coef"); _req(index, torch.int32, "index")
+    b = x0.shape[0]
+    assert x0.is_contiguous() and coef.is_contiguous() and coef.dim() == 2 and coef.shape[1] == 4
+    assert index.is_contiguous() and index.numel() == b
+    _noise_or_seeds(noise, seeds, x0)
+    if out is None:
+        out = torch.empty_like(x0)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == x0.shape
+    check(_lib.load().seer_q_sample(_p(x0), b, x0.numel() // b, _p(coef), coef.shape[0], _p(index), _p(noise), _p(seeds), _p(out),
+                                    _stream()), "seer_q_sample")
+    return out
+
+
+def _req_known(x: torch.Tensor, mask: torch.Tensor, known: torch.Tensor) -> None:
+    _req(x, torch.float32, "x"); _req(mask, torch.float32, "mask"); _req(known, torch.float32, "known")
+    rows, Cc, Fp, h, w = x.shape
+    assert x.is_contiguous() and known.is_contiguous() and known.shape == x.shape
+    assert mask.is_contiguous() and tuple(mask.shape) == (rows, Fp, h, w)
+
+
+def known_blend(x: torch.Tensor, mask: torch.Tensor, known: torch.Tensor, coef: torch.Tensor, index: int = 0, *,
+                step: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
+                seeds: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the mask blend in front of a sampler step, on x [b, C, Fp, h, w] IN PLACE: where mask [b, Fp, h, w] is 1, x = the given latent
+    `known` noised to the level of coef row `index` (`step[0]` when `step`, int32 on the device, is given: the captured form); where
+    it is 0, x keeps its bits; in between, q * m + (1 - m) * x.  The noise is `noise` or stream 2 of seeds[bi] at that index."""
+    _req_known(x, mask, known)
+    _req(coef, torch.float32, "coef")
+    if step is not None:
+        _req(step, torch.int32, "step")
+        assert step.numel() >= 2
+    elif not -1 <= int(index) < coef.shape[0]:
+        raise ValueError(f"index {index}: the table has {coef.shape[0]} rows")
+    _noise_or_seeds(noise, seeds, x)
+    b, Cc, Fp, h, w = x.shape
+    check(_lib.load().seer_known_blend(_p(x), _p(mask), _p(known), b, Cc, Fp, h * w, _p(coef), int(index), _p(step), _p(noise),
+                                       _p(seeds), _stream()), "seer_known_blend")
+    return x
+
+
+def slot_known_blend(x: torch.Tensor, mask: torch.Tensor, known: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
+                     seeds: torch.Tensor) -> None:
+    """known_blend over slots, seeded, in front of slot_step_begin: slot s blends with row step[s, 0] of coef[s] and seeds[s]; a slot
+    that is idle, or whose mask is all zero, is untouched (include/seer_hip.h, seer_slot_known_blend)"""
+    _req_known(x, mask, known)
+    _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    slots, Cc, Fp, h, w = x.shape
+    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
+    _req_seeds(seeds, slots)
+    check(_lib.load().seer_slot_known_blend(_p(x), _p(mask), _p(known), slots, Cc, Fp, h * w, _p(coef), coef.shape[1], _p(step),
+                                            _p(seeds), _stream()), "seer_slot_known_blend")
+
+
 SLOT_STATE_WORDS = 8    # int32 words of a slot's sampler state: (phase, valid, newest, -) of the next step, then of the step in flight
 
 

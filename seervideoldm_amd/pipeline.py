@@ -56,14 +56,16 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 @torch.no_grad()
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
                    latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
-                   plms: bool = False, stochastic: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
+                   plms: bool = False, stochastic: bool = False, editing: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
     empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
     optionally sampler = "ddim" (the default) or "plms").  `plms=True` builds the SlotSampler with plms=True, so that one captured
     step serves requests of either sampler; a request naming "plms" without it is a ValueError.  `stochastic=True` builds it with
     stochastic=True: a request may then carry seed, eta and temperature (SlotSampler.submit), and `noise` is optional when it has a
-    seed -- the start code is then drawn from the seed; in a queue started without it those keys are a ValueError.  The VAE encode
+    seed -- the start code is then drawn from the seed; in a queue started without it those keys are a ValueError.  `editing=True`
+    builds it with editing=True: a request may then carry mask with known (the given latents, SlotSampler.submit's x0; they need a
+    seed) and t_start; in a queue started without it those keys are a ValueError as well.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -89,14 +91,20 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
             if not sampler:
                 _, c_l, _, h_l, w_l = x0_emb.shape
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
-                                           max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic))
+                                           max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic,
+                                           **(dict(editing=True) if editing else {})))
             seeded = {k: r[k] for k in ("seed", "eta", "temperature") if k in r}
-            if seeded and not stochastic:
+            edit = {k: r[k] for k in ("mask", "known", "t_start") if r.get(k) is not None}
+            if edit and not editing:
+                raise ValueError(f"{sorted(edit)}: a request carries these only in a queue started with editing=True")
+            if "known" in edit:
+                edit["x0"] = edit.pop("known")
+            if seeded and not stochastic and not (editing and "mask" in edit and set(seeded) == {"seed"}):
                 raise ValueError(f"{sorted(seeded)}: a request carries these only in a queue started with stochastic=True")
             if r.get("noise") is None and seeded.get("seed") is None:
                 raise ValueError("a request needs `noise` (its start code) or, in a queue started with stochastic=True, a `seed`")
             yield dict(x_T=r.get("noise"), x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
-                       tag=r.get("tag"), method=method, **seeded)
+                       tag=r.get("tag"), method=method, **seeded, **edit)
 
     reqs = admitted()
     first = next(reqs, None)
@@ -108,6 +116,58 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
         x = vae.decode(z).sample
         x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
         yield tag, ops.clamp01_(x.float())
+
+
+def edit_t_enc(strength: float, entries: int) -> int:
+    """the level an edit of `strength` in (0, 1] starts from, out of a schedule of `entries`: max(1, int(strength * entries)), kept at
+    or below entries - 1 because stochastic_encode indexes the schedule tables with it (CompVis ddim.py:207-221)"""
+    if not 0. < float(strength) <= 1.:
+        raise ValueError(f"strength = {strength}: in (0, 1]")
+    if int(entries) < 2:
+        raise ValueError(f"a schedule of {entries} entries leaves no level to edit from")
+    return min(max(1, int(float(strength) * int(entries))), int(entries) - 1)
+
+
+@torch.no_grad()
+def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb: torch.Tensor, empty_emb: torch.Tensor, *,
+               cond_frames: int, ddim_steps: int = 30, scale: float = 7.5, strength: Optional[float] = None,
+               keep_mask: Optional[torch.Tensor] = None, seed, latent_generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """Edit an existing clip.  `video` [b, 3, F, H, W] in [-1, 1] is VAE-encoded in one call (as evaluate_batch does; the posterior
+    draw takes `latent_generator`); its first `cond_frames` latents condition the clip, the rest are the GIVEN latents.  Exactly one of
+      strength   in (0, 1] (SDEdit): the given latents are noised to level t_enc = edit_t_enc(strength, schedule entries) by
+                 sampler.stochastic_encode and denoised from there by sampler.decode(t_start=t_enc);
+      keep_mask  [b, 1, F - cond_frames, H/8, W/8], 1 where the given latents are kept: masked sampling from a seeded start code.
+    Every draw of the sampler comes from `seed` (an int, or one per row).  Returns the clips [b, 3, F - cond_frames, H, W] in [0, 1]
+    like generate_clips."""
+    if (strength is None) == (keep_mask is None):
+        raise ValueError("edit_clips: exactly one of `strength` and `keep_mask`")
+    b, _, F, H, W = video.shape
+    f1 = int(cond_frames)
+    if not 0 <= f1 < F:
+        raise ValueError(f"cond_frames = {cond_frames} of a video of {F} frames")
+    if strength is not None:
+        sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=0.0, verbose=False)
+        t_enc = edit_t_enc(strength, int(sampler.ddim_timesteps.shape[0]))
+    frames = video.permute(0, 2, 1, 3, 4).reshape(b * F, video.shape[1], H, W)                              # (b f) c h w
+    lat = vae.encode(frames).latent_dist.sample(generator=latent_generator) * 0.18215
+    lat = lat.reshape(b, F, *lat.shape[1:]).permute(0, 2, 1, 3, 4)                                          # b c f h w
+    x0_emb, given = (lat[:, :, :f1].contiguous() if f1 else None), lat[:, :, f1:].contiguous()
+    fstext_model.set_numframe(F)
+    c = fstext_model(context=text_emb)
+    uc = None if scale == 1.0 else empty_emb.unsqueeze(1).expand(-1, c.shape[1], -1, -1).contiguous()
+    if keep_mask is not None:
+        samples, _ = sampler.sample(unet=sunet, S=ddim_steps, conditioning=c, batch_size=b, shape=given.shape[1:], x0_emb=x0_emb,
+                                    verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0,
+                                    is_3d=True, seed=seed, mask=keep_mask, x0=given)
+    else:
+        noised = sampler.stochastic_encode(given, t_enc, seed=seed)
+        samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,
+                                 x0_emb=x0_emb, seed=seed)
+    n, ch, f, h, w = samples.shape
+    z = (samples.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
+    x = vae.decode(z).sample
+    x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
+    return ops.clamp01_(x.float())
 
 
 def concat_all_gather(t: torch.Tensor, process_group=None) -> torch.Tensor:

@@ -31,7 +31,12 @@ which draws a slot's noise itself from (the slot's seed, its schedule index, the
 its slot or its neighbours.  Each slot also has a seed pair and a temperature in device memory, and its coefficient rows carry the
 sigma of its own eta.  The promise above then holds for a seeded clip against DDIMSampler.sample(..., eta=, seed=, x_T=None).
 
-Out of scope: PLMS with noise, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
+With `editing=True` a request may carry a mask with given latents, and a start level (submit's `mask`, `x0`, `t_start`): the step
+opens with seer_slot_known_blend, which re-noises a slot's given latents to the level of the slot's next index from Philox stream 2 of
+its seed and blends them in where the slot's mask says so.  A slot whose mask is all zero -- every plain clip -- is not touched by it,
+so edited and plain clips share a queue, and a plain clip has the bits it has in a queue built without the keyword.
+
+Out of scope: PLMS with noise or with a mask, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
 """
 from __future__ import annotations
@@ -55,10 +60,12 @@ class SlotSampler:
     the two kernels that carry a sampler per slot, over three more static buffers, and is captured under a key of its own; with
     False everything is as it was before that keyword existed.  `stochastic=True` lets a request carry eta, seed and temperature
     (submit): the step's last kernel then draws the noise per slot, over two more static buffers, again under a key of its own; it
-    excludes plms=True (PLMS has no noise term)."""
+    excludes plms=True (PLMS has no noise term).  `editing=True` lets a request carry mask, x0 and t_start (submit): the step then
+    opens with the blend kernel, over per-slot mask, given-latent and seed buffers, under the key "slots-edit" ("slots-edit-rng" with
+    stochastic=True); it excludes plms=True as well."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
-                 model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False):
+                 model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False):
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -68,7 +75,9 @@ class SlotSampler:
             raise ValueError(f"shape {tuple(shape)}, cond_frames {cond_frames}, context_shape {tuple(context_shape)}, max_steps {max_steps}")
         if stochastic and plms:
             raise ValueError("stochastic=True with plms=True: PLMS is deterministic only, build one sampler for each")
-        if stochastic and C * Fp * h * w >= 1 << 31:
+        if editing and plms:
+            raise ValueError("editing=True with plms=True: PLMS with a mask is not built, build one sampler for each")
+        if (stochastic or editing) and C * Fp * h * w >= 1 << 31:
             raise ValueError(f"shape {tuple(shape)}: a seeded clip has fewer than 2^31 elements")
         if device is None:
             p0 = next(unet.parameters(), None) if hasattr(unet, "parameters") else None
@@ -95,9 +104,14 @@ class SlotSampler:
             self._ring = torch.zeros((n, 3, C, Fp, h, w), device=dev, dtype=f32)
             self._xprov = torch.zeros_like(self._x)
         self.stochastic = bool(stochastic)
-        if self.stochastic:
+        self.editing = bool(editing)
+        if self.stochastic or self.editing:
             self._seeds = torch.zeros((n, 2), device=dev, dtype=torch.int32)          # (lo, hi) words of a slot's uint64 seed
+        if self.stochastic:
             self._temp = torch.ones((n,), device=dev, dtype=f32)
+        if self.editing:
+            self._mask = torch.zeros((n, Fp, h, w), device=dev, dtype=f32)            # all zero: the blend leaves the slot alone
+            self._known = torch.zeros_like(self._x)
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
         self._tables: Dict[Tuple[int, float], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -130,7 +144,7 @@ class SlotSampler:
 
     @torch.no_grad()
     def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim", seed: Optional[int] = None,
-               temperature: float = 1.) -> int:
+               temperature: float = 1., mask=None, x0=None, t_start: Optional[int] = None) -> int:
         """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
         [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
         empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
@@ -142,14 +156,25 @@ class SlotSampler:
         A sampler built with stochastic=True also takes eta (the clip's tables then carry its sigma), seed (an unsigned 64-bit
         integer: the clip's noise is Philox stream 1 of it, and with x_T = None its start code is stream 0) and temperature; eta > 0
         needs a seed.  Without stochastic=True any of the three is a ValueError.
+        A sampler built with editing=True also takes mask ([1 or none, 1 or none, F_pred, h, w], values in [0, 1]) with x0 (the given
+        latents, shaped like x_T) -- in front of every step the slot's latent becomes q * mask + (1 - mask) * latent, q = x0 noised to
+        the step's level with Philox stream 2 of `seed`, which it therefore needs -- and t_start = k (1 .. the schedule's entries):
+        x_T is then the latent at level k, the slot's counter starts at k - 1 and the clip occupies its slot for k steps.  Without
+        editing=True any of the three is a ValueError.
         Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
         constructor's, eta != 0, a frame-sharded model, an unknown method and "plms" on a sampler built without it."""
         C, Fp, h, w = self.shape
         F, (L, D) = self.f1 + Fp, self.context_shape
+        if not self.editing and (mask is not None or x0 is not None or t_start is not None):
+            raise ValueError("mask / x0 / t_start need a sampler built with editing=True")
+        if (mask is None) != (x0 is None):
+            raise ValueError("mask and x0 go together: the mask says where the latent is given, x0 what it is there")
+        if mask is not None and seed is None:
+            raise ValueError("mask needs a seed: a slot re-noises the given latents from the clip's own seed, not from torch's generator")
         if not self.stochastic:
             if eta != 0:
                 raise ValueError(f"eta = {eta}: slots run the deterministic update only (eta = 0) unless built with stochastic=True")
-            if seed is not None or temperature != 1.:
+            if (seed is not None and mask is None) or temperature != 1.:
                 raise ValueError("seed / temperature need a sampler built with stochastic=True")
         elif eta < 0 or (eta != 0 and seed is None):
             raise ValueError(f"eta = {eta} needs a seed: a slot draws its noise from the clip's own seed, not from torch's generator")
@@ -161,8 +186,14 @@ class SlotSampler:
             raise ValueError("method = 'plms' needs a sampler built with plms=True")
         if getattr(self.unet, "_shard", None) is not None:
             raise ValueError("a frame-sharded model cannot run slots: detach it (parallel.attach) first")
-        if x_T is not None or seed is None:
+        if x_T is not None or seed is None or t_start is not None:
             x_T = self._clip(x_T, (C, Fp, h, w), "x_T")
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if tuple(mask.shape[-3:]) != (Fp, h, w) or any(d != 1 for d in mask.shape[:-3]) or mask.dim() > 5:
+                raise ValueError(f"mask {tuple(mask.shape)}: this sampler takes {(1, Fp, h, w)}, one mask for a clip's channels")
+            mask = mask.reshape(Fp, h, w).to(device=self.device, dtype=torch.float32)
+            x0 = self._clip(x0, (C, Fp, h, w), "x0")
         if self.f1:
             x0_emb = self._clip(x0_emb, (C, self.f1, h, w), "x0_emb")
         elif x0_emb is not None:
@@ -172,6 +203,9 @@ class SlotSampler:
         n = int(coef.shape[0])
         if n > self.max_steps:
             raise ValueError(f"S = {S} makes a schedule of {n} entries, this sampler was built for max_steps = {self.max_steps}")
+        start = n if t_start is None else int(t_start)
+        if not 1 <= start <= n:
+            raise ValueError(f"t_start = {t_start}: 1 .. {n}, the entries of the schedule of S = {S}")
         free = self.free_slots()
         if not free:
             raise RuntimeError(f"all {self.slots} slots are busy: step() until one finishes")
@@ -183,15 +217,19 @@ class SlotSampler:
             self.ops.philox_normal(int(seed), hip_ops.PHILOX_STREAM_START, 0, self._x[s].numel(), out=self._x[s])
         else:
             self._x[s].copy_(x_T)
-        if self.stochastic:
+        if self.stochastic or self.editing:
             self._seeds[s].copy_(hip_ops.seed_words([0 if seed is None else seed])[0])
+        if self.stochastic:
             self._temp[s:s + 1].fill_(float(temperature))
+        if mask is not None:
+            self._mask[s].copy_(mask)
+            self._known[s].copy_(x0)
         if self.f1:
             self._x0[s].copy_(x0_emb)
         self._context[s].copy_(uc)
         self._context[self.slots + s].copy_(c)
-        self._step[s, :1].fill_(n - 1)               # the one host-written counter of the clip: the kernels count it down
-        self._left[s] = n
+        self._step[s, :1].fill_(start - 1)           # the one host-written counter of the clip: the kernels count it down
+        self._left[s] = start
         if self.plms:
             # the slot's sampler: phase 1 opens a PLMS clip, phase 0 is DDIM; (valid, newest) = (0, 2), an empty ring.  The first PLMS
             # step is two steps of the slot
@@ -219,10 +257,13 @@ class SlotSampler:
                     self._x0[s].zero_()
                 if self.plms:
                     self._xprov[s].zero_()
+                if self.editing:
+                    self._mask[s].zero_()            # the next clip of this slot is a plain one until its submit says otherwise
+                    self._known[s].zero_()
         return done
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
-        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=]): fills free slots in request order (a
+        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=][, mask=, x0=, t_start=]): fills free slots in request order (a
         request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
         finishing order."""
         it, tags, more = iter(requests), {}, True
@@ -247,6 +288,8 @@ class SlotSampler:
             self.ops.slot_cfg_plms_step(eps, self._x, self._scale, self._coef, self._step, self._state, self._ring, self._xprov,
                                         cond_f=self.f1, x_prev=self._x, pred_x0=self._pred)
             return
+        if self.editing:
+            self.ops.slot_known_blend(self._x, self._mask, self._known, self._coef, self._step, self._seeds)
         self.ops.slot_step_begin(self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t)
         eps = model()
         if self.stochastic:
@@ -274,7 +317,9 @@ class SlotSampler:
         G = None
         if (unet.use_graph and self.ops is hip_ops and unet._ops_backend is hip_ops and self._x.is_cuda
                 and not self._capture_refused and not getattr(eng, "_graph_broken", False)):
-            key = ("slots-plms" if self.plms else "slots-rng" if self.stochastic else "slots", self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+            kind = "slots-plms" if self.plms else ("slots-edit-rng" if self.stochastic else "slots-edit") if self.editing else \
+                "slots-rng" if self.stochastic else "slots"
+            key = (kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)
