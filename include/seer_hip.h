@@ -510,6 +510,8 @@ int seer_cfg_ddim_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int3
  *                           cat([x0_emb, x], frames) repeated `reps` times (2 = the [uc, c] CFG pair), t_out[reps*b] =
  *                           t_table[step[0]], and step[1] = step[0];
  *   seer_cfg_ddim_step_dev  last kernel: seer_cfg_ddim_step with index = step[1]; then step[0] = index - 1.  x_prev may be x.
+ *                           A counter that ran past the schedule's end, step[1] < 0 (a replay after the chain's last step), still
+ *                           gives step[0] = index - 1, but reads no coefficient row and writes no element of x_prev or pred_x0.
  * No kernel reads and writes the same word, so replays of the captured step walk the schedule downwards on their own; the host
  * writes step[0] only to start a chain. */
 int seer_ddim_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, int32_t b, int32_t reps, int32_t C,
@@ -628,7 +630,9 @@ int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int3
  * for valid = 0 and order valid+1 otherwise, stores e into slot s = (newest+1)%3 (the oldest slot once all three are valid), and
  * one thread writes (min(valid+1, 3), s) into the pair of parity (index-1).  No kernel reads and writes the same word, so replays
  * walk the schedule and the ring with no host-written scalars; the host writes step[0] and the pair of the first index to start
- * a chain.  A pair outside those ranges is read as (0, 2).  x may alias x_prev. */
+ * a chain.  A pair outside those ranges is read as (0, 2).  x may alias x_prev.
+ * step[1] < 0, as in seer_cfg_ddim_step_dev: step[0] and the pair of parity (index-1) are written as above, no coefficient row is
+ * read and no element of x_prev, pred_x0 or the ring is written. */
 int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                            float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state, const float* x,
                            float* x_prev, float* pred_x0, void* stream);

@@ -18,7 +18,7 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libseer_hip.so"
-SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "rng.hip", "train.hip"]
+SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "train.hip"]
 ARCH = "gfx950"
 # per-source extra flags.  attention: keep the MFMA accumulators in VGPRs (gfx950's unified file allows it) -- the online
 # softmax touches S and O every key tile, and the default AGPR form costs ~220 v_accvgpr moves per tile per wave.

@@ -1,6 +1,6 @@
 // The counter-based generator on its own (seer_philox.h has the definitions): the raw words as a diagnostic, and the first n
 // normals of a clip's stream -- the start code of a seeded clip, and the noise tensor the two-stage comparison of the tests feeds to
-// seer_cfg_ddim_step.  One thread per Philox block of four; the step kernels in elementwise.hip draw per element through
+// seer_cfg_ddim_step.  One thread per Philox block of four; the step kernels in sampler_step.hip draw per element through
 // seer_philox::normal_at and get the same values.
 #include "seer_common.h"
 #include "seer_philox.h"

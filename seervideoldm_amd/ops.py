@@ -944,17 +944,64 @@ def nhwc_to_nchw_f32(x: torch.Tensor, N: int, H: int, W: int) -> torch.Tensor:
     return y
 
 
+# ---- the sampler step (csrc/sampler_step.hip): what its wrappers ask of their arguments -------------------------------------------
+def _req_update(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, *, cfg, cond_f: int, step: Optional[torch.Tensor] = None,
+                x_prev: Optional[torch.Tensor] = None):
+    """the arguments of every update: eps [2 rows or rows, C, F_total, h, w] next to x [rows, C, F_pred, h, w], the step words and
+    the output latent where the form has them -> (rows, C, F_total, h * w)"""
+    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
+    assert eps.is_contiguous() and x.is_contiguous()
+    if step is not None:
+        _req(step, torch.int32, "step")
+    if x_prev is not None:
+        assert x_prev.is_contiguous() and x_prev.shape == x.shape
+    rows, Cc, Fp, h, w = x.shape
+    Ft = eps.shape[2]
+    assert Ft == Fp + cond_f and eps.shape[0] == (2 * rows if cfg else rows)
+    return rows, Cc, Ft, h * w
+
+
+def _req_slot_tables(slots: int, coef: torch.Tensor, step: torch.Tensor, scale: Optional[torch.Tensor] = None) -> None:
+    """what a slot update reads per slot: coef fp32 [slots, nsched, 4], step int32 [slots, 2], scale fp32 [slots]"""
+    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
+    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
+    if scale is not None:
+        _req(scale, torch.float32, "scale")
+        assert scale.is_contiguous() and scale.numel() == slots
+
+
+def _req_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: torch.Tensor, step: torch.Tensor, reps: int,
+               sample: torch.Tensor, t_out: torch.Tensor, *, per_slot: bool) -> int:
+    """the arguments of a begin kernel; per_slot: a schedule row and a counter pair per row of x -> f1"""
+    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    rows, Cc, Fp, h, w = x.shape
+    f1 = 0 if x0_emb is None else x0_emb.shape[2]
+    if x0_emb is not None:
+        _req(x0_emb, torch.float32, "x0_emb")
+        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
+    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * rows, Cc, f1 + Fp, h, w)
+    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.numel() == reps * rows
+    if per_slot:
+        assert t_table.is_contiguous() and t_table.dim() == 2 and t_table.shape[0] == rows
+        assert step.is_contiguous() and tuple(step.shape) == (rows, 2) and t_out.is_contiguous()
+    else:
+        assert step.numel() >= 2
+    return f1
+
+
+def _req_pred(pred_x0: Optional[torch.Tensor], x: torch.Tensor) -> None:
+    if pred_x0 is not None:
+        _req(pred_x0, torch.float32, "pred_x0")
+        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
+
+
 def cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *, cfg: bool, scale: float,
                   cond_f: int, noise: Optional[torch.Tensor] = None, want_pred_x0=True):
     """eps [2b or b, C, F_total, h, w] fp32 ; x [b, C, F_pred, h, w] fp32 -> (x_prev, pred_x0)."""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
-    assert eps.is_contiguous() and x.is_contiguous()
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f)
     x_prev = torch.empty_like(x)
     pred = torch.empty_like(x) if want_pred_x0 else None
-    check(_lib.load().seer_cfg_ddim_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), index,
+    check(_lib.load().seer_cfg_ddim_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), index,
                                          _p(x), _p(noise), _p(x_prev), _p(pred), _stream()), "seer_cfg_ddim_step")
     return x_prev, pred
 
@@ -963,14 +1010,8 @@ def ddim_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: to
                     sample: torch.Tensor, t_out: torch.Tensor) -> None:
     """first kernel of a captured sampler step: sample[reps*b, C, f1+Fp, h, w] = cat([x0_emb, x], 2) x reps,
     t_out[:] = t_table[step[0]], step[1] = step[0] (include/seer_hip.h, seer_ddim_step_begin)"""
-    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    f1 = _req_begin(x0_emb, x, t_table, step, reps, sample, t_out, per_slot=False)
     b, Cc, Fp, h, w = x.shape
-    f1 = 0 if x0_emb is None else x0_emb.shape[2]
-    if x0_emb is not None:
-        _req(x0_emb, torch.float32, "x0_emb")
-        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
-    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * b, Cc, f1 + Fp, h, w) and step.numel() >= 2
-    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.numel() == reps * b
     check(_lib.load().seer_ddim_step_begin(_p(x0_emb), _p(x), b, reps, Cc, f1, Fp, h * w, _p(t_table), _p(step), _p(sample),
                                            _p(t_out), _stream()), "seer_ddim_step_begin")
 
@@ -978,12 +1019,8 @@ def ddim_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: to
 def cfg_ddim_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *, cfg: bool, scale: float,
                       cond_f: int, x_prev: torch.Tensor, pred_x0: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None):
     """last kernel of a captured sampler step: cfg_ddim_step with index = step[1], then step[0] = index - 1; x_prev may be x"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
-    check(_lib.load().seer_cfg_ddim_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), _p(step), _p(x),
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
+    check(_lib.load().seer_cfg_ddim_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step), _p(x),
                                              _p(noise), _p(x_prev), _p(pred_x0), _stream()), "seer_cfg_ddim_step_dev")
 
 
@@ -991,16 +1028,8 @@ def slot_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: to
                     sample: torch.Tensor, t_out: torch.Tensor) -> None:
     """ddim_step_begin over slots (x [slots, C, Fp, h, w]): t_table int64 [slots, nsched] and step int32 [slots, 2] hold a schedule
     and a counter pair per slot; row rep * slots + s of sample / t_out is slot s (include/seer_hip.h, seer_slot_step_begin)"""
-    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    f1 = _req_begin(x0_emb, x, t_table, step, reps, sample, t_out, per_slot=True)
     slots, Cc, Fp, h, w = x.shape
-    f1 = 0 if x0_emb is None else x0_emb.shape[2]
-    if x0_emb is not None:
-        _req(x0_emb, torch.float32, "x0_emb")
-        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
-    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * slots, Cc, f1 + Fp, h, w)
-    assert t_table.is_contiguous() and t_table.dim() == 2 and t_table.shape[0] == slots
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
-    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.is_contiguous() and t_out.numel() == reps * slots
     check(_lib.load().seer_slot_step_begin(_p(x0_emb), _p(x), slots, reps, Cc, f1, Fp, h * w, _p(t_table), t_table.shape[1],
                                            _p(step), _p(sample), _p(t_out), _stream()), "seer_slot_step_begin")
 
@@ -1010,18 +1039,10 @@ def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, 
     """cfg_ddim_step_dev over slots, CFG on, eta = 0: slot s updates x[s] from eps rows s and slots + s with scale[s] and row
     step[s, 1] of coef[s] (fp32 [slots, nsched, 4]), then step[s, 0] = that index - 1; a slot whose index is negative is left
     untouched.  x_prev may be x (include/seer_hip.h, seer_slot_cfg_ddim_step)"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
-    _req(scale, torch.float32, "scale")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
-    slots, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
-    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
-    if pred_x0 is not None:
-        _req(pred_x0, torch.float32, "pred_x0")
-        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
-    check(_lib.load().seer_slot_cfg_ddim_step(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+    slots, Cc, Ft, HW = _req_update(eps, x, coef, cfg=True, cond_f=cond_f, step=step, x_prev=x_prev)
+    _req_slot_tables(slots, coef, step, scale)
+    _req_pred(pred_x0, x)
+    check(_lib.load().seer_slot_cfg_ddim_step(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
                                               _p(x), _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
 
 
@@ -1069,17 +1090,13 @@ def cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, in
                       want_pred_x0=True):
     """cfg_ddim_step with seeded noise: seeds int32 [b, 2] (seed_words) and temperature in the place of the noise tensor; row bi gets
     sigma * (temperature * normal e of (seeds[bi], stream 1, index)).  x_prev may be x.  -> (x_prev, pred_x0)"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
-    assert eps.is_contiguous() and x.is_contiguous()
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
-    _req_seeds(seeds, b)
     if x_prev is None:
         x_prev = torch.empty_like(x)
-    assert x_prev.is_contiguous() and x_prev.shape == x.shape and x_prev.dtype == torch.float32
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, x_prev=x_prev)
+    assert x_prev.dtype == torch.float32
+    _req_seeds(seeds, b)
     pred = torch.empty_like(x) if want_pred_x0 else None
-    check(_lib.load().seer_cfg_ddim_step_rng(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), int(index), _p(x),
+    check(_lib.load().seer_cfg_ddim_step_rng(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), _p(x),
                                              _p(seeds), float(temperature), _p(x_prev), _p(pred), _stream()), "seer_cfg_ddim_step_rng")
     return x_prev, pred
 
@@ -1088,13 +1105,10 @@ def cfg_ddim_step_rng_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor
                           cfg: bool, scale: float, cond_f: int, temperature: float, x_prev: torch.Tensor,
                           pred_x0: Optional[torch.Tensor]) -> None:
     """last kernel of a captured seeded step: cfg_ddim_step_rng with index = step[1], then step[0] = index - 1; x_prev may be x"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b) and step.numel() >= 2
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
+    assert step.numel() >= 2
     _req_seeds(seeds, b)
-    check(_lib.load().seer_cfg_ddim_step_rng_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), _p(step), _p(x),
+    check(_lib.load().seer_cfg_ddim_step_rng_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step), _p(x),
                                                  _p(seeds), float(temperature), _p(x_prev), _p(pred_x0), _stream()),
           "seer_cfg_ddim_step_rng_dev")
 
@@ -1104,20 +1118,13 @@ def slot_cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tens
                            pred_x0: Optional[torch.Tensor]) -> None:
     """slot_cfg_ddim_step with seeded noise: seeds int32 [slots, 2] and temperature fp32 [slots] in device memory; a slot whose coef
     row has sigma == 0 runs the deterministic update (include/seer_hip.h, seer_slot_cfg_ddim_step_rng)"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
-    _req(scale, torch.float32, "scale"); _req(temperature, torch.float32, "temperature")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
-    slots, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
-    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
+    slots, Cc, Ft, HW = _req_update(eps, x, coef, cfg=True, cond_f=cond_f, step=step, x_prev=x_prev)
+    _req_slot_tables(slots, coef, step, scale)
+    _req(temperature, torch.float32, "temperature")
     assert temperature.is_contiguous() and temperature.numel() == slots
     _req_seeds(seeds, slots)
-    if pred_x0 is not None:
-        _req(pred_x0, torch.float32, "pred_x0")
-        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
-    check(_lib.load().seer_slot_cfg_ddim_step_rng(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+    _req_pred(pred_x0, x)
+    check(_lib.load().seer_slot_cfg_ddim_step_rng(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
                                                   _p(x), _p(seeds), _p(temperature), _p(x_prev), _p(pred_x0), _stream()),
           "seer_slot_cfg_ddim_step_rng")
 
@@ -1188,8 +1195,7 @@ def slot_known_blend(x: torch.Tensor, mask: torch.Tensor, known: torch.Tensor, c
     _req_known(x, mask, known)
     _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
     slots, Cc, Fp, h, w = x.shape
-    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
+    _req_slot_tables(slots, coef, step)
     _req_seeds(seeds, slots)
     check(_lib.load().seer_slot_known_blend(_p(x), _p(mask), _p(known), slots, Cc, Fp, h * w, _p(coef), coef.shape[1], _p(step),
                                             _p(seeds), _stream()), "seer_slot_known_blend")
@@ -1212,16 +1218,8 @@ def slot_plms_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, x_prov
     """slot_step_begin with a sampler per slot: state int32 [slots, 8] holds (phase, valid, newest) of the next step in words 0..2
     and receives them in words 4..6; a slot in phase 2 (the second evaluation of a PLMS clip's first step) takes its rows from
     x_prov and the next timestep of its table (include/seer_hip.h, seer_slot_plms_step_begin)"""
-    _req(x, torch.float32, "x"); _req(t_table, torch.int64, "t_table"); _req(step, torch.int32, "step")
+    f1 = _req_begin(x0_emb, x, t_table, step, reps, sample, t_out, per_slot=True)
     slots, Cc, Fp, h, w = x.shape
-    f1 = 0 if x0_emb is None else x0_emb.shape[2]
-    if x0_emb is not None:
-        _req(x0_emb, torch.float32, "x0_emb")
-        assert x0_emb.is_contiguous() and x0_emb.shape[:2] == x.shape[:2] and x0_emb.shape[3:] == x.shape[3:]
-    assert x.is_contiguous() and sample.is_contiguous() and sample.shape == (reps * slots, Cc, f1 + Fp, h, w)
-    assert t_table.is_contiguous() and t_table.dim() == 2 and t_table.shape[0] == slots
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2)
-    assert sample.dtype == torch.float32 and t_out.dtype == torch.int64 and t_out.is_contiguous() and t_out.numel() == reps * slots
     _req_slot_plms(x, state, x_prov)
     check(_lib.load().seer_slot_plms_step_begin(_p(x0_emb), _p(x), _p(x_prov), slots, reps, Cc, f1, Fp, h * w, _p(t_table),
                                                 t_table.shape[1], _p(step), _p(state), _p(sample), _p(t_out), _stream()),
@@ -1235,19 +1233,11 @@ def slot_cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, 
     provisional update of a PLMS clip's first step into x_prov[s] (1), the first step's final update (2) or a later PLMS step of
     order valid + 1 over ring[s] (3), and writes the slot's next state words.  ring fp32 [slots, 3, *x.shape[1:]]; x_prev may be
     x, x_prov may not (include/seer_hip.h, seer_slot_cfg_plms_step)"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
-    _req(scale, torch.float32, "scale")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
-    slots, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == 2 * slots
-    assert coef.is_contiguous() and coef.dim() == 3 and coef.shape[0] == slots and coef.shape[2] == 4
-    assert step.is_contiguous() and tuple(step.shape) == (slots, 2) and scale.is_contiguous() and scale.numel() == slots
+    slots, Cc, Ft, HW = _req_update(eps, x, coef, cfg=True, cond_f=cond_f, step=step, x_prev=x_prev)
+    _req_slot_tables(slots, coef, step, scale)
     _req_slot_plms(x, state, x_prov, ring)
-    if pred_x0 is not None:
-        _req(pred_x0, torch.float32, "pred_x0")
-        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
-    check(_lib.load().seer_slot_cfg_plms_step(_p(eps), slots, Cc, Ft, cond_f, h * w, _p(scale), _p(coef), coef.shape[1], _p(step),
+    _req_pred(pred_x0, x)
+    check(_lib.load().seer_slot_cfg_plms_step(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
                                               _p(state), _p(ring), _p(x), _p(x_prov), _p(x_prev), _p(pred_x0), _stream()),
           "seer_slot_cfg_plms_step")
 
@@ -1258,11 +1248,7 @@ def cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index:
     """eps [2b or b, C, F_total, h, w] fp32 ; x [b, C, F_pred, h, w] fp32 ; history = earlier e, newest first (order 1, 2: one,
     3: two, 4: three) -> (x_prev, pred_x0, e).  e is this evaluation's CFG-combined eps (None for order 1, which keeps none);
     x_prev may be x and e_out a history tensor (include/seer_hip.h, seer_cfg_plms_step)."""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
-    assert eps.is_contiguous() and x.is_contiguous()
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f)
     order = int(order)
     need = (0, 1, 1, 2, 3)[order] if 0 <= order <= 4 else None
     assert need is not None, f"order {order}: 0..4"
@@ -1280,7 +1266,7 @@ def cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index:
         if tt is not None:
             _req(tt, torch.float32, name)
             assert tt.is_contiguous() and tt.shape == x.shape
-    check(_lib.load().seer_cfg_plms_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), int(index), order,
+    check(_lib.load().seer_cfg_plms_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), order,
                                          _p(x), hp[0], hp[1], hp[2], _p(x_prev), _p(pred), _p(e), _stream()), "seer_cfg_plms_step")
     return x_prev, pred, (None if order == 1 else e)
 
@@ -1290,17 +1276,11 @@ def cfg_plms_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, st
                       pred_x0: Optional[torch.Tensor]) -> None:
     """last kernel of a captured PLMS step: cfg_plms_step with index = step[1] and the order / history taken from the 3-slot ring
     (ring [3, *x.shape], ring_state int32[4]: (valid, newest) per index parity); step[0] = index - 1; x_prev may be x"""
-    _req(eps, torch.float32, "eps"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef"); _req(step, torch.int32, "step")
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
     _req(ring, torch.float32, "ring"); _req(ring_state, torch.int32, "ring_state")
-    assert eps.is_contiguous() and x.is_contiguous() and x_prev.is_contiguous() and x_prev.shape == x.shape
     assert ring.is_contiguous() and tuple(ring.shape) == (3, *x.shape) and ring_state.numel() >= 4 and step.numel() >= 2
-    if pred_x0 is not None:
-        _req(pred_x0, torch.float32, "pred_x0")
-        assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
-    b, Cc, Fp, h, w = x.shape
-    Ft = eps.shape[2]
-    assert Ft == Fp + cond_f and eps.shape[0] == (2 * b if cfg else b)
-    check(_lib.load().seer_cfg_plms_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, h * w, float(scale), _p(coef), _p(step),
+    _req_pred(pred_x0, x)
+    check(_lib.load().seer_cfg_plms_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step),
                                              _p(ring), _p(ring_state), _p(x), _p(x_prev), _p(pred_x0), _stream()),
           "seer_cfg_plms_step_dev")
 

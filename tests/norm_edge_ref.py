@@ -1,6 +1,6 @@
 """References, emulations and exact constructions for csrc/norm.hip (the GroupNorm entry points, seer_layernorm, seer_softmax_rows) and
-csrc/elementwise.hip (rotary, timestep embedding, seer_linear_smallm, seer_conv_in / seer_conv_out, cast and layout, the DDIM step
-boundary, seer_conv1x1_nchw_f32, seer_clamp01, seer_gaussian_sample).  Plain torch in float64 on whatever device the operands live; no
+csrc/elementwise.hip (rotary, timestep embedding, seer_linear_smallm, seer_conv_in / seer_conv_out, cast and layout,
+seer_conv1x1_nchw_f32, seer_clamp01, seer_gaussian_sample) with the DDIM step boundary of csrc/sampler_step.hip.  Plain torch in float64 on whatever device the operands live; no
 dependency on the library and nothing here comes from a kernel's output.  Used by tests/test_gpu_norm_matrix.py and
 tests/test_gpu_edge_matrix.py (the kernels) and tests/test_norm_edge_ref_cpu.py (the preconditions and the mutation table, no GPU).
 

@@ -1,6 +1,6 @@
-"""csrc/elementwise.hip -- rotary, timestep embedding, seer_linear_smallm, seer_conv_in / seer_conv_out, cast and layout, the DDIM step
-boundary (seer_ddim_step_begin, seer_cfg_ddim_step, seer_cfg_ddim_step_dev), seer_conv1x1_nchw_f32, seer_clamp01 and
-seer_gaussian_sample -- tested exactly, per owner and at their edges: the second half of part 5 of the series (the first is
+"""csrc/elementwise.hip -- rotary, timestep embedding, seer_linear_smallm, seer_conv_in / seer_conv_out, cast and layout,
+seer_conv1x1_nchw_f32, seer_clamp01 and seer_gaussian_sample -- and the DDIM step boundary of csrc/sampler_step.hip
+(seer_ddim_step_begin, seer_cfg_ddim_step, seer_cfg_ddim_step_dev), tested exactly, per owner and at their edges: the second half of part 5 of the series (the first is
 test_gpu_norm_matrix.py).  The two PLMS entry points are left to test_gpu_plms.py, which holds them to 1e-6 per order.
 
 0. Pure data movement bit for bit into guarded arenas: layout conversion, cast (ties, +-0, +-inf, NaN, fp16 overflow, subnormals)
