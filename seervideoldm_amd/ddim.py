@@ -23,13 +23,11 @@ noise does not depend on the batch it is in.
 """
 from __future__ import annotations
 
-from types import SimpleNamespace
-from typing import Optional
-
 import numpy as np
 import torch
 
 from . import ops
+from .step_graph import capture_engine, capture_step, changed, refresh      # capture_step: slots.py and callers import it from here
 
 
 def _betas(n_train: int, beta_first: float, beta_last: float) -> np.ndarray:
@@ -60,6 +58,8 @@ class DDIMSampler(object):
         # p_sample_ddim under graph replay hands out its static latent buffers instead of copies of them: the next step
         # overwrites what the previous one returned.  ddim_sampling sets it for its own loop (and copies what it keeps).
         self.static_step_outputs = False
+        self._capture_refused = False       # set when a capture of this sampler's step fails: it steps launch by launch from then on
+        self._kept = {}                     # step_graph.changed's record of the (c, uc) pair behind _cfg_context
 
     def register_buffer(self, name, attr):
         setattr(self, name, attr)
@@ -100,84 +100,87 @@ class DDIMSampler(object):
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, null_cond_prob=None, is_3d=False,
                **kwargs):
-        if conditioning is not None and not isinstance(conditioning, dict):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
         seeds = _row_seeds(kwargs.get("seed"), batch_size)
-        if seeds is not None and getattr(unet, "_shard", None) is not None:
-            raise ValueError("seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)")
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        if is_3d:
-            C, Fr, H, W = shape
-            size = (batch_size, C, Fr, H, W)
-        else:
-            raise NotImplementedError("the Seer hot path is 5-D (is_3d=True, ddim_sampling_utils.py:36)")
+        size = self._sample_size(S, batch_size, shape, conditioning, eta, verbose, is_3d)
         return self.ddim_sampling(unet, conditioning, size, x0_emb=x0_emb, is_3d=is_3d, callback=callback,
                                   img_callback=img_callback, cond_frames=cond_frames, temperature=temperature,
                                   noise_dropout=noise_dropout, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning, seeds=seeds, mask=mask, x0=x0)
 
+    def _sample_size(self, S, batch_size, shape, conditioning, eta, verbose, is_3d):
+        """how every sample() starts (ddim_video.py:84-98): the conditioning warning, the schedule of S steps, the latent's 5-D size"""
+        if conditioning is not None and not isinstance(conditioning, dict):
+            if conditioning.shape[0] != batch_size:
+                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
+        if not is_3d:
+            raise NotImplementedError("the Seer hot path is 5-D (is_3d=True, ddim_sampling_utils.py:36)")
+        C, Fr, H, W = shape
+        return (batch_size, C, Fr, H, W)
+
+    def _chain_start(self, unet, shape, x_T, x0_emb):
+        """the latent a chain starts from -- x_T, or torch.randn(shape) -- in fp32 on the sampler's device, and x0_emb on that device.
+        One clip sharded over several ranks (parallel.attach): every rank must denoise the SAME latent, so the start code and the
+        conditioning latents (a per-rank posterior sample) come from rank 0, like any per-step noise."""
+        img = torch.randn(shape, device=self.device) if x_T is None else x_T.to(device=self.device, dtype=torch.float32)
+        img = _from_rank0(unet, img)
+        if x0_emb is not None:
+            x0_emb = _from_rank0(unet, x0_emb.to(self.device))
+        return img, x0_emb
+
     @torch.no_grad()
     def ddim_sampling(self, unet, cond, shape, is_3d, x0_emb=None, cond_frames=0, x_T=None, callback=None,
                       img_callback=None, log_every_t=100, temperature=1., noise_dropout=0.,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, seeds=None, mask=None, x0=None,
-                      **kwargs):
+                      t_start=None, **kwargs):
         """`seeds`: None, or one uint64 per batch row (sample's `seed`): the start code (when x_T is None) and the noise of every step
         then come from the rows' Philox streams, nothing from torch's generator.  `mask` (broadcastable to [b, 1, F_pred, h, w], values
         in [0, 1]) with `x0` [b, C, F_pred, h, w]: in front of every step the latent becomes q * mask + (1 - mask) * latent, q = x0
-        noised to that step's level (CompVis ddim.py:144-147); the final latent is not blended again."""
-        device = self.device
+        noised to that step's level (CompVis ddim.py:144-147); the final latent is not blended again.  `t_start` (decode): x_T is the
+        latent at that level of the schedule, and the chain runs the indices t_start - 1 ... 0 only."""
         b = shape[0]
+        if seeds is not None:
+            _refuse_sharded(unet, "seed")
         known = self._known_pair(unet, mask, x0, shape)
         if seeds is not None:
             seeds = list(seeds)
             if len(seeds) != b:
                 raise ValueError(f"seeds: {len(seeds)} for a batch of {b}")
             if x_T is None:
-                x_T = torch.empty(shape, device=device, dtype=torch.float32)
+                x_T = torch.empty(shape, device=self.device, dtype=torch.float32)
                 for row, s in zip(x_T, seeds):           # a row's start code: stream 0 of its own seed
                     self.ops.philox_normal(s, ops.PHILOX_STREAM_START, 0, row.numel(), out=row)
-            seeds = ops.seed_words(seeds).to(device)
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
-        # one clip sharded over several ranks (parallel.attach): every rank must denoise the SAME latent.  The start code,
-        # the conditioning latents (a per-rank posterior sample) and any per-step noise come from rank 0.
-        img = _from_rank0(unet, img)
-        if x0_emb is not None:
-            x0_emb = _from_rank0(unet, x0_emb.to(device))
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
-        img = self._run_chain(unet, img, cond, self.ddim_timesteps.shape[0], is_3d=is_3d, x0_emb=x0_emb, cond_frames=cond_frames,
-                              temperature=temperature, noise_dropout=noise_dropout, scale=unconditional_guidance_scale,
-                              uc=unconditional_conditioning, seeds=seeds, known=known, callback=callback, img_callback=img_callback,
-                              log_every_t=log_every_t, intermediates=intermediates)
-        return img, intermediates
+            seeds = ops.seed_words(seeds).to(self.device)
+        img, x0_emb = self._chain_start(unet, shape, x_T, x0_emb)
+        step = lambda img, index: self.p_sample_ddim(
+            unet, img, cond, self._t_table[index].expand(b), index=index, is_3d=is_3d, x0_emb=x0_emb, cond_frames=cond_frames,
+            temperature=temperature, noise_dropout=noise_dropout, unconditional_guidance_scale=unconditional_guidance_scale,
+            unconditional_conditioning=unconditional_conditioning, seeds=seeds, known=known)
+        return self._run_chain(img, self.ddim_timesteps.shape[0] if t_start is None else int(t_start), step, callback, img_callback,
+                               log_every_t)
 
-    def _run_chain(self, unet, img, cond, n_steps, *, is_3d=True, x0_emb=None, cond_frames=0, temperature=1., noise_dropout=0., scale=1.,
-                   uc=None, seeds=None, known=None, callback=None, img_callback=None, log_every_t=100, intermediates=None):
-        """schedule indices n_steps - 1 ... 0 through p_sample_ddim, starting from `img`; returns a copy of the last latent"""
-        b = img.shape[0]
+    def _run_chain(self, img, n_steps, step, callback=None, img_callback=None, log_every_t=100):
+        """The loop of a sample: schedule indices n_steps - 1 ... 0 through `step(img, index) -> (img, pred_x0)`, starting from
+        `img`, with the reference's callbacks and logged intermediates; returns (a copy of the last latent, the intermediates)."""
         total_steps = self.ddim_timesteps.shape[0]
+        intermediates = {"x_inter": [img], "pred_x0": [img]}
         # inside this loop a captured step may hand out its static buffers (nothing here keeps a step's output past the next
         # step without copying it)
         static_before, self.static_step_outputs = self.static_step_outputs, True
         try:
             for i, index in enumerate(reversed(range(n_steps))):
-                ts = self._t_table[index].expand(b)
-                img, pred_x0 = self.p_sample_ddim(unet, img, cond, ts, index=index, is_3d=is_3d, x0_emb=x0_emb,
-                                                  cond_frames=cond_frames, temperature=temperature,
-                                                  noise_dropout=noise_dropout,
-                                                  unconditional_guidance_scale=scale,
-                                                  unconditional_conditioning=uc, seeds=seeds, known=known)
+                img, pred_x0 = step(img, index)
                 if callback:
                     callback(i)
                 if img_callback:
                     img_callback(pred_x0.clone(), i)
-                if intermediates is not None and (index % log_every_t == 0 or index == total_steps - 1):
+                if index % log_every_t == 0 or index == total_steps - 1:
                     intermediates["x_inter"].append(img.clone())
                     intermediates["pred_x0"].append(pred_x0.clone())
         finally:
             self.static_step_outputs = static_before
-        return img.clone()
+        return img.clone(), intermediates
 
     def _known_pair(self, unet, mask, x0, shape):
         """sample's `mask` / `x0` -> None, or (mask fp32 [b, F_pred, h, w], x0 fp32 [b, C, F_pred, h, w]) on the sampler's device, made
@@ -186,8 +189,7 @@ class DDIMSampler(object):
             return None
         if mask is None or x0 is None:
             raise ValueError("mask and x0 go together: the mask says where the latent is given, x0 what it is there")
-        if getattr(unet, "_shard", None) is not None:
-            raise ValueError("mask: a frame-sharded model cannot blend given latents (detach it, parallel.attach)")
+        _refuse_sharded(unet, "mask")
         b, Cc, Fp, h, w = shape
         mask = torch.as_tensor(mask)
         if mask.dim() > 5 or (mask.dim() == 5 and mask.shape[1] != 1):
@@ -234,18 +236,10 @@ class DDIMSampler(object):
         n = int(self.ddim_timesteps.shape[0])
         if not 1 <= int(t_start) <= n:
             raise ValueError(f"t_start = {t_start}: 1 .. {n}, the entries of the current schedule")
-        b = x_latent.shape[0]
-        seeds = _row_seeds(seed, b)
-        if seeds is not None and getattr(unet, "_shard", None) is not None:
-            raise ValueError("seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)")
-        known = self._known_pair(unet, mask, x0, tuple(x_latent.shape))
-        if seeds is not None:
-            seeds = ops.seed_words(seeds).to(self.device)
-        img = _from_rank0(unet, x_latent.to(device=self.device, dtype=torch.float32))
-        if x0_emb is not None:
-            x0_emb = _from_rank0(unet, x0_emb.to(self.device))
-        return self._run_chain(unet, img, cond, int(t_start), x0_emb=x0_emb, cond_frames=cond_frames, temperature=temperature,
-                               scale=unconditional_guidance_scale, uc=unconditional_conditioning, seeds=seeds, known=known)
+        return self.ddim_sampling(unet, cond, tuple(x_latent.shape), True, x0_emb=x0_emb, cond_frames=cond_frames, x_T=x_latent,
+                                  temperature=temperature, unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning,
+                                  seeds=_row_seeds(seed, x_latent.shape[0]), mask=mask, x0=x0, t_start=t_start)[0]
 
     @torch.no_grad()
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
@@ -265,12 +259,12 @@ class DDIMSampler(object):
         if known is not None and seeds is None:
             x = self.ops.known_blend(x.clone(), known[0], known[1], self.ddim_coef, index, noise=torch.randn(x.shape, device=x.device))
             known = None
-        # the whole step -- input assembly, CFG-batched UNet, CFG combine, DDIM update -- as ONE replayed hipGraph when the model
-        # replays graphs anyway (unet.use_graph) and the step is the one ddim_sample drives: batched CFG or none, eta = 0, and
-        # t = the schedule's own timestep of `index` (recognised by its address: a view of the device timestep table)
-        if ((sigma == 0. or seeds is not None) and getattr(unet, "use_graph", False) and x.is_cuda and self.ops is ops and (uc is None or scale == 1. or uc.shape[2] == c.shape[2])
-                and torch.is_tensor(t) and t.dtype == torch.long and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
-            plain = uc is None or scale == 1.
+        # the whole step -- input assembly, CFG-batched UNet, CFG combine, DDIM update -- as ONE replayed hipGraph when the step is the
+        # one ddim_sample drives: batched CFG or none, eta = 0 or a seed, and t = the schedule's own timestep of `index` (recognised by
+        # its address: a view of the device timestep table).  Whether the model's steps may be captured at all is _step_graph's question.
+        plain = uc is None or scale == 1.
+        if ((sigma == 0. or seeds is not None) and (plain or uc.shape[2] == c.shape[2]) and torch.is_tensor(t) and t.dtype == torch.long
+                and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
             done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale,
                                     seeds=seeds, temperature=temperature, known=known)
             if done is not None:
@@ -286,9 +280,8 @@ class DDIMSampler(object):
             noise = torch.randn(x.shape, device=x.device) * temperature
             if sigma != 0.:
                 noise = _from_rank0(unet, noise)
-        x_prev, pred_x0 = self.ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale,
-                                                 cond_f=cond_f, noise=noise if sigma != 0. else None)
-        return x_prev, pred_x0
+        return self.ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale, cond_f=cond_f,
+                                      noise=noise if sigma != 0. else None)
 
     def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale):
         """the model call of p_sample_ddim (ddim_video.py:187-207): x0_emb in front of x along frames, batched CFG when uc has c's
@@ -304,12 +297,7 @@ class DDIMSampler(object):
             eps = unet(x_cat, t, c)
             cfg = False
         elif uc.shape[2] == c.shape[2]:
-            cached = getattr(self, "_cfg_inputs", None)
-            if (cached is None or cached[0] is not c or cached[1] is not uc or cached[3] != (c._version, uc._version)):
-                # one [uc, c] tensor per (c, uc) pair: its identity keys the UNet's cross-attention K/V cache and graph
-                cached = (c, uc, torch.cat([uc, c]).contiguous(), (c._version, uc._version))
-                self._cfg_inputs = cached
-            eps = unet(torch.cat([x_cat] * 2), torch.cat([t] * 2), cached[2], cond_frame=cond_frames)
+            eps = unet(torch.cat([x_cat] * 2), torch.cat([t] * 2), self._cfg_context(c, uc), cond_frame=cond_frames)
             cfg = True
         else:
             e_uc = unet(x_cat, t, uc, cond_frame=cond_frames)
@@ -326,23 +314,14 @@ class DDIMSampler(object):
         take the path (sharded model, capture refused): the caller then runs the launches one by one.  With `seeds` the last kernel
         is seer_cfg_ddim_step_rng_dev and the step draws nothing, at any eta.  With `known` (seeded only) seer_known_blend is the
         step's first node, over static copies of the mask and the given latents."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, rng=None if seeds is None else float(temperature),
-                             masked=known is not None)
+        kind = "step" if seeds is None else "step-rng" if known is None else "step-mask"
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, kind, None if seeds is None else float(temperature))
         if G is None:
             return None
         if seeds is not None:
-            k = (seeds.data_ptr(), seeds._version)
-            if G["seeds_key"] != k or G["seeds_ref"] is not seeds:
-                G["seeds"].copy_(seeds)
-                G["seeds_key"], G["seeds_ref"] = k, seeds
+            refresh(G["kept"], "seeds", (seeds,), (G["seeds"],))
         if known is not None:
-            k = tuple((t.data_ptr(), t._version) for t in known)
-            if G["known_key"] != k or G["known_ref"][0] is not known[0] or G["known_ref"][1] is not known[1]:
-                G["mask"].copy_(known[0])
-                G["known"].copy_(known[1])
-                G["known_key"], G["known_ref"] = k, known
-        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
-            G["x"].copy_(x)
+            refresh(G["kept"], "known", known, (G["mask"], G["known"]))
         if G["expect"] != index:
             G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
         return self._replay_step(G, x, index, draw=seeds is None)
@@ -356,41 +335,23 @@ class DDIMSampler(object):
             return G["x"], G["pred"]
         return G["x"].clone(), G["pred"].clone()
 
-    # what a subclass changes in the captured step: the first word of its graph-cache key, the static buffers beyond the DDIM
-    # step's, and the step's last kernel
-    _GRAPH_KIND = "step"
+    def _cfg_context(self, c, uc):
+        """the batched-CFG context [uc, c]: ONE tensor per (c, uc) pair, because its identity keys the UNet's cross-attention K|V cache
+        and graph.  Renewed when the caller brings another pair, as step_graph.refresh would: by a fresh concatenation, not a copy."""
+        if changed(self._kept, "cfg", (c, uc)):
+            self._cfg_cat = torch.cat([uc, c]).contiguous()
+        return self._cfg_cat
 
-    def _graph_buffers(self, x):
-        return {}
-
-    def _graph_update(self, G, eps, cfg, scale, cond_f):
-        ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], cfg=cfg, scale=scale, cond_f=cond_f, x_prev=G["x"],
-                              pred_x0=G["pred"])
-
-    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, rng=None, masked=False):
-        """the captured step of this shape / CFG / scale (captured on first use) with its read-by-address inputs refreshed; None
-        when the step cannot be captured.  rng = the temperature of a seeded step (None: the sampler's own step): a kind of its own in
-        the key -- "step-rng" -- with the temperature, which like the guidance scale is an argument of the last kernel and frozen into
-        the capture; the seeds live in a static buffer and are no part of the key.  masked (with rng only): the kind "step-mask", the
-        seeded step with seer_known_blend in front; mask and given latents are static buffers too."""
-        from .unet import SeerUNet
-        if not isinstance(unet, SeerUNet) or unet._shard is not None or unet._ops_backend is not ops \
-                or unet.config.center_input_sample or getattr(self, "_step_graph_broken", False):
-            return None
-        if unet._engine is None or unet._engine.device != x.device:
-            unet.prepare()
-        eng = unet._engine
-        if getattr(eng, "_graph_broken", False):
+    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, kind, temperature=None):
+        """the captured step of this kind / shape / CFG / scale (captured on first use) with x and its read-by-address inputs
+        refreshed; None when the step cannot be captured.  `kind` is the key's first word and an entry of STEP_KINDS.  A seeded kind
+        comes with its temperature, the key's last field: like the guidance scale it is an argument of the last kernel and frozen
+        into the capture; seeds, mask and given latents live in static buffers and are no part of the key."""
+        eng = None if self._capture_refused else capture_engine(unet, self.ops, x.device)
+        if eng is None:
             return None
         cfg = uc is not None
-        if cfg:
-            cached = getattr(self, "_cfg_inputs", None)
-            if cached is None or cached[0] is not c or cached[1] is not uc or cached[3] != (c._version, uc._version):
-                cached = (c, uc, torch.cat([uc, c]).contiguous(), (c._version, uc._version))
-                self._cfg_inputs = cached
-            context = cached[2]
-        else:
-            context = c
+        context = self._cfg_context(c, uc) if cfg else c
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
         reps = 2 if cfg else 1
@@ -400,89 +361,93 @@ class DDIMSampler(object):
             return None
         ctx, L = eng._context(context)          # new prompt: the static context / K|V buffers are refreshed in place
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
-        key = (self._GRAPH_KIND, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv)
-        if rng is not None:
-            key = ("step-mask" if masked else "step-rng", *key[1:], float(rng))
+        key = (kind, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv,
+               *(() if temperature is None else (float(temperature),)))
         G = eng.graph_get(key)
         if G is None:
-            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), ctx, L, rng, masked)
+            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L)
             if G is None:
                 return None
+        n = self.ddim_coef.shape[0]
+        if n > G["coef"].shape[0]:
+            return None                             # a longer schedule than the one captured for: take the eager path
         # inputs that are read by address: refreshed in place when the caller brings new ones (once per sample / per schedule)
-        # (the keyed tensors are kept alive with their keys: a freed tensor's address handed to the next sample's tensor must not
-        #  look like "unchanged")
         if x0_emb is not None:
-            k0 = (x0_emb.data_ptr(), x0_emb._version)
-            if G["x0_key"] != k0 or G["x0_ref"] is not x0_emb:
-                G["x0"].copy_(x0_emb)
-                G["x0_key"], G["x0_ref"] = k0, x0_emb
-        ksch = (self.ddim_coef.data_ptr(), self._t_table.data_ptr(), self.ddim_coef.shape[0])
-        if G["sched_key"] != ksch or G["sched_ref"][0] is not self.ddim_coef:
-            n = self.ddim_coef.shape[0]
-            if n > G["coef"].shape[0]:
-                return None                         # a longer schedule than the one captured for: take the eager path
-            G["coef"][:n].copy_(self.ddim_coef)
-            G["ttab"][:n].copy_(self._t_table)
-            G["sched_key"], G["sched_ref"] = ksch, (self.ddim_coef, self._t_table)
+            refresh(G["kept"], "x0_emb", (x0_emb,), (G["x0"],))
+        if refresh(G["kept"], "schedule", (self.ddim_coef, self._t_table), (G["coef"][:n], G["ttab"][:n])):
             G["expect"] = None
+        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
+            G["x"].copy_(x)
         return G
 
-    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, ctx, L, rng=None, masked=False):
+    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, temperature, ctx, L):
+        """the step of kind key[0] over fresh static buffers, captured and put under `key`; None when the capture is refused"""
         dev = x.device
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
         nsched = max(int(self.ddim_coef.shape[0]), 64)
+        buffers, front, update = STEP_KINDS[key[0]]
         G = dict(x=torch.empty_like(x), pred=torch.empty_like(x),
-                 x0=(torch.empty_like(x0_emb, dtype=torch.float32).contiguous() if x0_emb is not None else None), x0_key=None,
+                 x0=(torch.empty_like(x0_emb, dtype=torch.float32).contiguous() if x0_emb is not None else None),
                  sample=torch.empty((reps * b, Cc, f1 + Fp, h, w), device=dev, dtype=torch.float32),
                  t=torch.empty((reps * b,), device=dev, dtype=torch.long), step=torch.zeros((2,), device=dev, dtype=torch.int32),
                  coef=torch.zeros((nsched, 4), device=dev, dtype=torch.float32),
-                 ttab=torch.zeros((nsched,), device=dev, dtype=torch.long), sched_key=None, sched_ref=(None, None), x0_ref=None,
-                 expect=None, **(self._graph_buffers(x) if rng is None else
-                                 dict(seeds=torch.zeros((b, 2), device=dev, dtype=torch.int32), seeds_key=None, seeds_ref=None)))
+                 ttab=torch.zeros((nsched,), device=dev, dtype=torch.long), expect=None, **buffers(x),
+                 kept={})                            # step_graph.refresh's record of what the static buffers were last filled from
         G["coef"][:, 0] = 1.0                        # a_t = 1 in the unused rows: the warm-up below must stay finite
         G["x"].copy_(x)
         if x0_emb is not None:
             G["x0"].copy_(x0_emb)
-        if masked:
-            # an all-zero mask through warm-up and capture: the blend writes nothing there, whatever the step words hold; the caller's
-            # mask and latents are copied in by _graph_step afterwards
-            G.update(mask=torch.zeros((b, Fp, h, w), device=dev, dtype=torch.float32), known=torch.zeros_like(x), known_key=None,
-                     known_ref=(None, None))
 
         def body():
-            if masked:
-                ops.known_blend(G["x"], G["mask"], G["known"], G["coef"], step=G["step"], seeds=G["seeds"])
+            for launch in front:
+                launch(G)
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
-            if rng is None:
-                self._graph_update(G, eps, cfg, scale, f1)
-            else:
-                ops.cfg_ddim_step_rng_dev(eps, G["x"], G["coef"], G["step"], G["seeds"], cfg=cfg, scale=scale, cond_f=f1,
-                                          temperature=rng, x_prev=G["x"], pred_x0=G["pred"])
+            update(G, eps, temperature, cfg=cfg, scale=scale, cond_f=f1)
         if capture_step(eng, key, G, body) is None:
-            self._step_graph_broken = True
+            self._capture_refused = True
             return None
         return G
 
 
-def capture_step(eng, key, G, body):
-    """`body` (the launches of one sampler step over the static buffers in G) as ONE hipGraph: a warm-up run, the capture, and the
-    entry G -- with the graph under "graph" -- in the engine's graph cache under `key`.  Returns G, or None with a warning when the
-    capture is refused: the caller keeps the launch-by-launch path.  (DDIMSampler / PLMSSampler and slots.SlotSampler)"""
-    try:
-        body()                                       # warm-up: K|V / rotary caches, allocations
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            body()
-    except Exception as e:      # noqa: BLE001  capture refused: keep the launch-by-launch path
-        import warnings
-        warnings.warn(f"hipGraph capture of the sampler step failed ({type(e).__name__}: {e}); stepping launch by launch")
-        return None
-    G["graph"] = g
-    eng.graph_put(key, G)
-    return G
+# ---- the kinds of a captured step --------------------------------------------------------------------------------------------------
+def _seed_buffers(x):
+    return dict(seeds=torch.zeros((x.shape[0], 2), device=x.device, dtype=torch.int32))
+
+
+def _mask_buffers(x):
+    """an all-zero mask through warm-up and capture: the blend writes nothing there, whatever the step words hold; the caller's mask
+    and latents are copied in by _graph_step afterwards"""
+    b, _, Fp, h, w = x.shape
+    return dict(_seed_buffers(x), mask=torch.zeros((b, Fp, h, w), device=x.device, dtype=torch.float32), known=torch.zeros_like(x))
+
+
+def _blend(G):
+    ops.known_blend(G["x"], G["mask"], G["known"], G["coef"], step=G["step"], seeds=G["seeds"])
+
+
+def _ddim_update(G, eps, temperature, **kw):
+    ops.cfg_ddim_step_dev(eps, G["x"], G["coef"], G["step"], x_prev=G["x"], pred_x0=G["pred"], **kw)
+
+
+def _rng_update(G, eps, temperature, **kw):
+    ops.cfg_ddim_step_rng_dev(eps, G["x"], G["coef"], G["step"], G["seeds"], temperature=temperature, x_prev=G["x"],
+                              pred_x0=G["pred"], **kw)
+
+
+# kind (the first word of the graph-cache key) -> (its static buffers, its launches in front of seer_ddim_step_begin, its last kernel).
+# The step between the two is the same for every kind; plms.py adds "plms".
+STEP_KINDS = {"step": (lambda x: {}, (), _ddim_update),
+              "step-rng": (_seed_buffers, (), _rng_update),
+              "step-mask": (_mask_buffers, (_blend,), _rng_update)}
+
+
+def _refuse_sharded(unet, what: str) -> None:
+    """what one clip sharded over several ranks (parallel.attach) cannot do"""
+    if getattr(unet, "_shard", None) is not None:
+        raise ValueError({"seed": "seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)",
+                          "mask": "mask: a frame-sharded model cannot blend given latents (detach it, parallel.attach)"}[what])
 
 
 def _row_seeds(seed, batch_size: int):
@@ -521,8 +486,21 @@ def ddim_sample(sampler, unet, vae, shape, c, start_code, x0_emb, ddim_steps=10,
     samples_ddim, _ = sampler.sample(unet=unet, S=ddim_steps, conditioning=c, batch_size=shape[0], shape=shape[1:],
                                      x0_emb=x0_emb, verbose=False, unconditional_guidance_scale=scale,
                                      unconditional_conditioning=uc, eta=0.0, x_T=start_code, is_3d=True)
-    n, ch, f, h, w = samples_ddim.shape
-    z = (samples_ddim.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
+    return latents_to_clip(vae, samples_ddim)
+
+
+def latents_to_clip(vae, latents: torch.Tensor) -> torch.Tensor:
+    """latents [n, C, f, h, w] -> 1/0.18215 -> vae.decode of the n * f frames -> clip [n, 3, f, H, W], clamp((x + 1) / 2, 0, 1)"""
+    n, ch, f, h, w = latents.shape
+    z = (latents.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
     x = vae.decode(z).sample
     x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
     return ops.clamp01_(x.float())
+
+
+def frames_to_latents(vae, frames: torch.Tensor, generator=None) -> torch.Tensor:
+    """frames [b, 3, f, H, W] in [-1, 1] -> vae.encode of the b * f frames, one draw of the posterior from `generator`, * 0.18215 ->
+    latents [b, C, f, H/8, W/8] (inference_img.py:166-170)"""
+    b, ch, f, H, W = frames.shape
+    lat = vae.encode(frames.permute(0, 2, 1, 3, 4).reshape(b * f, ch, H, W)).latent_dist.sample(generator=generator) * 0.18215
+    return lat.reshape(b, f, *lat.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()

@@ -19,8 +19,7 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 
 import torch
 
-from . import ops
-from .ddim import ddim_sample
+from .ddim import ddim_sample, frames_to_latents, latents_to_clip
 
 
 @torch.no_grad()
@@ -35,11 +34,8 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
     if x0_image.shape[2] == 1:
         x0_image = x0_image.expand(-1, -1, f1, -1, -1)
     assert x0_image.shape[2] == f1, "x0_image must hold one frame or cond_frames frames"
-    b = x0_image.shape[0]
-    frames = x0_image.permute(0, 2, 1, 3, 4).reshape(b * f1, *x0_image.shape[1:2], *x0_image.shape[3:])    # (b f) c h w
-    lat = vae.encode(frames).latent_dist.sample(generator=latent_generator) * 0.18215
-    x0_emb = lat.reshape(b, f1, *lat.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()                       # b c f h w
-    _, c_l, _, h_l, w_l = x0_emb.shape
+    x0_emb = frames_to_latents(vae, x0_image, latent_generator)
+    b, c_l, _, h_l, w_l = x0_emb.shape
 
     fstext_model.set_numframe(num_frames)
     c = fstext_model(context=text_emb)
@@ -83,9 +79,7 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
             if x0_image.shape[2] == 1:
                 x0_image = x0_image.expand(-1, -1, f1, -1, -1)
             assert x0_image.shape[0] == 1 and x0_image.shape[2] == f1, "x0_image must hold one clip of one frame or cond_frames frames"
-            frames = x0_image.permute(0, 2, 1, 3, 4).reshape(f1, *x0_image.shape[1:2], *x0_image.shape[3:])    # (b f) c h w
-            lat = vae.encode(frames).latent_dist.sample(generator=latent_generator) * 0.18215
-            x0_emb = lat.reshape(1, f1, *lat.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()                     # b c f h w
+            x0_emb = frames_to_latents(vae, x0_image, latent_generator)
             c = fstext_model(context=r["text_emb"])
             uc = r["empty_emb"].unsqueeze(1).expand(-1, c.shape[1], -1, -1).contiguous()
             if not sampler:
@@ -111,11 +105,7 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     if first is None:
         return
     for tag, lat in sampler[0].run(itertools.chain([first], reqs)):
-        n, ch, f, h, w = lat.shape
-        z = (lat.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
-        x = vae.decode(z).sample
-        x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
-        yield tag, ops.clamp01_(x.float())
+        yield tag, latents_to_clip(vae, lat)
 
 
 def edit_t_enc(strength: float, entries: int) -> int:
@@ -148,9 +138,7 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
     if strength is not None:
         sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_eta=0.0, verbose=False)
         t_enc = edit_t_enc(strength, int(sampler.ddim_timesteps.shape[0]))
-    frames = video.permute(0, 2, 1, 3, 4).reshape(b * F, video.shape[1], H, W)                              # (b f) c h w
-    lat = vae.encode(frames).latent_dist.sample(generator=latent_generator) * 0.18215
-    lat = lat.reshape(b, F, *lat.shape[1:]).permute(0, 2, 1, 3, 4)                                          # b c f h w
+    lat = frames_to_latents(vae, video, latent_generator)
     x0_emb, given = (lat[:, :, :f1].contiguous() if f1 else None), lat[:, :, f1:].contiguous()
     fstext_model.set_numframe(F)
     c = fstext_model(context=text_emb)
@@ -163,11 +151,7 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
         noised = sampler.stochastic_encode(given, t_enc, seed=seed)
         samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,
                                  x0_emb=x0_emb, seed=seed)
-    n, ch, f, h, w = samples.shape
-    z = (samples.permute(0, 2, 1, 3, 4).reshape(n * f, ch, h, w) * (1 / 0.18215)).contiguous()
-    x = vae.decode(z).sample
-    x = x.reshape(n, f, *x.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
-    return ops.clamp01_(x.float())
+    return latents_to_clip(vae, samples)
 
 
 def concat_all_gather(t: torch.Tensor, process_group=None) -> torch.Tensor:

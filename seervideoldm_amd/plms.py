@@ -25,12 +25,11 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .ddim import DDIMSampler, _from_rank0
+from .ddim import STEP_KINDS, DDIMSampler
+from .step_graph import capture_engine
 
 
 class PLMSSampler(DDIMSampler):
-    _GRAPH_KIND = "plms"
-
     def make_schedule(self, ddim_num_steps, *args, ddim_eta=0., **kwargs):
         """DDIMSampler.make_schedule; PLMS is deterministic only (plms.py:25-26)"""
         if ddim_eta != 0:
@@ -43,15 +42,7 @@ class PLMSSampler(DDIMSampler):
                score_corrector=None, corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100,
                unconditional_guidance_scale=1., unconditional_conditioning=None, null_cond_prob=None, is_3d=False,
                **kwargs):
-        if conditioning is not None and not isinstance(conditioning, dict):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-        self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
-        if is_3d:
-            C, Fr, H, W = shape
-            size = (batch_size, C, Fr, H, W)
-        else:
-            raise NotImplementedError("the Seer hot path is 5-D (is_3d=True, ddim_sampling_utils.py:36)")
+        size = self._sample_size(S, batch_size, shape, conditioning, eta, verbose, is_3d)
         if noise_dropout > 0.:
             raise NotImplementedError("noise_dropout: only the deterministic PLMS path is built")
         return self.plms_sampling(unet, conditioning, size, x0_emb=x0_emb, is_3d=is_3d, callback=callback,
@@ -64,59 +55,41 @@ class PLMSSampler(DDIMSampler):
                       img_callback=None, log_every_t=100, temperature=1., unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, **kwargs):
         """plms.py:114-170 over the Seer model call"""
-        device = self.device
         b = shape[0]
-        img = torch.randn(shape, device=device) if x_T is None else x_T.to(device=device, dtype=torch.float32)
-        # a clip sharded over several ranks (parallel.attach): every rank runs the same update on rank 0's inputs
-        img = _from_rank0(unet, img)
-        if x0_emb is not None:
-            x0_emb = _from_rank0(unet, x0_emb.to(device))
+        img, x0_emb = self._chain_start(unet, shape, x_T, x0_emb)
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
-        total_steps = self.ddim_timesteps.shape[0]
-        intermediates = {"x_inter": [img], "pred_x0": [img]}
-        graph = (getattr(unet, "use_graph", False) and img.is_cuda
-                 and (uc is None or scale == 1. or uc.shape[2] == cond.shape[2]))
-        from .unet import SeerUNet
-        # the first step of a captured chain runs its two evaluations launch by launch, not as a UNet graph of their own
-        first_eager = graph and isinstance(unet, SeerUNet) and unet._shard is None
+        plain = uc is None or scale == 1.
+        # a chain whose later steps are captured (batched CFG or none, and a model whose steps may be captured at all) runs the two
+        # evaluations of its first step launch by launch, not as a UNet graph of their own
+        graph = ((plain or uc.shape[2] == cond.shape[2]) and not self._capture_refused
+                 and capture_engine(unet, self.ops, img.device) is not None)
         old_eps = []
         chained = False
-        static_before, self.static_step_outputs = self.static_step_outputs, True
-        try:
-            for i in range(total_steps):
-                index = total_steps - i - 1
-                out = None
-                if graph and i > 0:
-                    plain = uc is None or scale == 1.
-                    out = self._plms_graph_step(unet, img, cond, None if plain else uc, index, x0_emb,
-                                                0 if plain else cond_frames, scale, old_eps, restart=not chained)
-                chained = out is not None
-                if out is None:
-                    if i == 0 and first_eager:
-                        unet.use_graph = False
-                    try:
-                        # t_next = time_range[min(i + 1, n - 1)] (plms.py:145)
-                        out = self.p_sample_plms(unet, img, cond, self._t_table[index].expand(b), index, x0_emb=x0_emb,
-                                                 cond_frames=cond_frames, temperature=temperature,
-                                                 unconditional_guidance_scale=scale, unconditional_conditioning=uc,
-                                                 old_eps=old_eps, t_next=self._t_table[max(index - 1, 0)].expand(b))
-                    finally:
-                        if i == 0 and first_eager:
-                            unet.use_graph = True
-                img, pred_x0, e_t = out
-                old_eps.append(e_t)
-                if len(old_eps) >= 4:
-                    old_eps.pop(0)
-                if callback:
-                    callback(i)
-                if img_callback:
-                    img_callback(pred_x0.clone(), i)
-                if index % log_every_t == 0 or index == total_steps - 1:
-                    intermediates["x_inter"].append(img.clone())
-                    intermediates["pred_x0"].append(pred_x0.clone())
-        finally:
-            self.static_step_outputs = static_before
-        return img.clone(), intermediates
+
+        def step(img, index):
+            nonlocal chained
+            first, out = not old_eps, None
+            if graph and not first:
+                out = self._plms_graph_step(unet, img, cond, None if plain else uc, index, x0_emb, 0 if plain else cond_frames,
+                                            scale, old_eps, restart=not chained)
+            chained = out is not None
+            if out is None:
+                if first and graph:
+                    unet.use_graph = False
+                try:
+                    # t_next = time_range[min(i + 1, n - 1)] (plms.py:145)
+                    out = self.p_sample_plms(unet, img, cond, self._t_table[index].expand(b), index, x0_emb=x0_emb,
+                                             cond_frames=cond_frames, temperature=temperature, unconditional_guidance_scale=scale,
+                                             unconditional_conditioning=uc, old_eps=old_eps,
+                                             t_next=self._t_table[max(index - 1, 0)].expand(b))
+                finally:
+                    if first and graph:
+                        unet.use_graph = True
+            old_eps.append(out[2])
+            if len(old_eps) >= 4:
+                old_eps.pop(0)
+            return out[:2]
+        return self._run_chain(img, self.ddim_timesteps.shape[0], step, callback, img_callback, log_every_t)
 
     @torch.no_grad()
     def p_sample_plms(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
@@ -158,24 +131,13 @@ class PLMSSampler(DDIMSampler):
     def ddim_sampling(self, *args, **kwargs):
         raise NotImplementedError("PLMSSampler samples with plms_sampling")
 
-    # ---- the captured step: DDIMSampler's graph with a 3-slot eps ring and seer_cfg_plms_step_dev as its last kernel --------
-    def _graph_buffers(self, x):
-        return dict(ring=torch.zeros((3, *x.shape), device=x.device, dtype=torch.float32),
-                    ring_state=torch.zeros((4,), device=x.device, dtype=torch.int32), ring_host=None)
-
-    def _graph_update(self, G, eps, cfg, scale, cond_f):
-        ops.cfg_plms_step_dev(eps, G["x"], G["coef"], G["step"], G["ring"], G["ring_state"], cfg=cfg, scale=scale, cond_f=cond_f,
-                              x_prev=G["x"], pred_x0=G["pred"])
-
     def _plms_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, old_eps, restart):
         """one later PLMS step as a single replay; `restart` (or a chain the graph did not run last) seeds the ring from old_eps and
         writes the step index and the ring state of that index: the only host writes of a chain.  Returns None when the step
         cannot be captured."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale)
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "plms")
         if G is None:
             return None
-        if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
-            G["x"].copy_(x)
         if restart or G["expect"] != index or G["ring_host"] is None:
             hist = list(reversed(old_eps[-3:]))                         # newest first -> slots 0, 2, 1
             if hist:
@@ -192,3 +154,16 @@ class PLMSSampler(DDIMSampler):
         G["ring_host"] = (min(valid + 1, 3), slot)
         e_t = G["ring"][slot]
         return x_prev, pred_x0, (e_t if self.static_step_outputs else e_t.clone())
+
+
+# ---- the captured step: DDIMSampler's, with a 3-slot eps ring and seer_cfg_plms_step_dev as its last kernel ------------------------
+def _ring_buffers(x):
+    return dict(ring=torch.zeros((3, *x.shape), device=x.device, dtype=torch.float32),
+                ring_state=torch.zeros((4,), device=x.device, dtype=torch.int32), ring_host=None)
+
+
+def _plms_update(G, eps, temperature, **kw):
+    ops.cfg_plms_step_dev(eps, G["x"], G["coef"], G["step"], G["ring"], G["ring_state"], x_prev=G["x"], pred_x0=G["pred"], **kw)
+
+
+STEP_KINDS["plms"] = (_ring_buffers, (), _plms_update)

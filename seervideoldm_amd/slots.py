@@ -47,6 +47,7 @@ import torch
 
 from . import ops as hip_ops
 from .ddim import DDIMSampler, capture_step
+from .step_graph import capture_engine, engine_on
 
 MAX_SLOTS = 4           # the time-embedding MLP (seer_linear_smallm) takes up to 8 rows: the [uc | c] pair of 4 slots
 
@@ -61,7 +62,7 @@ class SlotSampler:
     False everything is as it was before that keyword existed.  `stochastic=True` lets a request carry eta, seed and temperature
     (submit): the step's last kernel then draws the noise per slot, over two more static buffers, again under a key of its own; it
     excludes plms=True (PLMS has no noise term).  `editing=True` lets a request carry mask, x0 and t_start (submit): the step then
-    opens with the blend kernel, over per-slot mask, given-latent and seed buffers, under the key "slots-edit" ("slots-edit-rng" with
+    opens with the blend kernel, over per-slot mask, given-latent and seed buffers, under a key of its own once more (and another with
     stochastic=True); it excludes plms=True as well."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
@@ -98,20 +99,34 @@ class SlotSampler:
         self._ttab = torch.zeros((n, self.max_steps), device=dev, dtype=torch.long)
         self._scale = torch.ones((n,), device=dev, dtype=f32)
         self._context = torch.zeros((2 * n, f1 + Fp, L, D), device=dev, dtype=f32)    # uc rows, then c rows
-        self.plms = bool(plms)
+        # The mode, decided here once: its buffers, the first word of its graph-cache key, the launches in front of the model call and the
+        # update behind it (names in the backend with their arguments, for _body), and the buffers to zero when a slot retires (step).
+        self.plms, self.stochastic, self.editing = bool(plms), bool(stochastic), bool(editing)
+        self._retire = [self._x] + ([self._x0] if f1 else [])
         if self.plms:
             self._state = torch.zeros((n, hip_ops.SLOT_STATE_WORDS), device=dev, dtype=torch.int32)    # phase 0, nothing in the ring
             self._ring = torch.zeros((n, 3, C, Fp, h, w), device=dev, dtype=f32)
             self._xprov = torch.zeros_like(self._x)
-        self.stochastic = bool(stochastic)
-        self.editing = bool(editing)
+            self._retire.append(self._xprov)
+            self._kind = "slots-plms"
+            self._front = [("slot_plms_step_begin", (self._x0, self._x, self._xprov, self._ttab, self._step, self._state, 2, self._sample,
+                                                     self._t))]
+            self._update = ("slot_cfg_plms_step", (self._state, self._ring, self._xprov))
+        else:
+            self._kind = {(False, False): "slots", (False, True): "slots-rng", (True, False): "slots-edit",
+                          (True, True): "slots-edit-rng"}[self.editing, self.stochastic]
+            self._front = [("slot_step_begin", (self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t))]
+            self._update = ("slot_cfg_ddim_step", ())
         if self.stochastic or self.editing:
             self._seeds = torch.zeros((n, 2), device=dev, dtype=torch.int32)          # (lo, hi) words of a slot's uint64 seed
-        if self.stochastic:
-            self._temp = torch.ones((n,), device=dev, dtype=f32)
         if self.editing:
             self._mask = torch.zeros((n, Fp, h, w), device=dev, dtype=f32)            # all zero: the blend leaves the slot alone
             self._known = torch.zeros_like(self._x)
+            self._retire += [self._mask, self._known]       # the next clip of a slot is a plain one until its submit says otherwise
+            self._front.insert(0, ("slot_known_blend", (self._x, self._mask, self._known, self._coef, self._step, self._seeds)))
+        if self.stochastic:
+            self._temp = torch.ones((n,), device=dev, dtype=f32)
+            self._update = ("slot_cfg_ddim_step_rng", (self._seeds, self._temp))
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
         self._tables: Dict[Tuple[int, float], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -252,14 +267,8 @@ class SlotSampler:
             self._left[s] -= 1
             if self._left[s] == 0:
                 done.append((s, self._x[s:s + 1].clone()))
-                self._x[s].zero_()                   # an idle slot's rows stay finite (its counter is -1 by now: the kernels saw to it)
-                if self.f1:
-                    self._x0[s].zero_()
-                if self.plms:
-                    self._xprov[s].zero_()
-                if self.editing:
-                    self._mask[s].zero_()            # the next clip of this slot is a plain one until its submit says otherwise
-                    self._known[s].zero_()
+                for buf in self._retire:             # an idle slot's rows stay finite (its counter is -1 by now: the kernels saw to it)
+                    buf[s].zero_()
         return done
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
@@ -282,22 +291,13 @@ class SlotSampler:
                 yield tags.pop(s), lat
 
     def _body(self, model) -> None:
-        if self.plms:
-            self.ops.slot_plms_step_begin(self._x0, self._x, self._xprov, self._ttab, self._step, self._state, 2, self._sample, self._t)
-            eps = model()
-            self.ops.slot_cfg_plms_step(eps, self._x, self._scale, self._coef, self._step, self._state, self._ring, self._xprov,
-                                        cond_f=self.f1, x_prev=self._x, pred_x0=self._pred)
-            return
-        if self.editing:
-            self.ops.slot_known_blend(self._x, self._mask, self._known, self._coef, self._step, self._seeds)
-        self.ops.slot_step_begin(self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t)
+        """the launches of the sampler's mode (__init__) around `model`, the UNet over the assembled [uc rows | c rows]"""
+        for name, args in self._front:
+            getattr(self.ops, name)(*args)
         eps = model()
-        if self.stochastic:
-            self.ops.slot_cfg_ddim_step_rng(eps, self._x, self._scale, self._coef, self._step, self._seeds, self._temp, cond_f=self.f1,
-                                            x_prev=self._x, pred_x0=self._pred)
-            return
-        self.ops.slot_cfg_ddim_step(eps, self._x, self._scale, self._coef, self._step, cond_f=self.f1, x_prev=self._x,
-                                    pred_x0=self._pred)
+        name, args = self._update
+        getattr(self.ops, name)(eps, self._x, self._scale, self._coef, self._step, *args, cond_f=self.f1, x_prev=self._x,
+                                pred_x0=self._pred)
 
     def _run_step(self) -> None:
         from .unet import SeerUNet
@@ -309,17 +309,12 @@ class SlotSampler:
             raise ValueError("slots run an unsharded model without center_input_sample")
         if self.shape[2] % 8 or self.shape[3] % 8:
             raise ValueError("latent height/width must be multiples of 8 (three stride-2 levels + 4/8 windows)")
-        if unet._engine is None or unet._engine.device != self.device:
-            unet.prepare()
-        eng = unet._engine
+        eng = engine_on(unet, self.device)           # the launch-by-launch step runs on the engine too
         ctx, L = eng._context(self._context)         # a new admission (or another caller's prompt since): refreshed in place, all slots
         model = lambda: eng._forward(self._sample, self._t, ctx, L, self.model_cond_frame)
         G = None
-        if (unet.use_graph and self.ops is hip_ops and unet._ops_backend is hip_ops and self._x.is_cuda
-                and not self._capture_refused and not getattr(eng, "_graph_broken", False)):
-            kind = "slots-plms" if self.plms else ("slots-edit-rng" if self.stochastic else "slots-edit") if self.editing else \
-                "slots-rng" if self.stochastic else "slots"
-            key = (kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+        if not self._capture_refused and capture_engine(unet, self.ops, self.device) is not None:
+            key = (self._kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)
