@@ -1,4 +1,4 @@
-// In-kernel timeline of one GEMM / conv tile: wall_clock64 stamps (10 ns) from a -DSEER_GEMM_STAMPS build of gemm.hip linked as
+// In-kernel timeline of one GEMM / conv tile: wall_clock64 stamps (10 ns) from a -DSEER_GEMM_STAMPS build of gemm_tiles_all.hip linked as
 // build/libprobe/libseer_hip.so (profiles/r02_pp8_stamps.log, r02_tile_stamps.log).
 //   lab_pp8stamps M N K geglu [tile [residual]]           plain GEMM (tile 21 = the 256x256 8-phase tile, 0 = auto)
 //   lab_pp8stamps conv n_img H Cin Cout [tile [splits]]   3x3 conv, stride 1

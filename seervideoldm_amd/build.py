@@ -18,7 +18,10 @@ ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libseer_hip.so"
-SOURCES = ["gemm.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "train.hip"]
+# the tile kernel of seer_gemm_bf16 compiles as units that share csrc/gemm_tiles.h (gemm_tiles_all.hip, every row in one unit, is
+# for the measurement builds of scripts/ and is not part of the library)
+GEMM_TILE_UNITS = [f"gemm_tiles_{u}.hip" for u in range(6)]
+SOURCES = ["gemm.hip", *GEMM_TILE_UNITS, "gemm_reduce.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "train.hip"]
 ARCH = "gfx950"
 # per-source extra flags.  attention: keep the MFMA accumulators in VGPRs (gfx950's unified file allows it) -- the online
 # softmax touches S and O every key tile, and the default AGPR form costs ~220 v_accvgpr moves per tile per wave.
@@ -29,6 +32,8 @@ EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gemm_tn.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # GEMM: the epilogue reads every accumulator once; VGPR form saves those moves (+0.7 % on the step, A/B in one run)
                "gemm.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+               **{u: ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] for u in GEMM_TILE_UNITS},
+               "gemm_reduce.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gemm_ws.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                "gemm_t320.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
                # rowchain: 120 accumulators + 80 weight-fragment registers + 48 of activation fragments fit the V file; its
@@ -65,6 +70,17 @@ def _digest() -> str:
     return h.hexdigest()
 
 
+def _shared_digest() -> "hashlib._Hash":
+    """what every object depends on besides its own source and flags: the headers and .inc files of csrc/ (no include scanning),
+    the public header, and the two files that decide how objects are built and checked"""
+    h = hashlib.sha256()
+    shared = [p for p in CSRC.glob("*") if p.suffix in (".h", ".inc")]
+    for p in sorted(shared + [ROOT / "include" / "seer_hip.h", Path(__file__).resolve(), PKG / "asm_check.py"]):
+        h.update(p.name.encode())
+        h.update(p.read_bytes())
+    return h
+
+
 def build_library(force: bool = False, verbose: bool = False) -> Path:
     LIBDIR.mkdir(exist_ok=True)
     stamp = LIBDIR / "build.sha256"
@@ -74,6 +90,7 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
     hipcc = _hipcc()
     objdir = LIBDIR / "obj"
     objdir.mkdir(exist_ok=True)
+    shared = _shared_digest()
     # -save-temps=obj: the device assembly of every source stays next to its object for asm_check (the other temporaries go)
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT / 'include'}", f"-I{CSRC}",
              "-fno-gpu-rdc", "-Wno-unused-result", "-save-temps=obj", *NO_PACKED_FP32]
@@ -81,6 +98,15 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
     def compile_one(src: str) -> Path:
         obj = objdir / (src + ".o")
         cmd = [hipcc, *flags, *EXTRA_FLAGS.get(src, []), "-c", str(CSRC / src), "-o", str(obj)]
+        # an object is reused while its source, its command line and the shared inputs are what they were when it was compiled
+        h = shared.copy()
+        h.update("\0".join(cmd).encode())
+        h.update((CSRC / src).read_bytes())
+        own, kept = h.hexdigest(), objdir / (src + ".sha256")
+        asm = objdir / f"{src.split('.')[0]}-hip-amdgcn-amd-amdhsa-{ARCH}.s"
+        if not force and obj.exists() and asm.exists() and kept.exists() and kept.read_text().strip() == own:
+            return obj
+        kept.unlink(missing_ok=True)
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -92,9 +118,11 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
                 tmp.unlink()
         for tmp in objdir.glob(f"{src}-*"):
             tmp.unlink()
+        kept.write_text(own)
         return obj
 
-    with ThreadPoolExecutor(max_workers=4) as ex:
+    # the pool is sized for the 8-16 CPUs a build gets, not for the machine's core count
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     # the assembly rules of asm_check.py: instruction forms that misbehaved on MI355X, and the register discipline of the
     # inline-asm LDS reads in attention40.hip

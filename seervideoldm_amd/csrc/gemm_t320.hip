@@ -5,9 +5,9 @@
 // ~1.1 PF, measured 1.07.  Every N of the denoising network is a multiple of 320 (320 * {1, 2, 3, 4, 6, 8, 12, 16, 32}) and
 // every M of its three upper levels a multiple of 256, so ONE tile shape, 256 x 320 (142 FLOP/B), covers them without a padded
 // column.  8 waves as 4 (M) x 2 (N), 64 x 160 wave tiles = 160 accumulator registers, v_mfma_f32_16x16x32_bf16 issued swapped
-// (a lane holds 4 consecutive output columns of one row, as in gemm.hip).
+// (a lane holds 4 consecutive output columns of one row, as in gemm_tile_kernel.h).
 //
-// Main loop = the 8-phase ping-pong schedule of gemm.hip's 256 x 256 tile (cdna_hip_programming.md, "256^2 8-phase template")
+// Main loop = the 8-phase ping-pong schedule of gemm_tile_kernel.h's 256 x 256 tile (cdna_hip_programming.md, "256^2 8-phase template")
 // re-derived for this wave grid: a K tile is four LDS regions (A rows of quadrant-row 0 / 1 of every wave row: 16 KB each;
 // W columns of quadrant-column 0 / 1 of both wave columns: 20 KB each), four phases each multiply one 32 x 80 quadrant of the
 // wave tile (20 MFMAs) in the order (r0,c0) (r1,c0) (r1,c1) (r0,c1) so that the 40-register W fragments are read twice and the
@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(NT) seer_gemm_t320_kernel(const seer_gemm_desc
     const int frow = lane & 15, fq = lane >> 4;
 
     // ---- block -> (tile, slice): slices of a tile have adjacent block ids (dispatched together); tiles in XCD-contiguous
-    // chunks grouped along M like gemm.hip (blocks b and b + 8 share an XCD)
+    // chunks grouped along M like gemm_tile_kernel.h (blocks b and b + 8 share an XCD)
     const int tiles_m = (p.M + BM - 1) / BM;
     const int tiles_n = p.N / BN;
     const int S = SPLIT ? p.splits : 1;
@@ -464,7 +464,7 @@ __global__ void __launch_bounds__(NT) seer_gemm_t320_kernel(const seer_gemm_desc
     const bool res_lds = !SPLIT && R != nullptr && (p.ldr % 8 == 0) && ((reinterpret_cast<uintptr_t>(R) & 15) == 0);
 
     if constexpr (!SPLIT) {
-        // unsplit: one pass per term over the register tile (the order of additions of gemm.hip: bias, GEGLU, row vector, rotary,
+        // unsplit: one pass per term over the register tile (the order of additions of gemm_tile_kernel.h: bias, GEGLU, row vector, rotary,
         // column scale, residual)
         if (p.bias) {
 #pragma unroll
@@ -679,7 +679,7 @@ std::once_flag g_t320_once;
 }  // namespace
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-// what the kernel handles (gemm.hip decides WHEN to use it)
+// what the kernel handles (the planner in gemm.hip decides WHEN to use it; the hooks are declared in gemm_tiles.h)
 bool seer_gemm_t320_eligible(const seer_gemm_desc& d) {
     if (d.N % 320 || d.K % 64 || d.M < 1) return false;
     if (d.epilogue & (SEER_EPI_OUT_F32 | SEER_EPI_TRANS_OUT | SEER_EPI_SILU | SEER_EPI_QUICKGELU | SEER_EPI_F16)) return false;

@@ -1,7 +1,7 @@
 // Weight-stationary persistent bf16 GEMM for the SHORT-K projections of the Seer UNet on gfx950 (MI355X):
 //     C[m, n] = epilogue( sum_k A(m, k) * W[n, k] ),   K = 320 or 640   (q|k|v, to_out, proj_in / proj_out, GEGLU ff.net.0 and
 //     the 1x1 shortcut convs of the two upper levels: attention.py:484-489,742,783, resnet.py:172)
-// Same descriptor and epilogue semantics as seer_gemm_bf16's tile kernel (gemm.hip), which keeps every other shape.
+// Same descriptor and epilogue semantics as seer_gemm_bf16's tile kernel (gemm_tile_kernel.h), which keeps every other shape.
 //
 // Why.  With K = 320 / 640 a 128x128 output tile has 5 / 10 K steps.  The tile kernel spends 5 us of CU time per tile on it
 // (profiles/r02_lab_gemm_base.log: 79 us for the 3840 tiles of the level-0 GEGLU projection) against 1.3 us of MFMA work: the
@@ -68,7 +68,7 @@ __device__ __forceinline__ void ws_wait_vmcnt(int n) {       // n is wave-unifor
 
 // CW: columns of W per wave (8 waves side by side: a workgroup covers 8 * CW columns).  NK = K / 64 is a template parameter:
 // the W fragments are a register array and must be indexed statically (the K loop is fully unrolled).
-// LDS (dynamic): [3 slots: NK x (ROWS rows x 128 B), 16-byte chunks XOR-swizzled by row & 7 as in gemm.hip]
+// LDS (dynamic): [3 slots: NK x (ROWS rows x 128 B), 16-byte chunks XOR-swizzled by row & 7 as in gemm_tile_kernel.h]
 //                [8 wave-private areas: a 32-row staging tile + the wave's CW bias values]
 template <int CW, int NK, bool GEGLU, bool F16 = false>
 __global__ void __launch_bounds__(512) seer_gemm_ws_kernel(const seer_gemm_desc p, const int n_panels, const int wpp) {
@@ -319,7 +319,7 @@ int ws_launch(const seer_gemm_desc& d, hipStream_t st) {
 
 }  // namespace
 
-// Can this (validated, normalised) descriptor run on the weight-stationary kernel?  Called by seer_gemm_bf16 (gemm.hip).
+// Can this (validated, normalised) descriptor run on the weight-stationary kernel?  Called by the planner of seer_gemm_bf16 (gemm.hip; declared in gemm_tiles.h).
 // Built for the two contraction lengths of the upper UNet levels: K = 320 (64 columns per wave) and K = 640 (32 columns per
 // wave); either way a wave holds 160 registers of W fragments.
 bool seer_gemm_ws_eligible(const seer_gemm_desc& d) {
