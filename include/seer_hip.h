@@ -543,6 +543,28 @@ int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t 
                             const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x, float* x_prev,
                             float* pred_x0, void* stream);
 
+/* DDIM inversion (CompVis ldm/models/diffusion/ddim.py, encode(); eta = 0 by definition): the same CFG combine, then the update one
+ * step UPWARD, fp32.  x is the latent at the level of a_prev, eps the model's output at the timestep of a_t:
+ *   x0     = (x - sqrt(1-a_prev) e)/sqrt(a_prev)
+ *   x_next = sqrt(a_t) x0 + sqrt(1-a_t) e          (sqrt(1-a_t) = column 3 of the row; sigma, column 2, is not read)
+ * eps, coef and the shapes as in seer_cfg_ddim_step; x_next may be x; pred_x0 (= x0) may be NULL: it is then not written.
+ *   seer_cfg_ddim_invert_step      row `index` of coef, from the host.
+ *   seer_cfg_ddim_invert_step_dev  last kernel of a captured inversion step behind seer_ddim_step_begin: index = step[1], then
+ *                                  step[0] = index + 1 -- replays walk the schedule upwards.  limit: int32[1] in DEVICE memory, the
+ *                                  number of rows the chain may use (the arguments of a replay are frozen, and the rows of a static
+ *                                  table beyond the schedule hold a_prev = 0, which the update divides by).  For index < 0 or
+ *                                  index >= limit[0] step[0] is written all the same, but no coefficient row is read and no element
+ *                                  of x_next or pred_x0 written; limit[0] = 0 makes a launch write nothing but that word.
+ * No kernel reads and writes the same word.  SEER_EINVAL for a NULL required pointer (eps, coef, x, x_next; step and limit),
+ * b <= 0, non-positive extents, cond_f < 0 or >= F_total, index < 0 from the host, a pointer that is not 4-byte aligned, a grid
+ * beyond one dimension. */
+int seer_cfg_ddim_invert_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                              float scale, const float* coef, int32_t index, const float* x, float* x_next,
+                              float* pred_x0 /* NULL: not written */, void* stream);
+int seer_cfg_ddim_invert_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                  float scale, const float* coef, int32_t* step, const int32_t* limit, const float* x,
+                                  float* x_next, float* pred_x0, void* stream);
+
 /* ---- seeded noise: the DDIM step with eta > 0 and no noise tensor ------------------------------------------------------------
  * A counter-based generator, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), runs
  * inside the kernels: a clip's noise is a pure function of (seed, schedule index, element), whatever batch row or slot holds it.

@@ -1,7 +1,7 @@
 // The kernels at both ends of a sampler step on gfx950, fp32, one thread per latent element: "assemble the UNet input and latch the
-// counter", "CFG-combine eps and apply the DDIM or PLMS update", "re-noise the given latents".  Every form of a step -- host index,
-// device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update, plms_update, known_blend_at), so an
-// element gets the same bits from each of them.
+// counter", "CFG-combine eps and apply the DDIM, inversion or PLMS update", "re-noise the given latents".  Every form of a step --
+// host index, device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update, invert_update,
+// plms_update, known_blend_at), so an element gets the same bits from each of them.
 #include "seer_common.h"
 #include "seer_philox.h"
 #include <cstdint>
@@ -65,6 +65,18 @@ __device__ __forceinline__ void step_update(float ep, const float* __restrict__ 
     } else {
         x_prev[i] = sqrtf(a_prev) * x0 + dir;
     }
+    if (pred_x0) pred_x0[i] = x0;
+}
+
+// DDIM inversion (CompVis ddim.py encode(), eta = 0 by definition): the probability-flow ODE one step UPWARD.  x is the latent at the
+// level of a_prev, e the CFG-combined eps the model gave at the timestep of a_t; x_next is the latent at the level of a_t.  sigma is
+// not read.  x may alias x_next: the element is read before it is written.
+__device__ __forceinline__ void invert_update(float e, const float* __restrict__ coef, int index, const float* x, float* x_next,
+                                              float* __restrict__ pred_x0, int64_t i) {
+    const float a_t = coef[4 * index], a_prev = coef[4 * index + 1], s1m = coef[4 * index + 3];
+    const float xv = x[i];
+    const float x0 = (xv - sqrtf(1.f - a_prev) * e) / sqrtf(a_prev);
+    x_next[i] = sqrtf(a_t) * x0 + s1m * e;
     if (pred_x0) pred_x0[i] = x0;
 }
 
@@ -132,6 +144,23 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int cfg, int b, i
     step_update<DDIM_TERM>(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), coef, index, x,
                            StepNoise{noise, seeds ? seeds + 2 * bi : nullptr, temperature, (uint32_t)(i - bi * per_clip)}, x_prev,
                            pred_x0, i);
+}
+
+// The inversion step.  step == nullptr: the host's `index`; else index = step[1], one thread writes step[0] = index + 1 (the chain
+// walks the schedule UPWARDS), and `limit` (one word in device memory: a replay's arguments are frozen, and the rows of a static table
+// beyond the schedule hold a_prev = 0, which this update divides by) ends it: index < 0 or index >= limit[0] reads no coefficient
+// row and writes no element.  x may alias x_next.
+__global__ void cfg_ddim_invert_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
+                                       const float* __restrict__ coef, int index, int* __restrict__ step,
+                                       const int* __restrict__ limit, const float* x, float* x_next, float* __restrict__ pred_x0) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step) {
+        index = step[1];
+        if (i == 0) step[0] = index + 1;
+        if (index < 0 || index >= limit[0]) return;
+    }
+    if (i >= (int64_t)b * C * (Ft - cond_f) * HW) return;
+    invert_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), coef, index, x, x_next, pred_x0, i);
 }
 
 __global__ void cfg_plms_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
@@ -423,6 +452,22 @@ extern "C" int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t
     if (!eps || !coef || !step || !x || !seeds || !x_prev || b <= 0 || !philox_clip_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
     return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, step, x, seeds, x_prev, pred_x0}, stream,
                               eps, cfg, b, C, F_total, cond_f, HW, scale, coef, 0, step, x, nullptr, seeds, temperature, x_prev, pred_x0);
+}
+
+extern "C" int seer_cfg_ddim_invert_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                         int32_t HW, float scale, const float* coef, int32_t index, const float* x, float* x_next,
+                                         float* pred_x0, void* stream) {
+    if (!eps || !coef || !x || !x_next || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || index < 0) return SEER_EINVAL;
+    return launch_per_element(cfg_ddim_invert_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, x, x_next, pred_x0}, stream, eps,
+                              cfg, b, C, F_total, cond_f, HW, scale, coef, index, nullptr, nullptr, x, x_next, pred_x0);
+}
+
+extern "C" int seer_cfg_ddim_invert_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
+                                             int32_t HW, float scale, const float* coef, int32_t* step, const int32_t* limit,
+                                             const float* x, float* x_next, float* pred_x0, void* stream) {
+    if (!eps || !coef || !step || !limit || !x || !x_next || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
+    return launch_per_element(cfg_ddim_invert_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, step, limit, x, x_next, pred_x0},
+                              stream, eps, cfg, b, C, F_total, cond_f, HW, scale, coef, 0, step, limit, x, x_next, pred_x0);
 }
 
 extern "C" int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,

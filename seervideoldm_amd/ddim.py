@@ -20,6 +20,10 @@ noise does not depend on the batch it is in.
 207-241), whose mask blend ddim_video.py lost: kept regions are re-noised to each step's level and blended in in front of the step
 (seer_known_blend; with a seed a node of the captured step, DESIGN.md "Editing"), a clip can be noised to a level of the schedule
 (seer_q_sample) and denoised from there.
+
+`encode` is DDIM inversion, the `encode()` CompVis added to ddim.py after the version the reference vendors: the probability-flow ODE
+upward from a clip's latents to a level of the schedule with the model in the loop (seer_cfg_ddim_invert_step; as a captured step its
+counter runs upward to a limit word in device memory, DESIGN.md "Editing"), so that decode comes back to the same clip.  Nothing is drawn.
 """
 from __future__ import annotations
 
@@ -242,6 +246,67 @@ class DDIMSampler(object):
                                   seeds=_row_seeds(seed, x_latent.shape[0]), mask=mask, x0=x0, t_start=t_start)[0]
 
     @torch.no_grad()
+    def encode(self, unet, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, callback=None, *, x0_emb=None, cond_frames=0):
+        """DDIM inversion, CompVis ddim.py encode() on the current schedule with the UNet first, as in sample: the deterministic
+        counterpart of stochastic_encode.  x0 [b, C, F_pred, h, w] is taken as the latent at the level of row 0's a_prev; the indices
+        0 ... t_enc - 1 run UPWARD through p_invert_ddim, each evaluating the model at its own (the target level's) timestep, and
+        the result is the latent at level t_enc: decode(t_start=t_enc) is the exact counterpart.  1 <= t_enc <= the schedule's entries.
+        Returns (x_latent, {"x_inter": [...], "pred_x0": [...]}): with return_intermediates = k the lists hold copies of the latent
+        and of pred_x0 after every k-th step (steps k - 1, 2k - 1, ...), otherwise they are empty.  callback(i) is called after
+        step i.  Inversion is eta = 0 by definition: NO draw is made from torch's generator, which is left where it was."""
+        if use_original_steps:
+            raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
+        n = int(self.ddim_timesteps.shape[0])
+        if not 1 <= int(t_enc) <= n:
+            raise ValueError(f"t_enc = {t_enc}: 1 .. {n}, the entries of the current schedule")
+        every = None if return_intermediates is None else int(return_intermediates)
+        if every is not None and every < 1:
+            raise ValueError(f"return_intermediates = {return_intermediates}: None, or keep every k-th latent with k >= 1")
+        t_enc = int(t_enc)
+        img, x0_emb = self._chain_start(unet, tuple(x0.shape), x0, x0_emb)
+        b = img.shape[0]
+        intermediates = {"x_inter": [], "pred_x0": []}
+        static_before, self.static_step_outputs = self.static_step_outputs, True
+        try:
+            for index in range(t_enc):
+                img, pred_x0 = self.p_invert_ddim(unet, img, c, self._t_table[index].expand(b), index, x0_emb=x0_emb,
+                                                  cond_frames=cond_frames, unconditional_guidance_scale=unconditional_guidance_scale,
+                                                  unconditional_conditioning=unconditional_conditioning, limit=t_enc)
+                if every is not None and (index + 1) % every == 0:
+                    intermediates["x_inter"].append(img.clone())
+                    intermediates["pred_x0"].append(pred_x0.clone())
+                if callback:
+                    callback(index)
+        finally:
+            self.static_step_outputs = static_before
+        return img.clone(), intermediates
+
+    @torch.no_grad()
+    def p_invert_ddim(self, unet, x, c, t, index, x0_emb=None, cond_frames=0, unconditional_guidance_scale=1.,
+                      unconditional_conditioning=None, limit=None):
+        """One step of encode: x at the level of row `index`'s a_prev, the model evaluated at t (encode passes the row's own timestep)
+        -> (x_next at the level of a_t, pred_x0).  Nothing is drawn.  `limit`: the number of rows the chain this step belongs to may
+        use (encode's t_enc; the whole schedule when None) -- what the captured step's counter stops at."""
+        n = int(self.ddim_coef.shape[0])
+        limit = n if limit is None else int(limit)
+        if not 0 <= int(index) < limit <= n:
+            raise ValueError(f"index = {index}, limit = {limit}: 0 <= index < limit <= {n}, the entries of the current schedule")
+        x = x.to(torch.float32).contiguous()
+        uc, scale = unconditional_conditioning, unconditional_guidance_scale
+        # the captured step is gated as p_sample_ddim gates its own: batched CFG or none, and t the schedule table's own entry
+        plain = uc is None or scale == 1.
+        if ((plain or uc.shape[2] == c.shape[2]) and torch.is_tensor(t) and t.dtype == torch.long
+                and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
+            done = self._invert_graph_step(unet, x, c, None if plain else uc, int(index), x0_emb, 0 if plain else cond_frames, scale,
+                                           limit)
+            if done is not None:
+                return done
+        eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        return self.ops.cfg_ddim_invert_step(eps.float().contiguous(), x, self.ddim_coef, int(index), cfg=cfg, scale=scale,
+                                             cond_f=cond_f)
+
+    @torch.no_grad()
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                       use_original_steps=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
@@ -326,11 +391,26 @@ class DDIMSampler(object):
             G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
         return self._replay_step(G, x, index, draw=seeds is None)
 
-    def _replay_step(self, G, x, index, draw=True):
+    def _invert_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, limit):
+        """One p_invert_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_invert_step_dev).
+        The captured step counts its index UPWARD and stops writing at the limit word of its static buffers; at the start of a chain
+        the host writes those two words, step[0] and limit[0], and nothing after.  None when the step cannot be captured."""
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "invert")
+        if G is None:
+            return None
+        if G["expect"] != index or G["limit_host"] != limit:
+            G["step"][:1].fill_(index)
+            G["limit"].fill_(limit)
+            G["limit_host"] = limit
+        return self._replay_step(G, x, index, draw=False, direction=1)
+
+    def _replay_step(self, G, x, index, draw=True, direction=-1):
+        """`direction`: where the captured step's last kernel leaves the counter, index - 1 for every sampling kind, index + 1 for
+        "invert"; G["expect"] follows it, so that a chain's later steps find the index they need already in device memory."""
         if draw and self.consume_rng_when_deterministic:
             torch.randn(x.shape, device=x.device)   # ddim_video.py:234 draws every step, also at sigma = 0: keep the RNG stream
         G["graph"].replay()
-        G["expect"] = index - 1
+        G["expect"] = index + direction
         if self.static_step_outputs:
             return G["x"], G["pred"]
         return G["x"].clone(), G["pred"].clone()
@@ -436,11 +516,23 @@ def _rng_update(G, eps, temperature, **kw):
                               pred_x0=G["pred"], **kw)
 
 
+def _limit_buffers(x):
+    """the word the upward counter stops at.  It is 0 through warm-up and capture, so that they write no element: the unused rows of
+    the static table hold a_prev = 0, which the inversion update divides by.  It lives in device memory because a replay's kernel
+    arguments are frozen; _invert_graph_step writes it, with the start index, once per chain."""
+    return dict(limit=torch.zeros((1,), device=x.device, dtype=torch.int32), limit_host=None)
+
+
+def _invert_update(G, eps, temperature, **kw):
+    ops.cfg_ddim_invert_step_dev(eps, G["x"], G["coef"], G["step"], G["limit"], x_next=G["x"], pred_x0=G["pred"], **kw)
+
+
 # kind (the first word of the graph-cache key) -> (its static buffers, its launches in front of seer_ddim_step_begin, its last kernel).
 # The step between the two is the same for every kind; plms.py adds "plms".
 STEP_KINDS = {"step": (lambda x: {}, (), _ddim_update),
               "step-rng": (_seed_buffers, (), _rng_update),
-              "step-mask": (_mask_buffers, (_blend,), _rng_update)}
+              "step-mask": (_mask_buffers, (_blend,), _rng_update),
+              "invert": (_limit_buffers, (), _invert_update)}
 
 
 def _refuse_sharded(unet, what: str) -> None:

@@ -1024,6 +1024,35 @@ def cfg_ddim_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, st
                                              _p(noise), _p(x_prev), _p(pred_x0), _stream()), "seer_cfg_ddim_step_dev")
 
 
+def cfg_ddim_invert_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *, cfg: bool, scale: float,
+                         cond_f: int, x_next: Optional[torch.Tensor] = None, want_pred_x0=True):
+    """DDIM inversion, one step upward: x [b, C, F_pred, h, w] at the level of a_prev of coef row `index`, eps the model's output at
+    that row's timestep -> (x_next at the level of a_t, pred_x0).  x_next may be x (include/seer_hip.h, seer_cfg_ddim_invert_step)"""
+    if x_next is None:
+        x_next = torch.empty_like(x)
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, x_prev=x_next)
+    assert x_next.dtype == torch.float32
+    if not 0 <= int(index) < coef.shape[0]:
+        raise ValueError(f"index {index}: the table has {coef.shape[0]} rows")
+    pred = torch.empty_like(x) if want_pred_x0 else None
+    check(_lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), _p(x),
+                                                _p(x_next), _p(pred), _stream()), "seer_cfg_ddim_invert_step")
+    return x_next, pred
+
+
+def cfg_ddim_invert_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, limit: torch.Tensor, *,
+                             cfg: bool, scale: float, cond_f: int, x_next: torch.Tensor, pred_x0: Optional[torch.Tensor]) -> None:
+    """last kernel of a captured inversion step: cfg_ddim_invert_step with index = step[1], then step[0] = index + 1; an index outside
+    0 .. limit[0] - 1 (limit: int32 [1] on the device) writes no latent.  x_next may be x"""
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_next)
+    _req(limit, torch.int32, "limit")
+    assert step.numel() >= 2 and limit.numel() >= 1 and x_next.dtype == torch.float32
+    _req_pred(pred_x0, x)
+    check(_lib.load().seer_cfg_ddim_invert_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step),
+                                                    _p(limit), _p(x), _p(x_next), _p(pred_x0), _stream()),
+          "seer_cfg_ddim_invert_step_dev")
+
+
 def slot_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: torch.Tensor, step: torch.Tensor, reps: int,
                     sample: torch.Tensor, t_out: torch.Tensor) -> None:
     """ddim_step_begin over slots (x [slots, C, Fp, h, w]): t_table int64 [slots, nsched] and step int32 [slots, 2] hold a schedule

@@ -121,15 +121,26 @@ def edit_t_enc(strength: float, entries: int) -> int:
 @torch.no_grad()
 def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb: torch.Tensor, empty_emb: torch.Tensor, *,
                cond_frames: int, ddim_steps: int = 30, scale: float = 7.5, strength: Optional[float] = None,
-               keep_mask: Optional[torch.Tensor] = None, seed, latent_generator: Optional[torch.Generator] = None) -> torch.Tensor:
+               keep_mask: Optional[torch.Tensor] = None, seed, latent_generator: Optional[torch.Generator] = None,
+               invert: bool = False, source_emb: Optional[torch.Tensor] = None, source_scale: float = 1.0) -> torch.Tensor:
     """Edit an existing clip.  `video` [b, 3, F, H, W] in [-1, 1] is VAE-encoded in one call (as evaluate_batch does; the posterior
     draw takes `latent_generator`); its first `cond_frames` latents condition the clip, the rest are the GIVEN latents.  Exactly one of
       strength   in (0, 1] (SDEdit): the given latents are noised to level t_enc = edit_t_enc(strength, schedule entries) by
                  sampler.stochastic_encode and denoised from there by sampler.decode(t_start=t_enc);
       keep_mask  [b, 1, F - cond_frames, H/8, W/8], 1 where the given latents are kept: masked sampling from a seeded start code.
     Every draw of the sampler comes from `seed` (an int, or one per row).  Returns the clips [b, 3, F - cond_frames, H, W] in [0, 1]
-    like generate_clips."""
-    if (strength is None) == (keep_mask is None):
+    like generate_clips.
+    `invert=True` (with `strength`; `keep_mask` is refused) replaces the re-noising by DDIM inversion: sampler.encode carries the given
+    latents up to t_enc with the model in the loop, under `source_emb` (the prompt that describes `video`; default `text_emb`) at
+    guidance `source_scale` (its unconditional branch is `empty_emb` when that scale is not 1), and sampler.decode brings them back
+    under `text_emb` at `scale`: the clip itself under the source prompt, a structure-preserving edit under another.  Nothing is
+    drawn on this path, so `seed` may be None."""
+    if invert:
+        if keep_mask is not None:
+            raise ValueError("edit_clips: invert=True inverts the whole clip; `keep_mask` belongs to masked sampling")
+        if strength is None:
+            raise ValueError("edit_clips: invert=True needs `strength`, the level the clip is inverted to")
+    elif (strength is None) == (keep_mask is None):
         raise ValueError("edit_clips: exactly one of `strength` and `keep_mask`")
     b, _, F, H, W = video.shape
     f1 = int(cond_frames)
@@ -147,6 +158,13 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
         samples, _ = sampler.sample(unet=sunet, S=ddim_steps, conditioning=c, batch_size=b, shape=given.shape[1:], x0_emb=x0_emb,
                                     verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0,
                                     is_3d=True, seed=seed, mask=keep_mask, x0=given)
+    elif invert:
+        c_src = c if source_emb is None or source_emb is text_emb else fstext_model(context=source_emb)
+        uc_src = None if source_scale == 1.0 else empty_emb.unsqueeze(1).expand(-1, c_src.shape[1], -1, -1).contiguous()
+        noised, _ = sampler.encode(sunet, given, c_src, t_enc, unconditional_guidance_scale=source_scale,
+                                   unconditional_conditioning=uc_src, x0_emb=x0_emb)
+        samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,
+                                 x0_emb=x0_emb)
     else:
         noised = sampler.stochastic_encode(given, t_enc, seed=seed)
         samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,

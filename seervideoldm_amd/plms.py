@@ -7,7 +7,8 @@ latent along frames, batched or unbatched CFG by uc's frame count, cond_frame.  
 `model.apply_model` and cannot run a SeerUNet.
 
 Same constructor, `sample(...)` keywords and return values as DDIMSampler, so ddim_sample, pipeline.generate_clips and
-pipeline.evaluate_batch take either sampler.  The schedule IS DDIMSampler.make_schedule (same tables, same 'uniform' stride).
+pipeline.evaluate_batch take either sampler.  The schedule IS DDIMSampler.make_schedule (same tables, same 'uniform' stride), and
+`encode` (DDIM inversion, first order by definition) is DDIMSampler's as it is.
 
 Kernels: CFG combine + PLMS combination + DDIM update are one fused HIP kernel (seer_cfg_plms_step; include/seer_hip.h).  With
 `unet.use_graph` on an unsharded SeerUNet every step after the first is ONE hipGraph replay -- seer_ddim_step_begin, the UNet,
