@@ -659,6 +659,42 @@ int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
                            float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state, const float* x,
                            float* x_prev, float* pred_x0, void* stream);
 
+/* CFG combine + DPM-Solver++ update of DPMSolverSampler (Lu et al. 2022, "DPM-Solver++", the data-prediction multistep solver 2M and
+ * its first-order form; eta = 0, nothing is drawn), fp32.  e is the CFG-combined eps as in seer_cfg_ddim_step (frames >= cond_f only).
+ * The step goes from the level s of schedule entry `index` (abar_s = a_t of the DDIM table) to the level t of its a_prev; with
+ * alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log(alpha / sigma), h = lambda_t - lambda_s:
+ *   D      = (x - sigma_s e) / alpha_s                                              the data prediction; pred_x0 receives it
+ *   order 1: x_prev = (sigma_t / sigma_s) x - alpha_t (exp(-h) - 1) D               (algebraically the eta = 0 DDIM update)
+ *   order 2: the same with D replaced by D + (D - d_prev) / (2 r), r = h_(index+1) / h_(index), d_prev = the D of entry index + 1
+ * The kernel evaluates no exp and no log: coef is the DPM table, fp32 [nsched][6], computed on the host in float64, one row per entry:
+ *   word 0  sigma_s          word 1  1 / alpha_s                                     D = (x - word0 e) word1
+ *   word 2  c_x = sigma_t / sigma_s        word 3  c_D1 = -alpha_t (exp(-h) - 1)     order 1: x_prev = word2 x + word3 D
+ *   word 4  c_D2 = c_D1 (1 + 1/(2r))       word 5  c_Dprev = -c_D1 / (2r)            order 2: x_prev = word2 x + word4 D + word5 d_prev
+ * The top entry of a schedule has no entry above it, so no r: its words 4 and 5 are (c_D1, 0), and a chain never runs it at order 2.
+ *   seer_cfg_dpm_step      row `index` and `order` (1 or 2) from the host.  d_prev is read at order 2 only (NULL or any contents, NaN
+ *                          included, at order 1).  x_prev may be x and pred_x0 (NULL: not written) may be d_prev: every thread reads
+ *                          its element of each before it writes it.
+ *   seer_cfg_dpm_step_dev  last kernel of a step captured whole in one hipGraph behind seer_ddim_step_begin: index = step[1], then
+ *                          step[0] = index - 1.  d_hist [b, C, F_pred, HW] is history and output at once: the D of the step before
+ *                          is read from it (order 2 only) and this step's D written over it.  state int32[4] in device memory =
+ *                          (history valid for an even index, history valid for an odd index, the sampler's order 1 or 2, nonzero
+ *                          when a schedule's final step -- index 0 -- is first order).  A step reads the valid word of its own
+ *                          index's parity and runs order 2 when that word is 1, state[2] is 2 and not (index == 0 and state[3] !=
+ *                          0), else order 1; one thread writes the valid word of parity (index - 1): 1 when this launch stored a D,
+ *                          0 when it did not.  state[2] and state[3] are only read, so no kernel reads and writes the same word and
+ *                          replays walk a schedule with no host-written scalar: to start a chain the host writes step[0] and zeroes
+ *                          state[0..1]; state[2..3] change with the sampler's settings and the schedule only.  An index outside
+ *                          0 .. nsched - 1: the two words are written all the same, no table row is read and no element written.
+ * SEER_EINVAL for a NULL required pointer (eps, x, coef, x_prev; d_prev at order 2; step, state, d_hist), b <= 0, non-positive
+ * extents, cond_f < 0 or >= F_total, nsched < 1, from the host an index outside 0 .. nsched - 1 or an order other than 1 and 2, a
+ * pointer that is not 4-byte aligned, a grid beyond one dimension. */
+int seer_cfg_dpm_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale,
+                      const float* x, const float* coef, int32_t nsched, int32_t index, int32_t order, const float* d_prev,
+                      float* x_prev, float* pred_x0 /* NULL: not written */, void* stream);
+int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                          float scale, const float* x, const float* coef, int32_t nsched, int32_t* step, int32_t* state,
+                          float* x_prev, float* d_hist, void* stream);
+
 /* The captured step over slots with a SAMPLER per slot: DDIM and PLMS clips side by side in one step (slots.py, plms=True).  The
  * buffers of the two slot entry points above, and per slot in device memory
  *   state   int32 [slots][8]: words 0..2 = (phase, valid, newest) of the slot's NEXT step, words 4..6 = the same three of the step

@@ -7,6 +7,7 @@ Importing the package never touches the GPU; the HIP library is loaded on first 
 """
 from .clip_text import CLIPTextEncoder  # noqa: F401
 from .ddim import DDIMSampler, ddim_sample  # noqa: F401
+from .dpm import DPMSolverSampler  # noqa: F401
 from .fstext import FSTextTransformer  # noqa: F401
 from .pipeline import edit_clips  # noqa: F401
 from .plms import PLMSSampler  # noqa: F401
@@ -14,5 +15,5 @@ from .slots import SlotSampler  # noqa: F401
 from .unet import SeerUNet  # noqa: F401
 from .vae import AutoencoderKL  # noqa: F401
 
-__all__ = ["SeerUNet", "DDIMSampler", "PLMSSampler", "SlotSampler", "ddim_sample", "AutoencoderKL", "FSTextTransformer",
+__all__ = ["SeerUNet", "DDIMSampler", "PLMSSampler", "DPMSolverSampler", "SlotSampler", "ddim_sample", "AutoencoderKL", "FSTextTransformer",
            "CLIPTextEncoder", "edit_clips"]

@@ -180,6 +180,8 @@ SIGNATURES = {
     "seer_cfg_plms_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp], C.c_int),
     "seer_cfg_plms_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_dpm_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_clamp01": ([_vp, _i64, _vp], C.c_int),
     "seer_gaussian_sample": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),
     # training step

@@ -18,7 +18,8 @@ runs the script with the aliases installed (`sys.argv`, `sys.path[0]` and `__mai
 `install(vae=True)` (or `SEER_COMPAT_VAE=1` with the runner) also replaces `diffusers.AutoencoderKL` by the product's VAE
 when `diffusers` is importable; without it the reference keeps its fp32 torch VAE for `vae.decode` / `vae.encode`.
 `SEER_COMPAT_SAMPLER=plms` (read by `install()`) makes the scripts sample with `PLMSSampler` under the name `DDIMSampler`: the
-yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluations).
+yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluations).  `SEER_COMPAT_SAMPLER=dpmpp` makes it
+`DPMSolverSampler` (DPM-Solver++ 2M with its defaults, one evaluation per step; INTEGRATION.md says which `ddim_steps` to pick).
 `SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
 `CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
 then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
@@ -57,6 +58,9 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
             if spec.name == "ldm.models.diffusion.ddim_video" and _sampler == "plms":
                 from seervideoldm_amd.plms import PLMSSampler
                 mod.DDIMSampler = PLMSSampler
+            if spec.name == "ldm.models.diffusion.ddim_video" and _sampler == "dpmpp":
+                from seervideoldm_amd.dpm import DPMSolverSampler
+                mod.DDIMSampler = DPMSolverSampler
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -80,7 +84,8 @@ _clip_saved = None          # (transformers module, its own CLIPTextModel) while
 
 def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
-    `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler; anything else keeps DDIMSampler.
+    `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler, "dpmpp" its DPMSolverSampler; anything else keeps
+    DDIMSampler.
     `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
     CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
     global _sampler, _clip_saved

@@ -1,7 +1,7 @@
 // The kernels at both ends of a sampler step on gfx950, fp32, one thread per latent element: "assemble the UNet input and latch the
-// counter", "CFG-combine eps and apply the DDIM, inversion or PLMS update", "re-noise the given latents".  Every form of a step --
-// host index, device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update, invert_update,
-// plms_update, known_blend_at), so an element gets the same bits from each of them.
+// counter", "CFG-combine eps and apply the DDIM, inversion, PLMS or DPM-Solver++ update", "re-noise the given latents".  Every form of
+// a step -- host index, device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update, invert_update,
+// plms_update, dpm_update, known_blend_at), so an element gets the same bits from each of them.
 #include "seer_common.h"
 #include "seer_philox.h"
 #include <cstdint>
@@ -100,6 +100,27 @@ __device__ __forceinline__ void plms_update(float e, int order, const float* h1,
     }
     step_update<NO_TERM>(ep, coef, index, x, StepNoise{}, x_prev, pred_x0, i);
     if (e_out && order != 1) e_out[i] = e;
+}
+
+// CFG + DPM-Solver++ update (first order, or second order multistep "2M"; eta = 0).  e = the CFG-combined eps; row = the schedule
+// entry's six words of the DPM table (include/seer_hip.h, seer_cfg_dpm_step): (sigma_s, 1/alpha_s, c_x, c_D1, c_D2, c_Dprev), every
+// exp and log of the exponential integrator folded into them on the host.  D = (x - sigma_s e) / alpha_s is the data prediction;
+//   order 1: x_prev = c_x x + c_D1 D                      order 2: x_prev = c_x x + c_D2 D + c_Dprev d_prev[i]
+// d_prev (the D of the step before) is read at order 2 only: at order 1 it may be NULL or hold anything, NaN included.  x may alias
+// x_prev and d_prev may alias pred_x0, which receives D: every thread reads its element of each before it writes it.
+enum { DPM_ROW_WORDS = 6 };
+
+__device__ __forceinline__ void dpm_update(float e, const float* __restrict__ row, int order, const float* x, const float* d_prev,
+                                           float* x_prev, float* pred_x0, int64_t i) {
+    const float xv = x[i];
+    const float d = (xv - row[0] * e) * row[1];
+    if (order == 2) {
+        const float dp = d_prev[i];
+        x_prev[i] = row[2] * xv + row[4] * d + row[5] * dp;
+    } else {
+        x_prev[i] = row[2] * xv + row[3] * d;
+    }
+    if (pred_x0) pred_x0[i] = d;
 }
 
 // ---- one clip batch: the schedule index from the host, or in DEVICE memory (a whole p_sample_ddim captured in one hipGraph: the
@@ -201,6 +222,31 @@ __global__ void cfg_plms_dev_kernel(const float* __restrict__ eps, int cfg, int 
     const float* h3 = ring + (int64_t)slot * n;
     plms_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), valid == 0 ? 0 : valid + 1, h1, h2, h3, i, coef, index,
                 x, x_prev, pred_x0, ring + (int64_t)slot * n);
+}
+
+// The DPM-Solver++ step.  step == nullptr: the host's `index` and `order`.  Else the captured form: index = step[1], and the order comes
+// from state int32[4] = (history valid for an even index, for an odd one, the sampler's order, whether a schedule's final step is first
+// order): order 2 when the word of the index's parity is 1, state[2] is 2 and not (index == 0 and state[3] != 0), else order 1.  One
+// thread writes step[0] = index - 1 and the valid word of parity (index - 1): 1 when this launch stores a D, 0 when it does not.
+// state[2] and state[3] are only read: no kernel reads and writes the same word.  The history is pred_x0 itself (d_prev == pred_x0 in
+// that form).  An index outside 0 .. nsched - 1 reads no table row and writes no element.
+__global__ void cfg_dpm_kernel(const float* __restrict__ eps, int cfg, int b, int C, int Ft, int cond_f, int HW, float scale,
+                               const float* __restrict__ coef, int nsched, int index, int order, int* __restrict__ step,
+                               int* __restrict__ state, const float* x, const float* d_prev, float* x_prev, float* pred_x0) {
+    const int64_t n = (int64_t)b * C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step) {
+        index = step[1];
+        const bool in_table = index >= 0 && index < nsched;
+        order = state[index & 1] == 1 && state[2] == 2 && !(index == 0 && state[3] != 0) ? 2 : 1;
+        if (i == 0) {
+            step[0] = index - 1;
+            state[(index - 1) & 1] = in_table ? 1 : 0;
+        }
+    }
+    if (index < 0 || index >= nsched || i >= n) return;
+    dpm_update(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), coef + DPM_ROW_WORDS * index, order, x, d_prev, x_prev, pred_x0,
+               i);
 }
 
 // ---- the captured step over SLOTS (continuous batching, seervideoldm_amd/slots.py): per-slot forms of ddim_assemble_kernel and
@@ -488,6 +534,27 @@ extern "C" int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, 
         return SEER_EINVAL;
     return launch_per_element(cfg_plms_dev_kernel, elements(b, C, F_total - cond_f, HW), {}, stream, eps, cfg, b, C, F_total, cond_f, HW,
                               scale, coef, step, ring, ring_state, x, x_prev, pred_x0);
+}
+
+extern "C" int seer_cfg_dpm_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                 float scale, const float* x, const float* coef, int32_t nsched, int32_t index, int32_t order,
+                                 const float* d_prev, float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !x || !coef || !x_prev || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || nsched < 1 || index < 0 ||
+        index >= nsched || (order != 1 && order != 2) || (order == 2 && !d_prev))
+        return SEER_EINVAL;
+    return launch_per_element(cfg_dpm_kernel, elements(b, C, F_total - cond_f, HW), {eps, x, coef, d_prev, x_prev, pred_x0}, stream, eps,
+                              cfg, b, C, F_total, cond_f, HW, scale, coef, nsched, index, order, nullptr, nullptr, x, d_prev, x_prev,
+                              pred_x0);
+}
+
+extern "C" int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                     float scale, const float* x, const float* coef, int32_t nsched, int32_t* step, int32_t* state,
+                                     float* x_prev, float* d_hist, void* stream) {
+    if (!eps || !x || !coef || !step || !state || !x_prev || !d_hist || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) ||
+        nsched < 1)
+        return SEER_EINVAL;
+    return launch_per_element(cfg_dpm_kernel, elements(b, C, F_total - cond_f, HW), {eps, x, coef, step, state, x_prev, d_hist}, stream,
+                              eps, cfg, b, C, F_total, cond_f, HW, scale, coef, nsched, 0, 1, step, state, x, d_hist, x_prev, d_hist);
 }
 
 extern "C" int seer_slot_step_begin(const float* x0_emb, const float* x, int32_t slots, int32_t reps, int32_t C, int32_t f1,

@@ -77,13 +77,13 @@ class DDIMSampler(object):
             # are not on this path
             raise NotImplementedError(f"schedule {beta_schedule!r} / discretisation {ddim_discretize!r}: this path has the "
                                       "'linear' (sqrt-space) betas and the 'uniform' stride only")
-        self.ddim_timesteps = _strided_timesteps(ddim_num_steps, self.ddpm_num_timesteps)
-        if verbose:
-            print(f"DDIM timesteps ({len(self.ddim_timesteps)}): {self.ddim_timesteps}")
         betas = np.asarray(given_betas, dtype=np.float64) if given_betas is not None else _betas(timesteps, linear_start, linear_end)
         alphas_cumprod = np.cumprod(1. - betas, axis=0)
         assert alphas_cumprod.shape[0] == self.ddpm_num_timesteps, "alphas have to be defined for each timestep"
         ac32 = torch.tensor(alphas_cumprod, dtype=torch.float32)
+        self.ddim_timesteps = self._sampling_timesteps(ddim_num_steps, ac32)
+        if verbose:
+            print(f"DDIM timesteps ({len(self.ddim_timesteps)}): {self.ddim_timesteps}")
         self.betas = torch.tensor(betas, dtype=torch.float32)
         self.alphas_cumprod = ac32
         self.alphas_cumprod_prev = torch.tensor(np.append(1., alphas_cumprod[:-1]), dtype=torch.float32)
@@ -97,6 +97,11 @@ class DDIMSampler(object):
         coef = np.stack([self.ddim_alphas, self.ddim_alphas_prev, self.ddim_sigmas, self.ddim_sqrt_one_minus_alphas], 1)
         self.ddim_coef = torch.tensor(coef, dtype=torch.float32, device=self.device)     # ONE upload per schedule
         self._t_table = torch.tensor(ts, dtype=torch.long, device=self.device)
+
+    def _sampling_timesteps(self, n_sample: int, alphas_cumprod: torch.Tensor) -> np.ndarray:
+        """the training steps a schedule of n_sample steps visits, ascending: the reference's 'uniform' stride.  `alphas_cumprod` is
+        the fp32 table of every training step, for a sampler that places its steps by noise level (dpm.py)."""
+        return _strided_timesteps(n_sample, self.ddpm_num_timesteps)
 
     @torch.no_grad()
     def sample(self, unet, S, batch_size, shape, x0_emb=None, conditioning=None, callback=None, normals_sequence=None,
@@ -528,7 +533,7 @@ def _invert_update(G, eps, temperature, **kw):
 
 
 # kind (the first word of the graph-cache key) -> (its static buffers, its launches in front of seer_ddim_step_begin, its last kernel).
-# The step between the two is the same for every kind; plms.py adds "plms".
+# The step between the two is the same for every kind; plms.py adds "plms", dpm.py "dpm".
 STEP_KINDS = {"step": (lambda x: {}, (), _ddim_update),
               "step-rng": (_seed_buffers, (), _rng_update),
               "step-mask": (_mask_buffers, (_blend,), _rng_update),

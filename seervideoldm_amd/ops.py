@@ -1314,6 +1314,53 @@ def cfg_plms_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, st
           "seer_cfg_plms_step_dev")
 
 
+DPM_ROW_WORDS = 6      # fp32 words of a row of the DPM-Solver++ table (include/seer_hip.h, seer_cfg_dpm_step)
+
+
+def _req_dpm_table(coef: torch.Tensor) -> int:
+    assert coef.is_contiguous() and coef.dim() == 2 and coef.shape[1] == DPM_ROW_WORDS
+    return coef.shape[0]
+
+
+def cfg_dpm_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, order: int, *, cfg: bool, scale: float,
+                 cond_f: int, d_prev: Optional[torch.Tensor] = None, x_prev: Optional[torch.Tensor] = None,
+                 pred_x0: Optional[torch.Tensor] = None, want_pred_x0=True):
+    """eps [2b or b, C, F_total, h, w] fp32 ; x [b, C, F_pred, h, w] fp32 ; coef the DPM table [nsched, 6] -> (x_prev, pred_x0), the
+    DPM-Solver++ step of `order` 1 or 2 with row `index`.  d_prev (the pred_x0 of the step before) is read at order 2 only; x_prev
+    may be x and pred_x0 may be d_prev (include/seer_hip.h, seer_cfg_dpm_step)."""
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f)
+    nsched, order = _req_dpm_table(coef), int(order)
+    if order not in (1, 2):
+        raise ValueError(f"order {order}: 1 or 2")
+    if not 0 <= int(index) < nsched:
+        raise ValueError(f"index {index}: the table has {nsched} rows")
+    if order == 2 and d_prev is None:
+        raise ValueError("order 2 reads d_prev, the data prediction of the step before")
+    x_prev = torch.empty_like(x) if x_prev is None else x_prev
+    pred = (torch.empty_like(x) if want_pred_x0 else None) if pred_x0 is None else pred_x0
+    for name, tt in (("d_prev", d_prev), ("x_prev", x_prev), ("pred_x0", pred)):
+        if tt is not None:
+            _req(tt, torch.float32, name)
+            assert tt.is_contiguous() and tt.shape == x.shape
+    check(_lib.load().seer_cfg_dpm_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(x), _p(coef), nsched, int(index),
+                                        order, _p(d_prev), _p(x_prev), _p(pred), _stream()), "seer_cfg_dpm_step")
+    return x_prev, pred
+
+
+def cfg_dpm_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, state: torch.Tensor, *, cfg: bool,
+                     scale: float, cond_f: int, x_prev: torch.Tensor, d_hist: torch.Tensor) -> None:
+    """last kernel of a captured DPM-Solver++ step: cfg_dpm_step with index = step[1] and the order taken from state int32[4] =
+    (history valid by index parity, twice; the sampler's order; final step first order); d_hist holds the step before's pred_x0 and
+    receives this step's; step[0] = index - 1; x_prev may be x (include/seer_hip.h, seer_cfg_dpm_step_dev)"""
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
+    nsched = _req_dpm_table(coef)
+    _req(state, torch.int32, "state"); _req(d_hist, torch.float32, "d_hist")
+    assert step.numel() >= 2 and state.is_contiguous() and state.numel() >= 4
+    assert d_hist.is_contiguous() and d_hist.shape == x.shape and x_prev.dtype == torch.float32
+    check(_lib.load().seer_cfg_dpm_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(x), _p(coef), nsched, _p(step),
+                                            _p(state), _p(x_prev), _p(d_hist), _stream()), "seer_cfg_dpm_step_dev")
+
+
 def clamp01_(x: torch.Tensor) -> torch.Tensor:
     _req(x, torch.float32, "x")
     assert x.is_contiguous()
