@@ -15,9 +15,7 @@
 //   No S x S matrix, no P round trip through LDS.
 // LDS images: K rows padded to an odd number of 16-byte chunks (conflict-free ds_read_b128 by key row);
 //             V row stride == 64 or 192 (mod 256) bytes (conflict-free transposed reads of 4 key rows).
-#include "seer_common.h"
-
-int seer_attn40_launch(const seer_attn_desc& d, int ws_log2, hipStream_t st);   // attention40.hip
+#include "attn_common.h"
 
 namespace {
 
@@ -34,51 +32,15 @@ namespace {
 #define SEER_ATTN_PIPE_MAXD 0
 #endif
 
-constexpr int KT = 64;            // keys per LDS tile
+constexpr int KT = ATTN_KT;       // keys per LDS tile
 constexpr float kNegInf = -__builtin_inff();
 
 template <int D>
-struct AttnCfg {
-    static constexpr int DP = (D + 15) / 16 * 16;      // contraction length of QK^T (zero padded)
-    static constexpr int KSTEPS = DP / 16;
-    static constexpr int NDT = (D + 31) / 32;          // 32-row d tiles of O^T
-    static constexpr int DV = NDT * 32;
-    static constexpr int KRS = DP + 8;                 // K row stride (elements): odd number of 16-B chunks
-    static constexpr int VRS = DV < 96 ? 96 : DV;      // V row stride (elements): 192 B or 320 B
-    static constexpr int CH = D / 8;                   // 16-byte chunks per row in global memory
-    static constexpr int NCH = (KT * CH + 255) / 256;  // chunks per thread per tile (K or V)
-    static constexpr int BUF = KT * (KRS + VRS);          // elements per K|V buffer (two buffers: ping-pong)
+struct AttnCfg : AttnGeom<D> {                         // K rows at the padded stride RS (conflict-free ds_read_b128 by key row)
+    using G = AttnGeom<D>;
+    static constexpr int VRS = G::DV < 96 ? 96 : G::DV;   // V row stride (elements): 192 B or 320 B
+    static constexpr int BUF = KT * (G::RS + VRS);        // elements per K|V buffer (two buffers: ping-pong)
     static constexpr size_t LDS_BYTES = (size_t)2 * BUF * 2;
-};
-
-// v_permlane32_swap a, b:  a' = [a.lo | b.lo], b' = [a.hi | b.hi]; with a = b = v every lane sees both halves' values.
-// Inline asm, not __builtin_amdgcn_permlane32_swap: hipcc (ROCm 7.2) returns the builtin's FIRST result for both elements of
-// its result pair (scripts/lab_probe3.cpp prints it), so max(r[0], r[1]) silently dropped the other half's 16 keys from the
-// running maximum.  Mild scores hide that (any reference near the maximum is fine); scores 130+ log2 units apart
-// overflowed exp2 and gave NaN rows -- found by the sharp-softmax cases of scripts/lab_attn.cpp / tests/test_gpu_kernels.py.
-// The s_nop pair covers the VALU-write -> permlane-read hazard, which nobody pads inside an asm statement.
-__device__ __forceinline__ float xhalf_max(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float lower_half_value(float v) {      // value of lane (l & 31) in every lane l
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a;
-}
-
-struct TokMap {
-    int ws_log2;   // -1: identity
-    int HW, W_, wy0, wx0;
-    __device__ __forceinline__ int operator()(int pos) const {
-        if (ws_log2 < 0) return pos;
-        const int ws2 = 2 * ws_log2;
-        const int f = pos >> ws2;
-        const int rem = pos & ((1 << ws2) - 1);
-        const int wy = rem >> ws_log2, wx = rem & ((1 << ws_log2) - 1);
-        return f * HW + (wy0 + wy) * W_ + wx0 + wx;
-    }
 };
 
 // DBUF: ping-pong K|V LDS buffers (one barrier per tile) vs one buffer (two barriers, half the LDS).
@@ -95,7 +57,7 @@ template <int D, bool DBUF, bool F16 = false, bool LSE = false>
 __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, const int ws_log2, const float defer_thr) {
     using C = AttnCfg<D>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16* const lds = reinterpret_cast<bf16*>(smem);    // 2 x { K [KT][KRS], V [KT][VRS] }
+    bf16* const lds = reinterpret_cast<bf16*>(smem);    // 2 x { K [KT][RS], V [KT][VRS] }
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // scalar: tile / mask decisions are wave-uniform branches
@@ -109,20 +71,8 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
 
     // ---- batch decode
     const int y = blockIdx.y;
-    const int head = y % p.heads;
-    int b = y / p.heads;
-    TokMap tok;
-    tok.ws_log2 = ws_log2;
-    tok.HW = p.H * p.W;
-    tok.W_ = p.W;
-    tok.wy0 = tok.wx0 = 0;
-    if (ws_log2 >= 0) {
-        const int win = b / p.batch;
-        b = b - win * p.batch;
-        const int nwx = p.W >> ws_log2;
-        tok.wy0 = (win / nwx) << ws_log2;
-        tok.wx0 = (win % nwx) << ws_log2;
-    }
+    int head, b;
+    const AttnTokMap tok = attn_block_origin(p, ws_log2, y, head, b);
     const bf16* __restrict__ Qg = reinterpret_cast<const bf16*>(p.Q) + (int64_t)b * p.q_bs + head * (p.q_hs ? p.q_hs : D);
     const bf16* __restrict__ Kg = reinterpret_cast<const bf16*>(p.K) + (int64_t)b * p.k_bs + head * (p.k_hs ? p.k_hs : D);
     const bf16* __restrict__ Vg = reinterpret_cast<const bf16*>(p.V) + (int64_t)b * p.v_bs + head * (p.v_hs ? p.v_hs : D);
@@ -137,14 +87,14 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
     // ---- zero the K pad columns once (D=40: elements 40..47 take part in the contraction)
     if constexpr (C::DP != D) {
         for (int r = tid; r < (DBUF ? 2 : 1) * KT; r += 256) {
-            bf16* kb_ = lds + (r / KT) * C::BUF + (r % KT) * C::KRS + (C::DP - 8);
+            bf16* kb_ = lds + (r / KT) * C::BUF + (r % KT) * C::RS + (C::DP - 8);
             *reinterpret_cast<u32x4*>(kb_) = u32x4{0u, 0u, 0u, 0u};
         }
     }
     // ---- V pad column D = 1.0 (never overwritten: the tile commits only write columns < D)
     if constexpr (LSUM_MFMA) {
         for (int r = tid; r < (DBUF ? 2 : 1) * KT; r += 256)
-            lds[(r / KT) * C::BUF + KT * C::KRS + (r % KT) * C::VRS + D] = to16<F16>(1.0f);
+            lds[(r / KT) * C::BUF + KT * C::RS + (r % KT) * C::VRS + D] = to16<F16>(1.0f);
     }
 
     // ---- Q fragments (B operand: col = query, k = 8h + j inside each 16-wide step)
@@ -183,35 +133,9 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
     }
     const int ntiles = (k_end + KT - 1) / KT;
 
-    u32x4 kreg[C::NCH], vreg[C::NCH];
-    auto prefetch = [&](int t) {
-        const int kt0 = t * KT;
-#pragma unroll
-        for (int i = 0; i < C::NCH; ++i) {
-            const int idx = tid + 256 * i;
-            if (idx < KT * C::CH) {
-                const int key = idx / C::CH, ch = idx - key * C::CH;
-                int kg = kt0 + key;
-                kg = kg < p.Sk ? kg : p.Sk - 1;
-                const int64_t tk = tok(kg);
-                kreg[i] = *reinterpret_cast<const u32x4*>(Kg + tk * p.k_ss + ch * 8);
-                vreg[i] = *reinterpret_cast<const u32x4*>(Vg + tk * p.v_ss + ch * 8);
-            }
-        }
-    };
-    auto commit = [&](int buf) {
-        bf16* Ks = lds + buf * C::BUF;
-        bf16* Vs = Ks + KT * C::KRS;
-#pragma unroll
-        for (int i = 0; i < C::NCH; ++i) {
-            const int idx = tid + 256 * i;
-            if (idx < KT * C::CH) {
-                const int key = idx / C::CH, ch = idx - key * C::CH;
-                *reinterpret_cast<u32x4*>(Ks + key * C::KRS + ch * 8) = kreg[i];
-                *reinterpret_cast<u32x4*>(Vs + key * C::VRS + ch * 8) = vreg[i];
-            }
-        }
-    };
+    AttnStager<D> stage;
+    auto prefetch = [&](int t) { stage.prefetch(tid, tok, Kg, p.k_ss, Vg, p.v_ss, t * KT, p.Sk); };
+    auto commit = [&](int buf) { stage.commit(tid, lds + buf * C::BUF, C::RS, lds + buf * C::BUF + KT * C::RS, C::VRS); };
 
     // ping-pong: tile t is computed from buffer t&1 while tile t+1 travels global -> registers; it is written to the other
     // buffer after the compute (its last readers passed the previous barrier).  One barrier per tile.
@@ -233,7 +157,7 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
         if (t + 1 < ntiles) prefetch(t + 1);
 #endif
         const bf16* Ks = lds + (DBUF ? (t & 1) : 0) * C::BUF;
-        const bf16* Vs = Ks + KT * C::KRS;
+        const bf16* Vs = Ks + KT * C::RS;
         const int kt0 = t * KT;
         // The two 32-key sub tiles of the LDS tile, one after the other -- or (SEER_ATTN_PIPE_MAXD, off by default) both QK^T
         // products first so that the matrix pipe works on sub tile 1 under the softmax of sub tile 0.
@@ -247,7 +171,7 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
             f32x16 sacc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) sacc[r] = 0.f;
-            const bf16* krow = Ks + (sub * 32 + lq) * C::KRS + 8 * lh;
+            const bf16* krow = Ks + (sub * 32 + lq) * C::RS + 8 * lh;
             bf16x8 kf[C::KSTEPS];            // all K fragments first: one exposed LDS latency per sub tile, not one per step
 #pragma unroll
             for (int s = 0; s < C::KSTEPS; ++s) kf[s] = *reinterpret_cast<const bf16x8*>(krow + 16 * s);
@@ -332,15 +256,7 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
             for (int s2 = 0; s2 < 2; ++s2) {
 #pragma unroll
                 for (int tt = 0; tt < C::NDT; ++tt) {
-                    const bf16* a0 = vbase + (16 * s2) * C::VRS + 32 * tt;
-                    const bf16* a1 = a0 + 8 * C::VRS;
-                    const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(a0));
-                    const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                        (__attribute__((address_space(3))) bf16x4*)(a1));
-                    bf16x8 vf;
-                    vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-                    vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
+                    const bf16x8 vf = tr_frag(vbase + (16 * s2) * C::VRS + 32 * tt, 8 * C::VRS);
 #if SEER_ATTN_PROBE & 2
                     oacc[tt][s2] += (float)vf[0] + (float)pf[s2][tt];
 #else
@@ -401,9 +317,7 @@ __global__ void __launch_bounds__(256) seer_attn_kernel(const seer_attn_desc p, 
 
 template <int D, bool DBUF, bool F16 = false, bool LSE = false>
 int launch_attn2(const seer_attn_desc& d, int ws_log2, float thr, hipStream_t st) {
-    int nbatch = d.batch;
-    if (ws_log2 >= 0) nbatch *= (d.H >> ws_log2) * (d.W >> ws_log2);
-    dim3 grid((d.Sq + 127) / 128, nbatch * d.heads, 1);
+    dim3 grid((d.Sq + 127) / 128, attn_launch_batches(d, ws_log2) * d.heads, 1);
     constexpr size_t lds = AttnCfg<D>::LDS_BYTES / (DBUF ? 1 : 2);
     static_assert(lds <= 64 * 1024, "above the default dynamic-LDS limit: would need a hipFuncSetAttribute opt-in");
     hipLaunchKernelGGL((seer_attn_kernel<D, DBUF, F16, LSE>), grid, dim3(256), lds, st, d, ws_log2, thr);
@@ -440,16 +354,10 @@ extern "C" int seer_attn_fwd(const seer_attn_desc* desc, void* stream) {
     if ((d.q_ss | d.k_ss | d.v_ss) % 8 || d.o_ss % 4) return SEER_EINVAL;
     if ((d.q_bs | d.k_bs | d.v_bs) % 8 || d.o_bs % 4) return SEER_EINVAL;
     if ((d.q_hs | d.k_hs | d.v_hs) % 8 || d.q_hs < 0 || d.k_hs < 0 || d.v_hs < 0) return SEER_EINVAL;
-    int ws_log2 = -1;
-    if (d.window_ws > 0) {
-        if (d.window_ws != 4 && d.window_ws != 8) return SEER_EINVAL;
-        ws_log2 = d.window_ws == 4 ? 2 : 3;
-        if (d.H % d.window_ws || d.W % d.window_ws) return SEER_EINVAL;
-        if (d.Fq <= 0 || d.Sq != d.Fq * d.window_ws * d.window_ws || d.Sk != d.F * d.window_ws * d.window_ws) return SEER_EINVAL;
-    }
+    int ws_log2;
+    if (attn_check_addressing(d, &ws_log2, false) != SEER_OK) return SEER_EINVAL;
     if (d.variant < 0 || d.variant > 7 || d.variant == 4) return SEER_EINVAL;
     if ((d.variant == 2 || d.variant == 3 || d.variant == 5 || d.variant == 7) && d.head_dim != 40) return SEER_EINVAL;
-    if (d.causal_offset < 0 || (d.causal && d.Sq + d.causal_offset > d.Sk)) return SEER_EINVAL;
     if ((d.flags & SEER_ATTN_F16) && (d.lse || (d.variant != 0 && d.variant != 1 && d.variant != 5))) return SEER_EINVAL;      // inference
     switch (d.head_dim) {
         case 40:

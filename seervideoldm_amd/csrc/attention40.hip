@@ -29,7 +29,7 @@
 //     (ds_read_b64_tr_b16) bank-conflict free on 80-byte rows.
 //   * blocks are handed out in XCD-contiguous chunks so that the heads of one frame (adjacent columns of the fused q|k|v
 //     rows) meet in one L2.
-#include "seer_common.h"
+#include "attn_common.h"
 
 namespace {
 
@@ -42,19 +42,6 @@ constexpr int A40_ZBYTES = 1472;                    // constant region: zeros wi
 constexpr float A40_NEG_INF = -__builtin_inff();
 constexpr float A40_THR = 16.0f;                    // TRACK: re-base when a score exceeds the reference by 2^16
 constexpr float A40_THR_F16 = 14.0f;                // ... by 2^14 on IEEE-half operands (P <= 2^14: the half range ends at 2^16)
-
-struct TokMap40 {
-    int ws_log2;   // -1: identity
-    int HW, W_, wy0, wx0;
-    __device__ __forceinline__ int operator()(int pos) const {
-        if (ws_log2 < 0) return pos;
-        const int ws2 = 2 * ws_log2;
-        const int f = pos >> ws2;
-        const int rem = pos & ((1 << ws2) - 1);
-        const int wy = rem >> ws_log2, wx = rem & ((1 << ws_log2) - 1);
-        return f * HW + (wy0 + wy) * W_ + wx0 + wx;
-    }
-};
 
 // a half-representable value >= x, at most one half ulp above it (x finite, |x| < 60000): the softmax reference of the half form
 __device__ __forceinline__ float f16_ceil(float x) {
@@ -75,19 +62,6 @@ __device__ __forceinline__ float bf16_ceil(float x) {
     unsigned u = __builtin_bit_cast(unsigned, x);
     if (!(u >> 31)) u += 0xffffu;        // positive: round the magnitude up; negative: truncation already rounds up
     return __builtin_bit_cast(float, u & 0xffff0000u);
-}
-// v_permlane32_swap a, b:  a' = [a.lo | b.lo], b' = [a.hi | b.hi].  Inline asm: the second result of
-// __builtin_amdgcn_permlane{16,32}_swap is not reliable with hipcc ROCm 7.2 (see attention.hip, scripts/lab_probe3.cpp);
-// the s_nops are the VALU -> permlane hazard, which nobody pads inside an asm statement.
-__device__ __forceinline__ float xhalf_max40(float v) {
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float lower_half_value40(float v) {      // value of lane (l & 31) in every lane l
-    float a = v, b = v;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 1" : "+v"(a), "+v"(b));
-    return a;
 }
 
 // LDS fragment reads in inline asm.  hipcc (ROCm 7.2) orders every LDS load it can see behind ALL pending LDS-DMA
@@ -242,20 +216,8 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
     }
     const int qblk = wg % nqb;
     const int y = wg / nqb;
-    const int head = y % p.heads;
-    int b = y / p.heads;
-    TokMap40 tok;
-    tok.ws_log2 = ws_log2;
-    tok.HW = p.H * p.W;
-    tok.W_ = p.W;
-    tok.wy0 = tok.wx0 = 0;
-    if (ws_log2 >= 0) {
-        const int win = b / p.batch;
-        b = b - win * p.batch;
-        const int nwx = p.W >> ws_log2;
-        tok.wy0 = (win / nwx) << ws_log2;
-        tok.wx0 = (win % nwx) << ws_log2;
-    }
+    int head, b;
+    const AttnTokMap tok = attn_block_origin(p, ws_log2, y, head, b);
     const bf16* __restrict__ Qg = reinterpret_cast<const bf16*>(p.Q) + (int64_t)b * p.q_bs + head * (p.q_hs ? p.q_hs : D);
     const bf16* __restrict__ Kg = reinterpret_cast<const bf16*>(p.K) + (int64_t)b * p.k_bs + head * (p.k_hs ? p.k_hs : D);
     const bf16* __restrict__ Vg = reinterpret_cast<const bf16*>(p.V) + (int64_t)b * p.v_bs + head * (p.v_hs ? p.v_hs : D);
@@ -457,7 +419,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
                     float mx = s[0];
 #pragma unroll
                     for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-                    mx = xhalf_max40(mx);
+                    mx = xhalf_max(mx);
                     set_ref(qb, mx == A40_NEG_INF ? 0.f : (F16 ? f16_ceil(mx) : bf16_ceil(mx)));
                 }
             }
@@ -559,7 +521,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
                         float mx = s[0];
 #pragma unroll
                         for (int r = 1; r < 16; ++r) mx = fmaxf(mx, s[r]);
-                        mx = xhalf_max40(mx);
+                        mx = xhalf_max(mx);
                         constexpr float THR = F16 ? A40_THR_F16 : A40_THR;
                         if (!__all(mx <= THR)) {
                             const float m_new = mx > THR ? (F16 ? f16_ceil(m_run[qb] + mx) : bf16_ceil(m_run[qb] + mx)) : m_run[qb];
@@ -618,7 +580,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
         bool ok = true;
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
-            const float l = lower_half_value40(oacc[qb][1][4]);
+            const float l = lower_half_value(oacc[qb][1][4]);
             float z = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) z = fmaf(oacc[qb][0][r], 0.f, z);
@@ -643,7 +605,7 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
     unsigned char* ost = stage_a + wave * (QW * A40_ROWB);
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
-        const float l = lower_half_value40(oacc[qb][1][4]);
+        const float l = lower_half_value(oacc[qb][1][4]);
         const float inv = l > 0.f ? 1.0f / l : 0.f;
         const int qi = q0w + 32 * qb + lq;
         // training: log2-domain log-sum-exp of the scaled scores, read back by seer_attn_bwd
@@ -677,63 +639,62 @@ __global__ void __launch_bounds__(256, (QB == 1 && NST == 2) ? 3 : 2) seer_attn4
     A40_STAMP();
 }
 
-}  // namespace
+// one launchable form of seer_attn40_kernel, its template arguments packed into an int
+constexpr int a40_form(int qb, bool track, bool plain, int nst = 2, bool f16 = false, bool lse = false) {
+    return qb | track << 2 | plain << 3 | (nst == 3) << 4 | f16 << 5 | lse << 6;
+}
 
-// called by seer_attn_fwd (attention.hip) for head_dim 40.  Two shapes: 32 queries per wave, 128 per workgroup, three workgroups
+// The form a descriptor gets, or SEER_EINVAL / SEER_ENOSYS.  Two shapes: 32 queries per wave, 128 per workgroup, three workgroups
 // per CU; and 64 queries per wave, 256 per workgroup, two workgroups per CU (under the three-workgroup register bound that form
 // spilled at 168 registers and measured 10-20 % slower, profiles/r02_attn40_variants.log; at its own 240 it does not).
 // variant 5, or lse != NULL, runs the tracked form directly.
-int seer_attn40_launch(const seer_attn_desc& d, int ws_log2, hipStream_t st) {
-    int nbatch = d.batch;
-    if (ws_log2 >= 0) nbatch *= (d.H >> ws_log2) * (d.W >> ws_log2);
+int a40_choose(const seer_attn_desc& d, int ws_log2, int nbatch) {
     // the LDS-DMA plan addresses K / V rows by 32-bit byte offsets from the (batch, head) base
-    {
-        const int64_t ntok = ws_log2 >= 0 ? (int64_t)d.F * d.H * d.W : (int64_t)d.Sk;
-        if (ntok * (d.k_ss > d.v_ss ? d.k_ss : d.v_ss) * 2 >= (int64_t)1 << 32) return SEER_ENOSYS;
-    }
+    const int64_t ntok = ws_log2 >= 0 ? (int64_t)d.F * d.H * d.W : (int64_t)d.Sk;
+    if (ntok * (d.k_ss > d.v_ss ? d.k_ss : d.v_ss) * 2 >= (int64_t)1 << 32) return SEER_ENOSYS;
     const bool track = d.variant == 5 || d.lse != nullptr;
     const bool plain = ws_log2 < 0 && !d.causal && d.causal_offset == 0;
-    if (d.flags & SEER_ATTN_F16) {          // IEEE-half operands: the tracked form (32 queries per wave), nothing else
-        const int nqbh = (d.Sq + 127) / 128;
-        dim3 gridh((unsigned)(nqbh * nbatch * d.heads));
-        if (plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true, 2, true>), gridh, dim3(256), 0, st, d, ws_log2, nqbh);
-        else hipLaunchKernelGGL((seer_attn40_kernel<1, true, false, 2, true>), gridh, dim3(256), 0, st, d, ws_log2, nqbh);
-        SEER_LAUNCH_CHECK();
-        return SEER_OK;
-    }
+    // IEEE-half operands: the tracked form (32 queries per wave), nothing else
+    if (d.flags & SEER_ATTN_F16) return a40_form(1, true, plain, 2, true);
     // 64 queries per wave: K / V fragments, LDS-DMA issue and barriers are shared by two query blocks, and the two blocks are
     // software-pipelined (both Q K^T chains first, then block 0's exponentials under block 1's chain, block 0's P V under block
     // 1's exponentials); 240 registers, two waves per SIMD.  [192, 1024, 40]: 53.2 vs 56.3 us, [192, 4096, 40]: 582 vs 643 us
     // (profiles/r03_lab_attn_qb2.log).  Taken by non-causal launches that fill at least one round of the 512 resident workgroups;
     // variant 2 forces it, variant 3 the 32-query form (A/B runs, tests)
-    const int nqb2 = (d.Sq + 255) / 256;
+    const bool fills = d.variant == 0 && (long)((d.Sq + 255) / 256) * nbatch * d.heads >= 512;
     // the 64-query form on a three-stage ring: whole tiles only (RING_FAST).  [192, 1024, 40] 54.1 -> 50.6 us, [192, 4096, 40]
     // 583 -> 566 us back to back (profiles/r05_attn40_ring.log); variant 7 forces it, variant 2 keeps the two-stage form (A/B runs)
     const bool ring_ok = plain && d.Sq % 256 == 0 && d.Sk % A40_KT == 0;
     if (d.variant == 7 && (track || !ring_ok)) return SEER_EINVAL;
-    if (!track && ring_ok && (d.variant == 7 || (d.variant == 0 && (long)nqb2 * nbatch * d.heads >= 512))) {
-        dim3 grid7((unsigned)(nqb2 * nbatch * d.heads));
-        hipLaunchKernelGGL((seer_attn40_kernel<2, false, true, 3>), grid7, dim3(256), 0, st, d, ws_log2, nqb2);
-        SEER_LAUNCH_CHECK();
-        return SEER_OK;
-    }
+    if (!track && ring_ok && (d.variant == 7 || fills)) return a40_form(2, false, true, 3);
     // (plain launches only: under a causal mask the 64-query wave does the work of its later query block for the earlier
     //  one too -- temporal window block 47 vs 36 us)
-    if (!track && (d.variant == 2 || (d.variant == 0 && plain && (long)nqb2 * nbatch * d.heads >= 512))) {
-        dim3 grid2((unsigned)(nqb2 * nbatch * d.heads));
-        if (plain) hipLaunchKernelGGL((seer_attn40_kernel<2, false, true>), grid2, dim3(256), 0, st, d, ws_log2, nqb2);
-        else hipLaunchKernelGGL((seer_attn40_kernel<2, false, false>), grid2, dim3(256), 0, st, d, ws_log2, nqb2);
-        SEER_LAUNCH_CHECK();
-        return SEER_OK;
-    }
-    const int nqb = (d.Sq + 127) / 128;
-    dim3 grid((unsigned)(nqb * nbatch * d.heads));
-    if (track && d.lse && plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true, 2, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
-    else if (track && d.lse) hipLaunchKernelGGL((seer_attn40_kernel<1, true, false, 2, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
-    else if (track && plain) hipLaunchKernelGGL((seer_attn40_kernel<1, true, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
-    else if (track) hipLaunchKernelGGL((seer_attn40_kernel<1, true, false>), grid, dim3(256), 0, st, d, ws_log2, nqb);
-    else if (plain) hipLaunchKernelGGL((seer_attn40_kernel<1, false, true>), grid, dim3(256), 0, st, d, ws_log2, nqb);
-    else hipLaunchKernelGGL((seer_attn40_kernel<1, false, false>), grid, dim3(256), 0, st, d, ws_log2, nqb);
+    if (!track && (d.variant == 2 || (fills && plain))) return a40_form(2, false, plain);
+    return a40_form(1, track, plain, 2, false, d.lse != nullptr);      // lse: always the tracked form
+}
+
+template <int QB, bool TRACK, bool PLAIN, int NST = 2, bool F16 = false, bool LSE = false>
+int launch40(const seer_attn_desc& d, int ws_log2, int nbatch, hipStream_t st) {
+    const int nqb = (d.Sq + 128 * QB - 1) / (128 * QB);
+    hipLaunchKernelGGL((seer_attn40_kernel<QB, TRACK, PLAIN, NST, F16, LSE>), dim3((unsigned)(nqb * nbatch * d.heads)), dim3(256), 0, st,
+                       d, ws_log2, nqb);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
+}
+
+}  // namespace
+
+// called by seer_attn_fwd (attention.hip) for head_dim 40: one decision, one launch, over the forms that are built
+int seer_attn40_launch(const seer_attn_desc& d, int ws_log2, hipStream_t st) {
+    const int nbatch = attn_launch_batches(d, ws_log2);
+    const int form = a40_choose(d, ws_log2, nbatch);
+    switch (form) {
+#define A40_FORM(...) case a40_form(__VA_ARGS__): return launch40<__VA_ARGS__>(d, ws_log2, nbatch, st);
+        A40_FORM(1, false, false) A40_FORM(1, false, true) A40_FORM(1, true, false) A40_FORM(1, true, true)
+        A40_FORM(1, true, false, 2, false, true) A40_FORM(1, true, true, 2, false, true)
+        A40_FORM(1, true, false, 2, true) A40_FORM(1, true, true, 2, true)
+        A40_FORM(2, false, false) A40_FORM(2, false, true) A40_FORM(2, false, true, 3)
+#undef A40_FORM
+        default: return form < 0 ? form : SEER_ENOSYS;
+    }
 }

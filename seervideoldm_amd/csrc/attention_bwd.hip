@@ -15,36 +15,17 @@
 // fragments as B; P / dS stay in the accumulator registers and become the B operand of the second pair of products
 // (accumulator-as-operand, as in the forward kernel), whose A operand A^T comes from the same [j][d] LDS image through
 // ds_read_b64_tr_b16.
-#include "seer_common.h"
+#include "attn_common.h"
 
 namespace {
 
-constexpr int KT = 64;    // streamed rows per LDS tile
+constexpr int KT = ATTN_KT;    // streamed rows per LDS tile
 
 template <int D>
-struct BwdCfg {
-    static constexpr int DP = (D + 15) / 16 * 16;
-    static constexpr int KSTEPS = DP / 16;
-    static constexpr int NDT = (D + 31) / 32;
-    static constexpr int DV = NDT * 32;
-    static constexpr int RS = DP + 8;                  // row stride (elements): odd number of 16-byte chunks
-    static constexpr int CH = D / 8;
-    static constexpr int NCH = (KT * CH + 255) / 256;
-    static constexpr int IMG = KT * RS + 64;           // one operand image (+ slack: the transposed reads of the last rows
-                                                       // touch columns up to DV, whose products are discarded)
+struct BwdCfg : AttnGeom<D> {                          // both images at the padded row stride RS
+    static constexpr int IMG = KT * AttnGeom<D>::RS + 64;   // one operand image (+ slack: the transposed reads of the last rows
+                                                            // touch columns up to DV, whose products are discarded)
     static constexpr size_t LDS_BYTES = (size_t)2 * IMG * 2 + 2 * KT * sizeof(float);
-};
-
-struct TokMapB {
-    int ws_log2, HW, W_, wy0, wx0;
-    __device__ __forceinline__ int operator()(int pos) const {
-        if (ws_log2 < 0) return pos;
-        const int ws2 = 2 * ws_log2;
-        const int f = pos >> ws2;
-        const int rem = pos & ((1 << ws2) - 1);
-        const int wy = rem >> ws_log2, wx = rem & ((1 << ws_log2) - 1);
-        return f * HW + (wy0 + wy) * W_ + wx0 + wx;
-    }
 };
 
 template <int D, int MODE>
@@ -62,20 +43,8 @@ __global__ void __launch_bounds__(256) seer_attn_bwd_kernel(const seer_attn_bwd_
     const int lq = lane & 31, lh = lane >> 5;
 
     const int y = blockIdx.y;
-    const int head = y % p.heads;
-    int b = y / p.heads;
-    TokMapB tok;
-    tok.ws_log2 = ws_log2;
-    tok.HW = p.H * p.W;
-    tok.W_ = p.W;
-    tok.wy0 = tok.wx0 = 0;
-    if (ws_log2 >= 0) {
-        const int win = b / p.batch;
-        b = b - win * p.batch;
-        const int nwx = p.W >> ws_log2;
-        tok.wy0 = (win / nwx) << ws_log2;
-        tok.wx0 = (win % nwx) << ws_log2;
-    }
+    int head, b;
+    const AttnTokMap tok = attn_block_origin(p, ws_log2, y, head, b);
     const bf16* __restrict__ Qg = reinterpret_cast<const bf16*>(p.Q) + (int64_t)b * p.q_bs + head * D;
     const bf16* __restrict__ Kg = reinterpret_cast<const bf16*>(p.K) + (int64_t)b * p.k_bs + head * D;
     const bf16* __restrict__ Vg = reinterpret_cast<const bf16*>(p.V) + (int64_t)b * p.v_bs + head * D;
@@ -159,27 +128,12 @@ __global__ void __launch_bounds__(256) seer_attn_bwd_kernel(const seer_attn_bwd_
     }
     const int t_begin = j_begin / KT, t_end = (j_end + KT - 1) / KT;
 
-    u32x4 r1reg[C::NCH], r2reg[C::NCH];
+    AttnStager<D> stage;
     float lreg = 0.f, dreg = 0.f;
     auto prefetch = [&](int t) {
         const int j0 = t * KT;
-#pragma unroll
-        for (int i = 0; i < C::NCH; ++i) {
-            const int idx = tid + 256 * i;
-            if (idx < KT * C::CH) {
-                const int row = idx / C::CH, ch = idx - row * C::CH;
-                int jg = j0 + row;
-                jg = jg < str_n ? jg : str_n - 1;
-                const int64_t tj = tok(jg);
-                if constexpr (MODE == 0) {
-                    r1reg[i] = *reinterpret_cast<const u32x4*>(Kg + tj * p.k_ss + ch * 8);
-                    r2reg[i] = *reinterpret_cast<const u32x4*>(Vg + tj * p.v_ss + ch * 8);
-                } else {
-                    r1reg[i] = *reinterpret_cast<const u32x4*>(Qg + tj * p.q_ss + ch * 8);
-                    r2reg[i] = *reinterpret_cast<const u32x4*>(dOg + tj * pd.do_ss + ch * 8);
-                }
-            }
-        }
+        if constexpr (MODE == 0) stage.prefetch(tid, tok, Kg, p.k_ss, Vg, p.v_ss, j0, str_n);
+        else stage.prefetch(tid, tok, Qg, p.q_ss, dOg, pd.do_ss, j0, str_n);
         if constexpr (MODE == 1) {
             if (tid < KT) {
                 int jg = j0 + tid;
@@ -190,15 +144,7 @@ __global__ void __launch_bounds__(256) seer_attn_bwd_kernel(const seer_attn_bwd_
         }
     };
     auto commit = [&]() {
-#pragma unroll
-        for (int i = 0; i < C::NCH; ++i) {
-            const int idx = tid + 256 * i;
-            if (idx < KT * C::CH) {
-                const int row = idx / C::CH, ch = idx - row * C::CH;
-                *reinterpret_cast<u32x4*>(img1 + row * C::RS + ch * 8) = r1reg[i];
-                *reinterpret_cast<u32x4*>(img2 + row * C::RS + ch * 8) = r2reg[i];
-            }
-        }
+        stage.commit(tid, img1, C::RS, img2, C::RS);
         if constexpr (MODE == 1) {
             if (tid < KT) {
                 Ls[tid] = lreg;
@@ -275,26 +221,9 @@ __global__ void __launch_bounds__(256) seer_attn_bwd_kernel(const seer_attn_bwd_
 #pragma unroll
                 for (int tt = 0; tt < C::NDT; ++tt) {
                     const int o0 = toff + (16 * s2) * C::RS + 32 * tt;
-                    {
-                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4*)(img1 + o0));
-                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4*)(img1 + o0 + 8 * C::RS));
-                        bf16x8 af;
-                        af[0] = lo[0]; af[1] = lo[1]; af[2] = lo[2]; af[3] = lo[3];
-                        af[4] = hi[0]; af[5] = hi[1]; af[6] = hi[2]; af[7] = hi[3];
-                        acc1[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, dsf[s2], acc1[tt], 0, 0, 0);
-                    }
-                    if constexpr (MODE == 1) {
-                        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4*)(img2 + o0));
-                        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-                            (__attribute__((address_space(3))) bf16x4*)(img2 + o0 + 8 * C::RS));
-                        bf16x8 af;
-                        af[0] = lo[0]; af[1] = lo[1]; af[2] = lo[2]; af[3] = lo[3];
-                        af[4] = hi[0]; af[5] = hi[1]; af[6] = hi[2]; af[7] = hi[3];
-                        acc2[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, pf[s2], acc2[tt], 0, 0, 0);
-                    }
+                    acc1[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(img1 + o0, 8 * C::RS), dsf[s2], acc1[tt], 0, 0, 0);
+                    if constexpr (MODE == 1)
+                        acc2[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(img2 + o0, 8 * C::RS), pf[s2], acc2[tt], 0, 0, 0);
                 }
             }
         }
@@ -328,10 +257,8 @@ __global__ void __launch_bounds__(256) seer_attn_bwd_kernel(const seer_attn_bwd_
 
 template <int D, int MODE>
 int launch_one(const seer_attn_bwd_desc& d, int ws_log2, hipStream_t st) {
-    int nbatch = d.fwd.batch;
-    if (ws_log2 >= 0) nbatch *= (d.fwd.H >> ws_log2) * (d.fwd.W >> ws_log2);
     const int own_n = MODE == 0 ? d.fwd.Sq : d.fwd.Sk;
-    dim3 grid((own_n + 127) / 128, nbatch * d.fwd.heads, 1);
+    dim3 grid((own_n + 127) / 128, attn_launch_batches(d.fwd, ws_log2) * d.fwd.heads, 1);
     constexpr size_t lds = BwdCfg<D>::LDS_BYTES;
     hipLaunchKernelGGL((seer_attn_bwd_kernel<D, MODE>), grid, dim3(256), lds, st, d, ws_log2);
     SEER_LAUNCH_CHECK();
@@ -358,14 +285,8 @@ extern "C" int seer_attn_bwd(const seer_attn_bwd_desc* desc, void* stream) {
     if (f.flags & SEER_ATTN_Q_PRESCALED) return SEER_ENOSYS;   // ... and an un-prescaled q (it applies scale * log2(e) itself)
     if ((f.q_ss | f.k_ss | f.v_ss | f.o_ss | d.do_ss) % 8 || (d.dq_ss | d.dk_ss | d.dv_ss) % 4) return SEER_EINVAL;
     if ((f.q_bs | f.k_bs | f.v_bs | f.o_bs | d.do_bs) % 8 || (d.dq_bs | d.dk_bs | d.dv_bs) % 4) return SEER_EINVAL;
-    int ws_log2 = -1;
-    if (f.window_ws > 0) {
-        if (f.window_ws != 4 && f.window_ws != 8) return SEER_EINVAL;
-        ws_log2 = f.window_ws == 4 ? 2 : 3;
-        if (f.H % f.window_ws || f.W % f.window_ws) return SEER_EINVAL;
-        if (f.Fq != f.F || f.Sq != f.F * f.window_ws * f.window_ws || f.Sk != f.Sq) return SEER_EINVAL;
-    }
-    if (f.causal_offset < 0 || (f.causal && f.Sq + f.causal_offset > f.Sk)) return SEER_EINVAL;
+    int ws_log2;
+    if (attn_check_addressing(f, &ws_log2, true) != SEER_OK) return SEER_EINVAL;
     switch (f.head_dim) {
         case 40: return launch_bwd<40>(d, ws_log2, st);
         case 80: return launch_bwd<80>(d, ws_log2, st);

@@ -7,7 +7,7 @@
 // Tile 128 (n) x 128 (k) per block, 4 waves (2 x 2) of 64 x 64 = 2 x 2 v_mfma_f32_32x32x16_bf16 accumulators; the long
 // contraction (rows of the activation: 12 288 at the 32x32 level) is split across grid.z, slices write fp32 partial tiles to a
 // workspace and a second kernel adds them in slice order (deterministic, no atomics).
-#include "seer_common.h"
+#include "attn_common.h"      // tr_frag
 
 #include <algorithm>
 #include <vector>
@@ -76,15 +76,7 @@ __device__ __forceinline__ void tn_tile(bf16* imgA, bf16* imgB, const bf16* __re
     const int li = lane & 15, g16 = (lane >> 4) & 1;
     // transposed-read base: contraction rows 4*lh + (li >> 2) (+8), columns 16*g16 + 4*(li & 3) of a 32-wide operand tile
     const int toff = (4 * lh + (li >> 2)) * TRS + 16 * g16 + 4 * (li & 3);
-    auto frag = [&](const bf16* img, int col0, int s) -> bf16x8 {
-        const bf16* a0 = img + toff + (16 * s) * TRS + col0;
-        const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(a0));
-        const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf16x4*)(a0 + 8 * TRS));
-        bf16x8 f;
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-        f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        return f;
-    };
+    auto frag = [&](const bf16* img, int col0, int s) { return tr_frag(img + toff + (16 * s) * TRS + col0, 8 * TRS); };
 
     if (m_begin < m_end) prefetch(m_begin);
     for (int m0 = m_begin; m0 < m_end; m0 += TM) {
