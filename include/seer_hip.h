@@ -734,6 +734,33 @@ int seer_slot_cfg_plms_step(const float* eps, int32_t slots, int32_t C, int32_t 
                             const float* scale, const float* coef, int32_t nsched, int32_t* step, int32_t* state, float* ring,
                             const float* x, float* x_prov, float* x_prev, float* pred_x0, void* stream);
 
+/* The captured step over slots with DDIM and DPM-Solver++ clips side by side (slots.py, dpm=True): the per-slot form of
+ * seer_cfg_dpm_step_dev, as seer_slot_cfg_ddim_step is of seer_cfg_ddim_step_dev.  Its first kernel is seer_slot_step_begin,
+ * unchanged: DPM-Solver++ needs no provisional latent and no second evaluation.  Per slot in device memory, beside scale[s],
+ * coef[s] (fp32 [slots][nsched][4], the DDIM rows) and step[s][0..1] of seer_slot_cfg_ddim_step:
+ *   dpm_coef  fp32 [slots][nsched][6]: a DPM table per slot, the six words per row of seer_cfg_dpm_step;
+ *   state     int32 [slots][4]: word 0 = history valid for an even index, word 1 = history valid for an odd index, word 2 = the
+ *             slot's sampler (0 DDIM, 1 DPM-Solver++ first order, 2 DPM-Solver++ 2M), word 3 = nonzero when the schedule's final
+ *             step -- index 0 -- is first order;
+ *   d_hist    fp32 [slots][C*F_pred*HW]: the slot's pred_x0 rows, history and output at once.
+ * For every slot s: index = step[s][1], e = the CFG combination with scale[s].
+ *   word 2 is 1 or 2:  order 2 when state[s][index & 1] == 1, word 2 == 2 and not (index == 0 and word 3 != 0), else order 1;
+ *                      seer_cfg_dpm_step's update of that order with row `index` of dpm_coef[s], d_prev = d_hist[s] (read at order
+ *                      2 only: at order 1 it may hold anything, NaN included), and this step's D written over d_hist[s].  The
+ *                      slot's first thread writes step[s][0] = index - 1 and state[s][(index - 1) & 1] = 1.
+ *   any other word 2:  exactly seer_slot_cfg_ddim_step's update with row `index` of coef[s], pred_x0 = d_hist[s]; step[s][0] =
+ *                      index - 1; no state word is written.
+ * Words 2 and 3 are only read and the valid word written is of the other parity than the one read: no kernel reads and writes the
+ * same word.  The arithmetic is the device code of seer_cfg_ddim_step / seer_cfg_dpm_step, so an element gets their bits.
+ * index < 0 or >= nsched: nothing of that slot is written -- no latent, no element of d_hist, no word of step or state.  The host
+ * writes step[s][0] and state[s] = (0, 0, sampler, final-step rule) only when it fills slot s: a clip's first step is first order.
+ * x_prev may be x; d_hist may be neither.  SEER_EINVAL, and nothing launched, for a NULL pointer (d_hist is required), slots
+ * outside 1 .. 4, non-positive extents, cond_f outside 0 .. F_total - 1, nsched < 1, a pointer that is not 4-byte aligned, d_hist
+ * == x or d_hist == x_prev, a grid beyond one dimension. */
+int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                           const float* scale, const float* coef, const float* dpm_coef, int32_t nsched, int32_t* step,
+                           int32_t* state, const float* x, float* x_prev, float* d_hist, void* stream);
+
 /* decoded image post-process of ddim_sample (utils/ddim_sampling_utils.py:41): clamp((x+1)/2, 0, 1) in place */
 int seer_clamp01(float* x, int64_t n, void* stream);
 

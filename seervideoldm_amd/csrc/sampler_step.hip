@@ -360,6 +360,36 @@ __global__ void slot_cfg_plms_kernel(const float* __restrict__ eps, int slots, i
     }
 }
 
+// DDIM and DPM-Solver++ clips side by side.  CFG always on, eta = 0.  dpm_coef [slots][nsched][6] holds a DPM table per slot, state
+// int32 [slots][4] the four words of cfg_dpm_kernel per slot, with word 2 = the slot's sampler: 0 DDIM, 1 DPM first order, 2 2M (any
+// other value is read as 0).  The arithmetic is cfg_eps_at with scale[s], then step_update (a DDIM slot, as slot_cfg_ddim_kernel
+// without seeds) or dpm_update with cfg_dpm_kernel's order rule: an element gets the bits of seer_cfg_ddim_step / seer_cfg_dpm_step.
+// d_hist is the slot's pred_x0 rows: an order-2 step reads the D of the step before from it, every step writes its own over it.
+// A DPM slot's first thread also writes the valid word of parity (index - 1); words 2 and 3 are only read.  x may alias x_prev.
+__global__ void slot_cfg_dpm_kernel(const float* __restrict__ eps, int slots, int C, int Ft, int cond_f, int HW,
+                                    const float* __restrict__ scale, const float* __restrict__ coef,
+                                    const float* __restrict__ dpm_coef, int nsched, int* __restrict__ step, int* __restrict__ state,
+                                    const float* x, float* x_prev, float* d_hist) {
+    const int64_t per_slot = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)slots * per_slot) return;
+    const int s = (int)(i / per_slot);
+    const int index = step[2 * s + 1];
+    if (index < 0 || index >= nsched) return;            // idle (or a counter outside the table): nothing of this slot is written
+    int* st = state + 4 * s;
+    const int sampler = st[2];
+    const bool first = i == (int64_t)s * per_slot;
+    const float e = cfg_eps_at(eps, 1, slots, C, Ft, cond_f, HW, scale[s], i);
+    if (sampler == 1 || sampler == 2) {
+        const int order = st[index & 1] == 1 && sampler == 2 && !(index == 0 && st[3] != 0) ? 2 : 1;
+        if (first) step[2 * s] = index - 1, st[(index - 1) & 1] = 1;
+        dpm_update(e, dpm_coef + ((int64_t)s * nsched + index) * DPM_ROW_WORDS, order, x, d_hist, x_prev, d_hist, i);
+    } else {
+        if (first) step[2 * s] = index - 1;
+        step_update<DDIM_TERM>(e, coef + (int64_t)s * nsched * 4, index, x, StepNoise{}, x_prev, d_hist, i);
+    }
+}
+
 // ---- GIVEN latents (masked sampling, stochastic_encode; CompVis ldm/models/diffusion/ddim.py:144-147, 207-221): q(e) is the given
 // latent x0 noised to the level of coefficient row `index`, its noise n either read from a tensor or normal e of Philox stream 2 of
 // the clip's seed at that index.  One expression for the three kernels below, so the seeded form gets the bits of the noise-tensor
@@ -611,6 +641,19 @@ extern "C" int seer_slot_cfg_plms_step(const float* eps, int32_t slots, int32_t 
     return launch_per_element(slot_cfg_plms_kernel, elements(slots, C, (int64_t)F_total - cond_f, HW),
                               {eps, scale, coef, step, state, ring, x, x_prov, x_prev, pred_x0}, stream, eps, slots, C, F_total, cond_f,
                               HW, scale, coef, nsched, step, state, ring, x, x_prov, x_prev, pred_x0);
+}
+
+// slots 1..4 (the [uc | c] rows of all slots go through the 8-row time embedding); d_hist is read and written, so it is neither x
+// nor x_prev
+extern "C" int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                      const float* scale, const float* coef, const float* dpm_coef, int32_t nsched, int32_t* step,
+                                      int32_t* state, const float* x, float* x_prev, float* d_hist, void* stream) {
+    if (!eps || !scale || !coef || !dpm_coef || !step || !state || !x || !x_prev || !d_hist || slots < 1 || slots > 4 || nsched < 1 ||
+        !update_shape_ok(C, F_total, cond_f, HW) || d_hist == x || d_hist == x_prev)
+        return SEER_EINVAL;
+    return launch_per_element(slot_cfg_dpm_kernel, elements(slots, C, (int64_t)F_total - cond_f, HW),
+                              {eps, scale, coef, dpm_coef, step, state, x, x_prev, d_hist}, stream, eps, slots, C, F_total, cond_f, HW,
+                              scale, coef, dpm_coef, nsched, step, state, x, x_prev, d_hist);
 }
 
 // given latents: exactly one of noise and seeds; a clip's element index is a Philox counter word, as in the seeded steps

@@ -26,8 +26,9 @@ the history is the step's own pred_x0 buffer, and the kernel picks its order fro
 no host-written scalar after its first step.
 
 Only the deterministic solver is built: no mask / x0, no seed, no eta > 0 (the SDE variant), no noise_dropout, no order 3, no
-singlestep (2S) form, no slots.  The per-step torch.randn draw of the reference's samplers is kept (consume_rng_when_deterministic),
-as in PLMSSampler.
+singlestep (2S) form.  The per-step torch.randn draw of the reference's samplers is kept (consume_rng_when_deterministic), as in
+PLMSSampler.  A queue of clips runs this solver through SlotSampler(dpm=True) (slots.py): submit(method="dpmpp") with this
+constructor's order, lower_order_final and discretize, bit for bit this sampler's latent under the layout-invariant mode.
 """
 from __future__ import annotations
 

@@ -1361,6 +1361,32 @@ def cfg_dpm_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, ste
                                             _p(state), _p(x_prev), _p(d_hist), _stream()), "seer_cfg_dpm_step_dev")
 
 
+SLOT_DPM_STATE_WORDS = 4    # int32 words of a slot's state in slot_cfg_dpm_step: (valid even, valid odd, sampler, final step first order)
+SLOT_DDIM, SLOT_DPM1, SLOT_DPM2M = 0, 1, 2     # word 2: the slot's sampler
+
+
+def slot_cfg_dpm_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
+                      dpm_coef: torch.Tensor, state: torch.Tensor, *, cond_f: int, x_prev: torch.Tensor,
+                      pred_x0: torch.Tensor) -> None:
+    """slot_cfg_ddim_step with a sampler per slot, DDIM or DPM-Solver++: by word 2 of state[s] (int32 [slots, 4]) slot s runs the
+    DDIM update with row step[s, 1] of coef[s], or cfg_dpm_step_dev's with that row of dpm_coef[s] (fp32 [slots, nsched, 6]) and the
+    order its state words give.  pred_x0 [slots, ...] is the history: read at order 2, written by every step.  A slot whose index is
+    outside its table is left untouched.  x_prev may be x, pred_x0 may be neither (include/seer_hip.h, seer_slot_cfg_dpm_step)"""
+    slots, Cc, Ft, HW = _req_update(eps, x, coef, cfg=True, cond_f=cond_f, step=step, x_prev=x_prev)
+    _req_slot_tables(slots, coef, step, scale)
+    _req(dpm_coef, torch.float32, "dpm_coef"); _req(state, torch.int32, "state")
+    assert dpm_coef.is_contiguous() and dpm_coef.dim() == 3 and tuple(dpm_coef.shape[:2]) == tuple(coef.shape[:2])
+    _req_dpm_table(dpm_coef.view(-1, dpm_coef.shape[2]))
+    assert state.is_contiguous() and tuple(state.shape) == (slots, SLOT_DPM_STATE_WORDS)
+    if pred_x0 is None:
+        raise ValueError("pred_x0 is the history of a DPM-Solver++ slot: it is required")
+    _req_pred(pred_x0, x)
+    assert pred_x0.data_ptr() not in (x.data_ptr(), x_prev.data_ptr()) and x_prev.dtype == torch.float32
+    check(_lib.load().seer_slot_cfg_dpm_step(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), _p(dpm_coef), coef.shape[1],
+                                             _p(step), _p(state), _p(x), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_slot_cfg_dpm_step")
+
+
 def clamp01_(x: torch.Tensor) -> torch.Tensor:
     _req(x, torch.float32, "x")
     assert x.is_contiguous()

@@ -52,7 +52,8 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 @torch.no_grad()
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
                    latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
-                   plms: bool = False, stochastic: bool = False, editing: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
+                   plms: bool = False, stochastic: bool = False, editing: bool = False,
+                   dpm: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
     empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
@@ -61,7 +62,9 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     stochastic=True: a request may then carry seed, eta and temperature (SlotSampler.submit), and `noise` is optional when it has a
     seed -- the start code is then drawn from the seed; in a queue started without it those keys are a ValueError.  `editing=True`
     builds it with editing=True: a request may then carry mask with known (the given latents, SlotSampler.submit's x0; they need a
-    seed) and t_start; in a queue started without it those keys are a ValueError as well.  The VAE encode
+    seed) and t_start; in a queue started without it those keys are a ValueError as well.  `dpm=True`
+    builds it with dpm=True: a request may then name sampler = "dpmpp" and carry order, lower_order_final and discretize
+    (SlotSampler.submit); a request naming "dpmpp" without it is a ValueError.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -73,8 +76,9 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     def admitted():
         for r in requests:
             method = r.get("sampler", "ddim")
-            if method not in ("ddim", "plms") or (method == "plms" and not plms):
-                raise ValueError(f"sampler = {method!r}: 'ddim', or 'plms' in a queue started with plms=True")
+            if method not in ("ddim", "plms", "dpmpp") or (method == "plms" and not plms) or (method == "dpmpp" and not dpm):
+                raise ValueError(f"sampler = {method!r}: 'ddim', 'plms' in a queue started with plms=True, or 'dpmpp' in one started "
+                                 "with dpm=True")
             x0_image = r["x0_image"]
             if x0_image.shape[2] == 1:
                 x0_image = x0_image.expand(-1, -1, f1, -1, -1)
@@ -86,9 +90,10 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
                 _, c_l, _, h_l, w_l = x0_emb.shape
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
                                            max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic,
-                                           **(dict(editing=True) if editing else {})))
+                                           **(dict(editing=True) if editing else {}), **(dict(dpm=True) if dpm else {})))
             seeded = {k: r[k] for k in ("seed", "eta", "temperature") if k in r}
             edit = {k: r[k] for k in ("mask", "known", "t_start") if r.get(k) is not None}
+            solver = {k: r[k] for k in ("order", "lower_order_final", "discretize") if k in r}
             if edit and not editing:
                 raise ValueError(f"{sorted(edit)}: a request carries these only in a queue started with editing=True")
             if "known" in edit:
@@ -98,7 +103,7 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
             if r.get("noise") is None and seeded.get("seed") is None:
                 raise ValueError("a request needs `noise` (its start code) or, in a queue started with stochastic=True, a `seed`")
             yield dict(x_T=r.get("noise"), x0_emb=x0_emb, c=c, uc=uc, S=r.get("ddim_steps", 30), scale=r.get("scale", 7.5),
-                       tag=r.get("tag"), method=method, **seeded, **edit)
+                       tag=r.get("tag"), method=method, **seeded, **edit, **solver)
 
     reqs = admitted()
     first = next(reqs, None)

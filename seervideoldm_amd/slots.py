@@ -31,12 +31,23 @@ which draws a slot's noise itself from (the slot's seed, its schedule index, the
 its slot or its neighbours.  Each slot also has a seed pair and a temperature in device memory, and its coefficient rows carry the
 sigma of its own eta.  The promise above then holds for a seeded clip against DDIMSampler.sample(..., eta=, seed=, x_T=None).
 
+With `dpm=True` a request may choose DPM-Solver++ (submit's method="dpmpp", with order, lower_order_final and discretize as
+DPMSolverSampler takes them): the step is seer_slot_step_begin -> the UNet -> seer_slot_cfg_dpm_step, and every slot also has a DPM
+table and four state words in device memory -- history valid by index parity (twice), the slot's sampler (0 DDIM, 1 first order, 2
+2M) and the final-step rule.  The history of a 2M clip is the slot's own pred_x0 rows.  A clip of n schedule entries occupies its slot
+for n steps, one evaluation each, whichever sampler it runs: 2M at 25 steps is where DDIM is at 50 on the analytic model
+(profiles/dpm_sampler.md), so the queue turns clips over twice as fast.  The host writes the four words only when it fills the slot --
+(0, 0, sampler, rule): a clip's first step is first order and never reads the stale D of the slot's last clip -- and the kernel walks
+the orders itself.  The promise above then reads: a "dpmpp" clip's latent is bit for bit DPMSolverSampler(order=, lower_order_final=,
+discretize=).sample's for that clip alone, and a DDIM clip in such a queue has the bits it has in a plain one.
+
 With `editing=True` a request may carry a mask with given latents, and a start level (submit's `mask`, `x0`, `t_start`): the step
 opens with seer_slot_known_blend, which re-noises a slot's given latents to the level of the slot's next index from Philox stream 2 of
 its seed and blends them in where the slot's mask says so.  A slot whose mask is all zero -- every plain clip -- is not touched by it,
 so edited and plain clips share a queue, and a plain clip has the bits it has in a queue built without the keyword.
 
-Out of scope: PLMS with noise or with a mask, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
+Out of scope: PLMS with noise or with a mask, DPM-Solver++ with noise, with a mask or from a start level, PLMS and DPM-Solver++ in one
+queue, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
 """
 from __future__ import annotations
@@ -47,6 +58,7 @@ import torch
 
 from . import ops as hip_ops
 from .ddim import DDIMSampler, capture_step
+from .dpm import DPMSolverSampler
 from .step_graph import capture_engine, engine_on
 
 MAX_SLOTS = 4           # the time-embedding MLP (seer_linear_smallm) takes up to 8 rows: the [uc | c] pair of 4 slots
@@ -63,10 +75,14 @@ class SlotSampler:
     (submit): the step's last kernel then draws the noise per slot, over two more static buffers, again under a key of its own; it
     excludes plms=True (PLMS has no noise term).  `editing=True` lets a request carry mask, x0 and t_start (submit): the step then
     opens with the blend kernel, over per-slot mask, given-latent and seed buffers, under a key of its own once more (and another with
-    stochastic=True); it excludes plms=True as well."""
+    stochastic=True); it excludes plms=True as well.  `dpm=True` lets a request choose DPM-Solver++ (submit's `method`, `order`,
+    `lower_order_final`, `discretize`): the step's last kernel then carries a sampler per slot, DDIM or DPM-Solver++, over two more
+    static buffers, under a key of its own; it excludes plms, stochastic and editing (the solo DPMSolverSampler has no seeded or masked
+    form for a slot to be bit-equal to)."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
-                 model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False):
+                 model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False,
+                 dpm: bool = False):
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -78,6 +94,12 @@ class SlotSampler:
             raise ValueError("stochastic=True with plms=True: PLMS is deterministic only, build one sampler for each")
         if editing and plms:
             raise ValueError("editing=True with plms=True: PLMS with a mask is not built, build one sampler for each")
+        if dpm and plms:
+            raise ValueError("dpm=True with plms=True: PLMS and DPM-Solver++ in one queue is not built, build one sampler for each")
+        if stochastic and dpm:
+            raise ValueError("stochastic=True with dpm=True: DPM-Solver++ is deterministic only, build one sampler for each")
+        if editing and dpm:
+            raise ValueError("editing=True with dpm=True: DPM-Solver++ with a mask is not built, build one sampler for each")
         if (stochastic or editing) and C * Fp * h * w >= 1 << 31:
             raise ValueError(f"shape {tuple(shape)}: a seeded clip has fewer than 2^31 elements")
         if device is None:
@@ -101,7 +123,7 @@ class SlotSampler:
         self._context = torch.zeros((2 * n, f1 + Fp, L, D), device=dev, dtype=f32)    # uc rows, then c rows
         # The mode, decided here once: its buffers, the first word of its graph-cache key, the launches in front of the model call and the
         # update behind it (names in the backend with their arguments, for _body), and the buffers to zero when a slot retires (step).
-        self.plms, self.stochastic, self.editing = bool(plms), bool(stochastic), bool(editing)
+        self.plms, self.stochastic, self.editing, self.dpm = bool(plms), bool(stochastic), bool(editing), bool(dpm)
         self._retire = [self._x] + ([self._x0] if f1 else [])
         if self.plms:
             self._state = torch.zeros((n, hip_ops.SLOT_STATE_WORDS), device=dev, dtype=torch.int32)    # phase 0, nothing in the ring
@@ -112,6 +134,12 @@ class SlotSampler:
             self._front = [("slot_plms_step_begin", (self._x0, self._x, self._xprov, self._ttab, self._step, self._state, 2, self._sample,
                                                      self._t))]
             self._update = ("slot_cfg_plms_step", (self._state, self._ring, self._xprov))
+        elif self.dpm:
+            self._dpm_coef = torch.zeros((n, self.max_steps, hip_ops.DPM_ROW_WORDS), device=dev, dtype=f32)
+            self._dpm_state = torch.zeros((n, hip_ops.SLOT_DPM_STATE_WORDS), device=dev, dtype=torch.int32)   # every slot DDIM
+            self._kind = "slots-dpm"
+            self._front = [("slot_step_begin", (self._x0, self._x, self._ttab, self._step, 2, self._sample, self._t))]
+            self._update = ("slot_cfg_dpm_step", (self._dpm_coef, self._dpm_state))
         else:
             self._kind = {(False, False): "slots", (False, True): "slots-rng", (True, False): "slots-edit",
                           (True, True): "slots-edit-rng"}[self.editing, self.stochastic]
@@ -130,6 +158,7 @@ class SlotSampler:
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
         self._tables: Dict[Tuple[int, float], Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._dpm_tables: Dict[Tuple[int, str], Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}
         self._capture_refused = False
 
     # ---- the queue's host side -----------------------------------------------------------------------------------------------
@@ -151,6 +180,16 @@ class SlotSampler:
             self._tables[key] = (self._sched.ddim_coef, self._sched._t_table)
         return self._tables[key]
 
+    def _dpm_schedule(self, S: int, discretize: str):
+        """DPMSolverSampler(discretize=).make_schedule(S): (ddim_coef, _t_table, dpm_coef), the same tables bit for bit, made once per
+        (S, discretize)"""
+        key = (S, discretize)
+        if key not in self._dpm_tables:
+            sched = DPMSolverSampler(self.device, discretize=discretize)
+            sched.make_schedule(ddim_num_steps=S, ddim_eta=0., verbose=False)
+            self._dpm_tables[key] = (sched.ddim_coef, sched._t_table, sched.dpm_coef)
+        return self._dpm_tables[key]
+
     def _clip(self, t: Optional[torch.Tensor], want, what: str) -> torch.Tensor:
         if t is None or tuple(t.shape) not in (tuple(want), (1, *want)):
             raise ValueError(f"{what}: shape {None if t is None else tuple(t.shape)}, this sampler takes {tuple(want)} (with or without "
@@ -159,7 +198,8 @@ class SlotSampler:
 
     @torch.no_grad()
     def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim", seed: Optional[int] = None,
-               temperature: float = 1., mask=None, x0=None, t_start: Optional[int] = None) -> int:
+               temperature: float = 1., mask=None, x0=None, t_start: Optional[int] = None, order: int = 2,
+               lower_order_final: bool = True, discretize: str = "uniform") -> int:
         """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
         [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
         empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
@@ -176,8 +216,13 @@ class SlotSampler:
         the step's level with Philox stream 2 of `seed`, which it therefore needs -- and t_start = k (1 .. the schedule's entries):
         x_T is then the latent at level k, the slot's counter starts at k - 1 and the clip occupies its slot for k steps.  Without
         editing=True any of the three is a ValueError.
+        A sampler built with dpm=True also takes method "dpmpp" with order (1 or 2: first order or 2M), lower_order_final (the final
+        step of a schedule of fewer than 15 entries is first order) and discretize ("uniform", or "logsnr": the schedule can then
+        have fewer than S entries) -- DPMSolverSampler's constructor keywords, with its defaults; the clip's tables are that sampler's
+        make_schedule(S) and it occupies its slot for one step per entry.  The three keywords belong to "dpmpp": with another method
+        anything but their defaults is a ValueError, as is "dpmpp" on a sampler built without dpm=True.
         Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
-        constructor's, eta != 0, a frame-sharded model, an unknown method and "plms" on a sampler built without it."""
+        constructor's, eta != 0, a frame-sharded model, an unknown method, and "plms" or "dpmpp" on a sampler built without it."""
         C, Fp, h, w = self.shape
         F, (L, D) = self.f1 + Fp, self.context_shape
         if not self.editing and (mask is not None or x0 is not None or t_start is not None):
@@ -195,10 +240,18 @@ class SlotSampler:
             raise ValueError(f"eta = {eta} needs a seed: a slot draws its noise from the clip's own seed, not from torch's generator")
         if seed is not None and not 0 <= int(seed) < 1 << 64:
             raise ValueError(f"seed = {seed}: a seed is an unsigned 64-bit integer")
-        if method not in ("ddim", "plms"):
-            raise ValueError(f"method = {method!r}: 'ddim' or 'plms'")
+        if method not in ("ddim", "plms", "dpmpp"):
+            raise ValueError(f"method = {method!r}: 'ddim', 'plms' or 'dpmpp'")
         if method == "plms" and not self.plms:
             raise ValueError("method = 'plms' needs a sampler built with plms=True")
+        if method == "dpmpp" and not self.dpm:
+            raise ValueError("method = 'dpmpp' needs a sampler built with dpm=True")
+        if method != "dpmpp" and (order != 2 or not bool(lower_order_final) or discretize != "uniform"):
+            raise ValueError(f"order / lower_order_final / discretize belong to method = 'dpmpp', not to {method!r}")
+        if order not in (1, 2):
+            raise ValueError(f"order = {order!r}: 1 (first order) or 2 (2M)")
+        if discretize not in ("uniform", "logsnr"):
+            raise ValueError(f"discretize = {discretize!r}: 'uniform' or 'logsnr'")
         if getattr(self.unet, "_shard", None) is not None:
             raise ValueError("a frame-sharded model cannot run slots: detach it (parallel.attach) first")
         if x_T is not None or seed is None or t_start is not None:
@@ -214,7 +267,11 @@ class SlotSampler:
         elif x0_emb is not None:
             raise ValueError("x0_emb given to a sampler built with cond_frames = 0")
         c, uc = self._clip(c, (F, L, D), "c"), self._clip(uc, (F, L, D), "uc")
-        coef, ttab = self._schedule(int(S), eta)
+        dpm_coef = None
+        if method == "dpmpp":
+            coef, ttab, dpm_coef = self._dpm_schedule(int(S), discretize)
+        else:
+            coef, ttab = self._schedule(int(S), eta)
         n = int(coef.shape[0])
         if n > self.max_steps:
             raise ValueError(f"S = {S} makes a schedule of {n} entries, this sampler was built for max_steps = {self.max_steps}")
@@ -251,6 +308,12 @@ class SlotSampler:
             first = 1 if method == "plms" else 0
             self._state[s, :3].copy_(torch.tensor([first, 0, 2], dtype=torch.int32))
             self._left[s] = n + first
+        if self.dpm:
+            # the slot's sampler and its order rule, history invalid: the one host write of these words, the kernel walks the rest
+            words = [0, 0, int(order), int(bool(lower_order_final) and n < 15)] if dpm_coef is not None else [0, 0, 0, 0]
+            if dpm_coef is not None:
+                self._dpm_coef[s, :n].copy_(dpm_coef)
+            self._dpm_state[s].copy_(torch.tensor(words, dtype=torch.int32))
         return s
 
     # ---- the step ------------------------------------------------------------------------------------------------------------
@@ -272,9 +335,9 @@ class SlotSampler:
         return done
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
-        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=][, mask=, x0=, t_start=]): fills free slots in request order (a
-        request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
-        finishing order."""
+        """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=]
+        [, mask=, x0=, t_start=][, order=, lower_order_final=, discretize=]): fills free slots in request order (a request is taken
+        from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in finishing order."""
         it, tags, more = iter(requests), {}, True
         while True:
             while more and self.free_slots():
