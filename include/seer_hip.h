@@ -761,6 +761,35 @@ int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C, int32_t F
                            const float* scale, const float* coef, const float* dpm_coef, int32_t nsched, int32_t* step,
                            int32_t* state, const float* x, float* x_prev, float* d_hist, void* stream);
 
+/* ---- v-prediction: the output of a model trained on the velocity target (train.py:373-374, diffusers get_velocity), as eps -------------
+ * With x_t = sqrt(a) x0 + sqrt(1 - a) eps such a model gives v = sqrt(a) eps - sqrt(1 - a) x0, and a sampler needs
+ *   eps = sqrtf(a_t) * v + s1m * x_t          a_t = coef[4 r], s1m = coef[4 r + 3] of the DDIM coefficient row r of seer_cfg_ddim_step
+ * (rounded fp32 products, then the sum).  ONE elementwise launch in front of a step's last kernel, whichever sampler that is: the
+ * conversion is affine in v with the same x_t for both rows of a CFG pair, so converting the rows and then CFG-combining them is the eps
+ * of combining v first, and every update kernel above is unchanged.
+ *   v, out  fp32 [reps * b, C, F_total, HW], reps 1 (no CFG) or 2 (uc rows, then c rows); only frames >= cond_f are read or written (the
+ *           conditioning frames of a model output may hold anything, NaN included); out may be v;
+ *   x       fp32 [b, C, F_total - cond_f, HW], the latent the model was evaluated at: output row r reads x[r mod b].
+ *   seer_v_to_eps      row `index` from the host.
+ *   seer_v_to_eps_dev  inside a captured step, between seer_ddim_step_begin and the update: index = step[1], the word the begin kernel
+ *                      latched.  It is only read -- this kernel writes NO counter word, so "no kernel reads and writes the same word"
+ *                      holds for the step as before.  An index outside 0 .. nsched - 1 reads no row and writes no element.
+ *   seer_slot_v_to_eps over slots, CFG on: rows s and slots + s read x[s], row step[s][1] of coef[s] (fp32 [slots][nsched][4]).  With
+ *                      `state` (int32 [slots][8] of seer_slot_plms_step_begin; x_prov then required, NULL both otherwise) a slot whose
+ *                      IN-FLIGHT phase word (state[s][4]) is 2 was evaluated at x_prov[s] and t_table[max(index - 1, 0)]: it reads
+ *                      x_prov[s] and row max(index - 1, 0).  An idle slot, or a counter outside the table, leaves its rows untouched.
+ *                      No step or state word is written.
+ * SEER_EINVAL, nothing launched: a NULL required pointer, reps outside {1, 2}, b <= 0, slots outside 1 .. 4, non-positive extents,
+ * cond_f outside 0 .. F_total - 1, nsched < 1, a host index outside 0 .. nsched - 1, state without x_prov or the reverse, x_prov == x, a
+ * pointer that is not 4-byte aligned, a grid beyond one dimension. */
+int seer_v_to_eps(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, const float* coef,
+                  int32_t nsched, int32_t index, const float* x, float* out, void* stream);
+int seer_v_to_eps_dev(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                      const float* coef, int32_t nsched, const int32_t* step, const float* x, float* out, void* stream);
+int seer_slot_v_to_eps(const float* v, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, const float* coef,
+                       int32_t nsched, const int32_t* step, const int32_t* state /* NULL: no sampler per slot */, const float* x,
+                       const float* x_prov /* NULL with state */, float* out, void* stream);
+
 /* decoded image post-process of ddim_sample (utils/ddim_sampling_utils.py:41): clamp((x+1)/2, 0, 1) in place */
 int seer_clamp01(float* x, int64_t n, void* stream);
 
@@ -938,6 +967,15 @@ int seer_adamw8_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* 
 int seer_train_inputs(const float* moments, const float* eps_post, const float* noise, const int64_t* timesteps,
                       const float* alphas_cumprod, int32_t T, int32_t b, int32_t C, int32_t f1, int32_t f2, int32_t HW,
                       float latent_scale, float* model_input, float* latents, void* stream);
+
+/* The loss target of a v-prediction model (train.py:373-374, `noise_scheduler.get_velocity(latents, noise, timesteps)`):
+ *   target[bi, e] = sqrtf(a) * noise[bi, e] - sqrtf(1 - a) * latents[bi, e],   a = alphas_cumprod[timesteps[bi]]
+ * latents, noise, target fp32 [b, per_row] (the clean scaled latents seer_train_inputs writes, and its noise); timesteps int64 [b];
+ * alphas_cumprod fp32 [T].  A timestep outside [0, T) is clamped into the table, as in seer_train_inputs.  16-byte accesses when
+ * per_row % 4 == 0 and the three bases are 16-byte aligned, a scalar path otherwise.  SEER_EINVAL: a NULL pointer, T, b or per_row not
+ * positive, b above 65535 (the launch grid), a float pointer not 4-byte or timesteps not 8-byte aligned, a grid beyond its limit. */
+int seer_velocity_target(const float* latents, const float* noise, const int64_t* timesteps, const float* alphas_cumprod, int32_t T,
+                         int32_t b, int64_t per_row, float* target, void* stream);
 
 #ifdef __cplusplus
 }

@@ -183,6 +183,9 @@ SIGNATURES = {
     "seer_cfg_plms_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_cfg_dpm_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp], C.c_int),
+    "seer_v_to_eps_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_slot_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_clamp01": ([_vp, _i64, _vp], C.c_int),
     "seer_gaussian_sample": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),
     # training step
@@ -216,6 +219,7 @@ SIGNATURES = {
     "seer_adamw8_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp],
                          C.c_int),
     "seer_train_inputs": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp], C.c_int),
+    "seer_velocity_target": ([_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp], C.c_int),
 }
 
 

@@ -20,6 +20,9 @@ when `diffusers` is importable; without it the reference keeps its fp32 torch VA
 `SEER_COMPAT_SAMPLER=plms` (read by `install()`) makes the scripts sample with `PLMSSampler` under the name `DDIMSampler`: the
 yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluations).  `SEER_COMPAT_SAMPLER=dpmpp` makes it
 `DPMSolverSampler` (DPM-Solver++ 2M with its defaults, one evaluation per step; INTEGRATION.md says which `ddim_steps` to pick).
+`SEER_COMPAT_PREDICTION=v_prediction` (read by `install()`, or `install(prediction="v_prediction")`) makes that sampler, whichever it
+is, treat the UNet's output as the velocity v (a model fine-tuned with `prediction_type: v_prediction`, train.py:373-374); unset or
+`epsilon`, it is eps as before.
 `SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
 `CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
 then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
@@ -61,6 +64,8 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
             if spec.name == "ldm.models.diffusion.ddim_video" and _sampler == "dpmpp":
                 from seervideoldm_amd.dpm import DPMSolverSampler
                 mod.DDIMSampler = DPMSolverSampler
+            if spec.name == "ldm.models.diffusion.ddim_video" and _prediction == "v_prediction":
+                mod.DDIMSampler = _v_sampler(mod.DDIMSampler)
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -79,17 +84,35 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
 
 _finder = _AliasFinder()
 _sampler = None
+_prediction = None
+_v_samplers = {}            # sampler class -> its subclass whose prediction_type defaults to "v_prediction": one per class
+
+
+def _v_sampler(cls):
+    """`cls` with prediction_type="v_prediction" as its constructor's default: the scripts build their sampler without the keyword"""
+    if cls not in _v_samplers:
+        def __init__(self, *args, **kwargs):
+            kwargs.setdefault("prediction_type", "v_prediction")
+            cls.__init__(self, *args, **kwargs)
+        _v_samplers[cls] = type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__, "__module__": cls.__module__})
+    return _v_samplers[cls]
 _clip_saved = None          # (transformers module, its own CLIPTextModel) while the native text encoder stands in
 
 
-def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None) -> None:
+def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None,
+            prediction: Optional[str] = None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
     `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler, "dpmpp" its DPMSolverSampler; anything else keeps
     DDIMSampler.
+    `prediction` (default: the environment's SEER_COMPAT_PREDICTION) = "v_prediction" makes that class one whose constructor defaults
+    to prediction_type="v_prediction"; "epsilon" or nothing keeps it as it is; anything else is train.py:376's ValueError.
     `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
     CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
-    global _sampler, _clip_saved
+    global _sampler, _prediction, _clip_saved
     _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
+    _prediction = (os.environ.get("SEER_COMPAT_PREDICTION", "") if prediction is None else prediction).strip().lower()
+    if _prediction not in ("", "epsilon", "v_prediction"):
+        raise ValueError(f"Unknown prediction type {_prediction}")
     if (os.environ.get("SEER_COMPAT_CLIP", "") if clip is None else clip).strip().lower() == "native" and _clip_saved is None:
         import transformers
         from seervideoldm_amd import CLIPTextEncoder

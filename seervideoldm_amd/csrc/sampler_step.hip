@@ -1,7 +1,8 @@
 // The kernels at both ends of a sampler step on gfx950, fp32, one thread per latent element: "assemble the UNet input and latch the
-// counter", "CFG-combine eps and apply the DDIM, inversion, PLMS or DPM-Solver++ update", "re-noise the given latents".  Every form of
-// a step -- host index, device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update, invert_update,
-// plms_update, dpm_update, known_blend_at), so an element gets the same bits from each of them.
+// counter", "CFG-combine eps and apply the DDIM, inversion, PLMS or DPM-Solver++ update", "re-noise the given latents", and between the two
+// ends "turn a v-model's output into eps".  Every form of a step -- host index, device counter, seeded, over slots -- runs ONE device
+// body per idea (cfg_eps_at, step_update, invert_update, plms_update, dpm_update, eps_from_v, known_blend_at), so an element gets the
+// same bits from each of them.
 #include "seer_common.h"
 #include "seer_philox.h"
 #include <cstdint>
@@ -123,6 +124,25 @@ __device__ __forceinline__ void dpm_update(float e, const float* __restrict__ ro
     if (pred_x0) pred_x0[i] = d;
 }
 
+// A v-prediction model's output as eps (diffusers get_velocity read backwards): with x_t = sqrt(a) x0 + sqrt(1 - a) eps the model gives
+// v = sqrt(a) eps - sqrt(1 - a) x0, so eps = sqrt(a) v + sqrt(1 - a) x_t.  a_t and s1m are words 0 and 3 of the DDIM coefficient row of the
+// timestep the model was evaluated at.  Affine in v with the same x for both rows of a CFG pair: converting the rows and CFG-combining
+// them after gives the eps of combining first, so the conversion sits in front of the update kernels and those do not know of it.
+__device__ __forceinline__ float eps_from_v(float v, float x, float a_t, float s1m) { return sqrtf(a_t) * v + s1m * x; }
+
+// element i of out / v [rows, C, Ft - cond_f predicted frames of Ft, HW], counted over the predicted frames only: the conditioning
+// frames of the model output are neither read nor written.  xrow = the latent row [C, Ft - cond_f, HW] this output row was evaluated
+// at, `per` = its element count, e = i's offset in it.  out may alias v: the element is read before it is written.
+__device__ __forceinline__ void v_to_eps_at(const float* v, const float* __restrict__ xrow, const float* __restrict__ row, int C,
+                                            int Ft, int cond_f, int HW, int64_t r, int64_t e, float* out) {
+    const int Fp = Ft - cond_f;
+    const int hw = (int)(e % HW);
+    const int f = (int)((e / HW) % Fp);
+    const int c = (int)(e / ((int64_t)HW * Fp));
+    const int64_t off = ((r * C + c) * Ft + (f + cond_f)) * HW + hw;
+    out[off] = eps_from_v(v[off], xrow[e], row[0], row[3]);
+}
+
 // ---- one clip batch: the schedule index from the host, or in DEVICE memory (a whole p_sample_ddim captured in one hipGraph: the
 // kernel arguments of a replay are frozen, the step counter is not).  step[0] = index of the NEXT step to run, step[1] = index of the
 // step in flight.  seer_ddim_step_begin (first kernel of a step) reads step[0] everywhere and one thread copies it to step[1]; the
@@ -165,6 +185,21 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ eps, int cfg, int b, i
     step_update<DDIM_TERM>(cfg_eps_at(eps, cfg, b, C, Ft, cond_f, HW, scale, i), coef, index, x,
                            StepNoise{noise, seeds ? seeds + 2 * bi : nullptr, temperature, (uint32_t)(i - bi * per_clip)}, x_prev,
                            pred_x0, i);
+}
+
+// The conversion in front of an update kernel, for a model that predicts v: v [reps * b (uc rows then c rows, or b), C, Ft, HW] -> eps in
+// the same layout, frames >= cond_f only; output row r was evaluated at x[r mod b].  step == nullptr: the host's `index`; else index =
+// step[1], which seer_ddim_step_begin latched -- it is only read, NO counter word is written here: the kernel sits between the begin
+// kernel and the update kernel, and the update still finds step[1] as begin left it.  An index outside 0 .. nsched - 1 reads no row and
+// writes no element.  out may alias v.
+__global__ void v_to_eps_kernel(const float* v, int reps, int b, int C, int Ft, int cond_f, int HW, const float* __restrict__ coef,
+                                int nsched, int index, const int* __restrict__ step, const float* __restrict__ x, float* out) {
+    const int64_t per = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (step) index = step[1];
+    if (index < 0 || index >= nsched || i >= (int64_t)reps * b * per) return;
+    const int64_t r = i / per;
+    v_to_eps_at(v, x + (r % b) * per, coef + 4 * index, C, Ft, cond_f, HW, r, i - r * per, out);
 }
 
 // The inversion step.  step == nullptr: the host's `index`; else index = step[1], one thread writes step[0] = index + 1 (the chain
@@ -388,6 +423,29 @@ __global__ void slot_cfg_dpm_kernel(const float* __restrict__ eps, int slots, in
         if (first) step[2 * s] = index - 1;
         step_update<DDIM_TERM>(e, coef + (int64_t)s * nsched * 4, index, x, StepNoise{}, x_prev, d_hist, i);
     }
+}
+
+// v_to_eps_kernel over slots, between a slot begin kernel and a slot update kernel: rows s and slots + s of the [uc | c] pair are slot
+// s, converted with row step[s][1] of coef[s] against x[s].  state != nullptr (a queue with a sampler per slot, slots.py plms=True): the
+// slot's IN-FLIGHT phase word, as slot_assemble_kernel reads the next one; in phase 2 that kernel assembled x_prov[s] at
+// t_table[max(index - 1, 0)], so the conversion reads x_prov[s] and that row.  An idle slot, or a counter outside the table, leaves its
+// rows untouched; no step or state word is written.  out may alias v.
+__global__ void slot_v_to_eps_kernel(const float* v, int slots, int C, int Ft, int cond_f, int HW, const float* __restrict__ coef,
+                                     int nsched, const int* __restrict__ step, const int* __restrict__ state,
+                                     const float* __restrict__ x, const float* __restrict__ x_prov, float* out) {
+    const int64_t per = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 2 * (int64_t)slots * per) return;
+    const int64_t r = i / per;
+    const int s = (int)(r % slots);
+    int index = step[2 * s + 1];
+    if (index < 0 || index >= nsched) return;
+    const float* lat = x;
+    if (state && state[SLOT_STATE_WORDS * s + SLOT_IN_FLIGHT] == 2) {
+        lat = x_prov;
+        index = index > 0 ? index - 1 : 0;
+    }
+    v_to_eps_at(v, lat + s * per, coef + ((int64_t)s * nsched + index) * 4, C, Ft, cond_f, HW, r, i - r * per, out);
 }
 
 // ---- GIVEN latents (masked sampling, stochastic_encode; CompVis ldm/models/diffusion/ddim.py:144-147, 207-221): q(e) is the given
@@ -654,6 +712,37 @@ extern "C" int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C
     return launch_per_element(slot_cfg_dpm_kernel, elements(slots, C, (int64_t)F_total - cond_f, HW),
                               {eps, scale, coef, dpm_coef, step, state, x, x_prev, d_hist}, stream, eps, slots, C, F_total, cond_f, HW,
                               scale, coef, dpm_coef, nsched, step, state, x, x_prev, d_hist);
+}
+
+// v-prediction: the model output converted to eps in front of an update kernel; reps 1 (no CFG) or 2 (the [uc | c] pair); out may be v
+extern "C" int seer_v_to_eps(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                             const float* coef, int32_t nsched, int32_t index, const float* x, float* out, void* stream) {
+    if (!v || !coef || !x || !out || (reps != 1 && reps != 2) || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || nsched < 1 ||
+        index < 0 || index >= nsched)
+        return SEER_EINVAL;
+    return launch_per_element(v_to_eps_kernel, reps * elements(b, C, (int64_t)F_total - cond_f, HW), {v, coef, x, out}, stream, v, reps, b,
+                              C, F_total, cond_f, HW, coef, nsched, index, nullptr, x, out);
+}
+
+extern "C" int seer_v_to_eps_dev(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                 const float* coef, int32_t nsched, const int32_t* step, const float* x, float* out, void* stream) {
+    if (!v || !coef || !step || !x || !out || (reps != 1 && reps != 2) || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) ||
+        nsched < 1)
+        return SEER_EINVAL;
+    return launch_per_element(v_to_eps_kernel, reps * elements(b, C, (int64_t)F_total - cond_f, HW), {v, coef, step, x, out}, stream, v,
+                              reps, b, C, F_total, cond_f, HW, coef, nsched, 0, step, x, out);
+}
+
+// state and x_prov go together (NULL both: every slot is read as phase 0); slots 1..4 as in the slot updates' widest form
+extern "C" int seer_slot_v_to_eps(const float* v, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                  const float* coef, int32_t nsched, const int32_t* step, const int32_t* state, const float* x,
+                                  const float* x_prov, float* out, void* stream) {
+    if (!v || !coef || !step || !x || !out || (state != nullptr) != (x_prov != nullptr) || slots < 1 || slots > 4 || nsched < 1 ||
+        !update_shape_ok(C, F_total, cond_f, HW) || x_prov == x)
+        return SEER_EINVAL;
+    return launch_per_element(slot_v_to_eps_kernel, 2 * elements(slots, C, (int64_t)F_total - cond_f, HW),
+                              {v, coef, step, state, x, x_prov, out}, stream, v, slots, C, F_total, cond_f, HW, coef, nsched, step, state,
+                              x, x_prov, out);
 }
 
 // given latents: exactly one of noise and seeds; a clip's element index is a Philox counter word, as in the seeded steps

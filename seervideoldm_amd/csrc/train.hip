@@ -995,6 +995,33 @@ __global__ void __launch_bounds__(256) train_inputs_kernel(const float* __restri
     if (lat) st(lat + j, z);
 }
 
+// train.py:373-374, the loss target of a v-prediction model (diffusers DDPMScheduler.get_velocity): per batch row bi,
+// target = sqrt(a) noise - sqrt(1 - a) latents with a = alphas_cumprod[timesteps[bi]], rounded fp32 products and their difference in this
+// order.  grid (per_row / V / 256, b): the timestep and the table entry are block-uniform; V = 4: 16-byte loads and stores (per_row % 4
+// == 0, every base 16-byte aligned), V = 1 otherwise.  The timestep is clamped into the table as train_inputs_kernel clamps it.
+template <int V>
+__global__ void __launch_bounds__(256) velocity_target_kernel(const float* __restrict__ lat, const float* __restrict__ noise,
+                                                              const int64_t* __restrict__ ts, const float* __restrict__ acp, int T,
+                                                              int64_t per_row_v, float* __restrict__ target) {
+    const int64_t pv = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pv >= per_row_v) return;
+    const int64_t bi = blockIdx.y;
+    int64_t t = ts[bi];
+    t = t < 0 ? 0 : (t >= T ? T - 1 : t);
+    const float a = acp[t];
+    const float sa = sqrtf(a), sb = sqrtf(1.0f - a);
+    const int64_t j = (bi * per_row_v + pv) * V;
+    if constexpr (V == 4) {
+        const f32x4 l = *reinterpret_cast<const f32x4*>(lat + j), n = *reinterpret_cast<const f32x4*>(noise + j);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = sa * n[k] - sb * l[k];
+        *reinterpret_cast<f32x4*>(target + j) = o;
+    } else {
+        target[j] = sa * noise[j] - sb * lat[j];
+    }
+}
+
 }  // namespace
 
 extern "C" int seer_transpose_bf16(const void* x, int64_t rows, int32_t cols, int32_t ldx, void* y, int64_t ldy,
@@ -1364,6 +1391,26 @@ extern "C" int seer_train_inputs(const float* moments, const float* eps_post, co
     else
         hipLaunchKernelGGL(train_inputs_kernel<1>, grid, dim3(256), 0, st, moments, eps_post, noise, timesteps, alphas_cumprod, T,
                            C, f1, HWv, latent_scale, model_input, latents);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_velocity_target(const float* latents, const float* noise, const int64_t* timesteps, const float* alphas_cumprod,
+                                    int32_t T, int32_t b, int64_t per_row, float* target, void* stream) {
+    if (!latents || !noise || !timesteps || !alphas_cumprod || !target) return SEER_EINVAL;
+    if (T <= 0 || b <= 0 || b > 65535 || per_row <= 0) return SEER_EINVAL;                 // b: grid y
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(latents) | reinterpret_cast<uintptr_t>(noise) | reinterpret_cast<uintptr_t>(target);
+    if ((bases & 3) || (reinterpret_cast<uintptr_t>(alphas_cumprod) & 3) || (reinterpret_cast<uintptr_t>(timesteps) & 7)) return SEER_EINVAL;
+    const bool vec = per_row % 4 == 0 && (bases & 15) == 0;         // every row starts a multiple of per_row floats behind its base
+    const int64_t per_row_v = vec ? per_row / 4 : per_row;
+    const int64_t blocks = (per_row_v + 255) / 256;
+    if (blocks > 0x7fffffff) return SEER_EINVAL;
+    const dim3 grid((unsigned)blocks, (unsigned)b);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (vec)
+        hipLaunchKernelGGL(velocity_target_kernel<4>, grid, dim3(256), 0, st, latents, noise, timesteps, alphas_cumprod, T, per_row_v, target);
+    else
+        hipLaunchKernelGGL(velocity_target_kernel<1>, grid, dim3(256), 0, st, latents, noise, timesteps, alphas_cumprod, T, per_row_v, target);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }

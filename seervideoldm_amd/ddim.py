@@ -24,6 +24,12 @@ noise does not depend on the batch it is in.
 `encode` is DDIM inversion, the `encode()` CompVis added to ddim.py after the version the reference vendors: the probability-flow ODE
 upward from a clip's latents to a level of the schedule with the model in the loop (seer_cfg_ddim_invert_step; as a captured step its
 counter runs upward to a limit word in device memory, DESIGN.md "Editing"), so that decode comes back to the same clip.  Nothing is drawn.
+
+`DDIMSampler(device, prediction_type="v_prediction")` samples a model fine-tuned on the velocity target (train.py:373-374): the UNet's
+output is then v = sqrt(a) eps - sqrt(1 - a) x0, and ONE more elementwise kernel (seer_v_to_eps; in the captured step one more node,
+seer_v_to_eps_dev) turns it into eps = sqrt(a) v + sqrt(1 - a) x_t in front of the step's last kernel, with the coefficient row that
+kernel reads.  Everything behind it -- CFG, eta > 0, seeds, mask / x0, decode, stochastic_encode -- acts on eps or on latents and is
+unchanged.  `encode` is refused for such a model (see there).  With the default "epsilon" nothing new is launched or allocated.
 """
 from __future__ import annotations
 
@@ -58,6 +64,8 @@ class DDIMSampler(object):
         # the backend of the step's own kernels outside the captured step (tests inject a torch restatement to run this class on the
         # CPU; the captured step is taken with the HIP backend only)
         self.ops = kwargs.get("ops") or ops
+        # what the UNet's output is (train.py:371-376): "epsilon", or "v_prediction" -- converted to eps in front of every update
+        self.prediction_type = ops.check_prediction_type(kwargs.get("prediction_type", "epsilon"))
         self.consume_rng_when_deterministic = True
         # p_sample_ddim under graph replay hands out its static latent buffers instead of copies of them: the next step
         # overwrites what the previous one returned.  ddim_sampling sets it for its own loop (and copies what it keeps).
@@ -259,7 +267,10 @@ class DDIMSampler(object):
         the result is the latent at level t_enc: decode(t_start=t_enc) is the exact counterpart.  1 <= t_enc <= the schedule's entries.
         Returns (x_latent, {"x_inter": [...], "pred_x0": [...]}): with return_intermediates = k the lists hold copies of the latent
         and of pred_x0 after every k-th step (steps k - 1, 2k - 1, ...), otherwise they are empty.  callback(i) is called after
-        step i.  Inversion is eta = 0 by definition: NO draw is made from torch's generator, which is left where it was."""
+        step i.  Inversion is eta = 0 by definition: NO draw is made from torch's generator, which is left where it was.
+        Refused (NotImplementedError) with prediction_type="v_prediction": encode evaluates the model at the TARGET level's timestep on
+        a latent of the level below, so it is ambiguous which level's coefficients turn v into eps."""
+        self._refuse_v_inversion()
         if use_original_steps:
             raise NotImplementedError("only the DDIM-subsequence path that ddim_sample drives is built")
         n = int(self.ddim_timesteps.shape[0])
@@ -292,7 +303,9 @@ class DDIMSampler(object):
                       unconditional_conditioning=None, limit=None):
         """One step of encode: x at the level of row `index`'s a_prev, the model evaluated at t (encode passes the row's own timestep)
         -> (x_next at the level of a_t, pred_x0).  Nothing is drawn.  `limit`: the number of rows the chain this step belongs to may
-        use (encode's t_enc; the whole schedule when None) -- what the captured step's counter stops at."""
+        use (encode's t_enc; the whole schedule when None) -- what the captured step's counter stops at.  Refused for a v-model, as
+        encode is."""
+        self._refuse_v_inversion()
         n = int(self.ddim_coef.shape[0])
         limit = n if limit is None else int(limit)
         if not 0 <= int(index) < limit <= n:
@@ -310,6 +323,20 @@ class DDIMSampler(object):
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
         return self.ops.cfg_ddim_invert_step(eps.float().contiguous(), x, self.ddim_coef, int(index), cfg=cfg, scale=scale,
                                              cond_f=cond_f)
+
+    def _refuse_v_inversion(self):
+        if self.prediction_type != "epsilon":
+            raise NotImplementedError("DDIM inversion (encode / p_invert_ddim) of a v-prediction model: the step evaluates the model at "
+                                      "the target level's timestep on a latent of the level below, so it is ambiguous which level's "
+                                      "coefficients convert v to eps")
+
+    def _as_eps(self, out, x, index, cond_f):
+        """the model output `out` [2b or b, C, cond_f + F, h, w] of an evaluation at x and at schedule entry `index`'s timestep, as fp32
+        eps for the update kernel: itself, or -- a v-model -- through seer_v_to_eps with row `index` of the DDIM table"""
+        out = out.float().contiguous()
+        if self.prediction_type == "epsilon":
+            return out
+        return self.ops.v_to_eps(out, x, self.ddim_coef, int(index), cond_f=cond_f)
 
     @torch.no_grad()
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
@@ -342,21 +369,22 @@ class DDIMSampler(object):
         if known is not None:
             x = self.ops.known_blend(x.clone(), known[0], known[1], self.ddim_coef, index, seeds=seeds)
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        eps = self._as_eps(eps, x, index, cond_f)
         if seeds is not None:
-            return self.ops.cfg_ddim_step_rng(eps.float().contiguous(), x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale,
+            return self.ops.cfg_ddim_step_rng(eps, x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale,
                                               cond_f=cond_f, temperature=temperature)
         noise = None
         if sigma != 0. or self.consume_rng_when_deterministic:
             noise = torch.randn(x.shape, device=x.device) * temperature
             if sigma != 0.:
                 noise = _from_rank0(unet, noise)
-        return self.ops.cfg_ddim_step(eps.float().contiguous(), x, self.ddim_coef, index, cfg=cfg, scale=scale, cond_f=cond_f,
+        return self.ops.cfg_ddim_step(eps, x, self.ddim_coef, index, cfg=cfg, scale=scale, cond_f=cond_f,
                                       noise=noise if sigma != 0. else None)
 
     def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale):
         """the model call of p_sample_ddim (ddim_video.py:187-207): x0_emb in front of x along frames, batched CFG when uc has c's
         frame count, two calls otherwise.  Returns (eps [2b or b, C, cond_f + F, h, w], cfg, cond_f): the CFG combine and the
-        slicing off of the conditioning frames are the update kernel's."""
+        slicing off of the conditioning frames are the update kernel's.  For a v-model "eps" is v: the caller passes it through _as_eps."""
         cond_f = 0
         x_cat = x
         if x0_emb is not None:
@@ -431,7 +459,8 @@ class DDIMSampler(object):
         """the captured step of this kind / shape / CFG / scale (captured on first use) with x and its read-by-address inputs
         refreshed; None when the step cannot be captured.  `kind` is the key's first word and an entry of STEP_KINDS.  A seeded kind
         comes with its temperature, the key's last field: like the guidance scale it is an argument of the last kernel and frozen
-        into the capture; seeds, mask and given latents live in static buffers and are no part of the key."""
+        into the capture; seeds, mask and given latents live in static buffers and are no part of the key.  A v-model's step has one
+        more node and "v_prediction" as the key's very last word; the default's keys are what they were."""
         eng = None if self._capture_refused else capture_engine(unet, self.ops, x.device)
         if eng is None:
             return None
@@ -447,7 +476,8 @@ class DDIMSampler(object):
         ctx, L = eng._context(context)          # new prompt: the static context / K|V buffers are refreshed in place
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
         key = (kind, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv,
-               *(() if temperature is None else (float(temperature),)))
+               *(() if temperature is None else (float(temperature),)),
+               *(() if self.prediction_type == "epsilon" else (self.prediction_type,)))
         G = eng.graph_get(key)
         if G is None:
             G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L)
@@ -489,6 +519,8 @@ class DDIMSampler(object):
                 launch(G)
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
+            if self.prediction_type != "epsilon":       # in place, on the engine's output buffer: nothing is allocated for it
+                ops.v_to_eps_dev(eps, G["x"], G["coef"], G["step"], cond_f=f1, out=eps)
             update(G, eps, temperature, cfg=cfg, scale=scale, cond_f=f1)
         if capture_step(eng, key, G, body) is None:
             self._capture_refused = True

@@ -25,6 +25,9 @@ hipGraph replay -- seer_ddim_step_begin, the UNet, seer_cfg_dpm_step_dev -- capt
 the history is the step's own pred_x0 buffer, and the kernel picks its order from words in device memory, so a chain of replays needs
 no host-written scalar after its first step.
 
+prediction_type="v_prediction" (DDIMSampler's keyword) converts the model's v with the DDIM coefficient rows of this sampler's own
+timesteps, the log-SNR grid included, in front of either form of the step.
+
 Only the deterministic solver is built: no mask / x0, no seed, no eta > 0 (the SDE variant), no noise_dropout, no order 3, no
 singlestep (2S) form.  The per-step torch.randn draw of the reference's samplers is kept (consume_rng_when_deterministic), as in
 PLMSSampler.  A queue of clips runs this solver through SlotSampler(dpm=True) (slots.py): submit(method="dpmpp") with this
@@ -163,8 +166,8 @@ class DPMSolverSampler(DDIMSampler):
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
         if self.consume_rng_when_deterministic:
             torch.randn(x.shape, device=x.device)       # the reference's samplers draw in every update, also at sigma = 0
-        return self.ops.cfg_dpm_step(eps.float().contiguous(), x, self.dpm_coef, int(index), order, cfg=cfg, scale=scale, cond_f=cond_f,
-                                     d_prev=d_prev.to(torch.float32).contiguous() if order == 2 else None)
+        return self.ops.cfg_dpm_step(self._as_eps(eps, x, index, cond_f), x, self.dpm_coef, int(index), order, cfg=cfg, scale=scale,
+                                     cond_f=cond_f, d_prev=d_prev.to(torch.float32).contiguous() if order == 2 else None)
 
     def p_sample_ddim(self, *args, **kwargs):
         raise NotImplementedError("DPMSolverSampler steps with p_sample_dpm")

@@ -1387,6 +1387,75 @@ def slot_cfg_dpm_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, c
           "seer_slot_cfg_dpm_step")
 
 
+# ---- v-prediction (include/seer_hip.h, "v-prediction"): the model output converted to eps in front of a step's last kernel -----------
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
+def check_prediction_type(prediction_type: str) -> str:
+    """train.py:371-376: "epsilon" or "v_prediction"; anything else is the reference's ValueError"""
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"Unknown prediction type {prediction_type}")
+    return prediction_type
+
+
+def _req_v(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, cond_f: int, out: Optional[torch.Tensor]):
+    """v [reps * rows, C, F_total, h, w] next to x [rows, C, F_pred, h, w], out None (a new tensor) or shaped like v (v itself: in
+    place) -> (reps, rows, C, F_total, h * w, out)"""
+    _req(v, torch.float32, "v"); _req(x, torch.float32, "x"); _req(coef, torch.float32, "coef")
+    assert v.is_contiguous() and x.is_contiguous() and coef.is_contiguous() and coef.shape[-1] == 4
+    rows, Cc, Fp, h, w = x.shape
+    assert v.shape[0] in (rows, 2 * rows) and v.shape[1] == Cc and v.shape[2] == Fp + cond_f and v.shape[3:] == x.shape[3:]
+    if out is None:
+        out = torch.empty_like(v)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == v.shape
+    return v.shape[0] // rows, rows, Cc, Fp + cond_f, h * w, out
+
+
+def v_to_eps(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *, cond_f: int,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the output of a v-prediction model as eps: out[r, :, cond_f:] = sqrt(a_t) v[r, :, cond_f:] + sqrt(1 - a_t) x[r mod b] with row
+    `index` of coef [nsched, 4]; v [2b or b, C, F_total, h, w], x [b, C, F_pred, h, w] the latent the model was evaluated at.  The
+    conditioning frames of out are not written (a new tensor holds nothing defined there); out may be v (seer_v_to_eps)"""
+    reps, b, Cc, Ft, HW, out = _req_v(v, x, coef, cond_f, out)
+    if not 0 <= int(index) < coef.shape[0]:
+        raise ValueError(f"index {index}: the table has {coef.shape[0]} rows")
+    check(_lib.load().seer_v_to_eps(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], int(index), _p(x), _p(out),
+                                    _stream()), "seer_v_to_eps")
+    return out
+
+
+def v_to_eps_dev(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *, cond_f: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v_to_eps inside a captured step, between ddim_step_begin and the update: index = step[1], which is only read; an index
+    outside the table writes nothing (seer_v_to_eps_dev)"""
+    reps, b, Cc, Ft, HW, out = _req_v(v, x, coef, cond_f, out)
+    _req(step, torch.int32, "step")
+    assert step.numel() >= 2 and coef.dim() == 2
+    check(_lib.load().seer_v_to_eps_dev(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], _p(step), _p(x), _p(out),
+                                        _stream()), "seer_v_to_eps_dev")
+    return out
+
+
+def slot_v_to_eps(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *, cond_f: int,
+                  state: Optional[torch.Tensor] = None, x_prov: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """v_to_eps over slots (v [2 slots, ...]): slot s converts its two rows against x[s] with row step[s, 1] of coef[s]; with `state`
+    and `x_prov` (a queue with a sampler per slot) a slot in phase 2 reads x_prov[s] and the row below; an idle slot's rows are
+    untouched (seer_slot_v_to_eps)"""
+    reps, slots, Cc, Ft, HW, out = _req_v(v, x, coef, cond_f, out)
+    assert reps == 2, "slots evaluate the [uc | c] pair"
+    _req(step, torch.int32, "step")
+    _req_slot_tables(slots, coef, step)
+    if (state is None) != (x_prov is None):
+        raise ValueError("state and x_prov go together")
+    if state is not None:
+        _req_slot_plms(x, state, x_prov)
+    check(_lib.load().seer_slot_v_to_eps(_p(v), slots, Cc, Ft, cond_f, HW, _p(coef), coef.shape[1], _p(step), _p(state), _p(x),
+                                         _p(x_prov), _p(out), _stream()), "seer_slot_v_to_eps")
+    return out
+
+
 def clamp01_(x: torch.Tensor) -> torch.Tensor:
     _req(x, torch.float32, "x")
     assert x.is_contiguous()

@@ -53,7 +53,7 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
                    latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
                    plms: bool = False, stochastic: bool = False, editing: bool = False,
-                   dpm: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
+                   dpm: bool = False, prediction_type: str = "epsilon") -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
     empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
@@ -64,7 +64,8 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     builds it with editing=True: a request may then carry mask with known (the given latents, SlotSampler.submit's x0; they need a
     seed) and t_start; in a queue started without it those keys are a ValueError as well.  `dpm=True`
     builds it with dpm=True: a request may then name sampler = "dpmpp" and carry order, lower_order_final and discretize
-    (SlotSampler.submit); a request naming "dpmpp" without it is a ValueError.  The VAE encode
+    (SlotSampler.submit); a request naming "dpmpp" without it is a ValueError.  `prediction_type="v_prediction"`
+    builds it for a model fine-tuned on the velocity target: it belongs to the queue, not to a request.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -90,7 +91,8 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
                 _, c_l, _, h_l, w_l = x0_emb.shape
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
                                            max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic,
-                                           **(dict(editing=True) if editing else {}), **(dict(dpm=True) if dpm else {})))
+                                           **(dict(editing=True) if editing else {}), **(dict(dpm=True) if dpm else {}),
+                                           **(dict(prediction_type=prediction_type) if prediction_type != "epsilon" else {})))
             seeded = {k: r[k] for k in ("seed", "eta", "temperature") if k in r}
             edit = {k: r[k] for k in ("mask", "known", "t_start") if r.get(k) is not None}
             solver = {k: r[k] for k in ("order", "lower_order_final", "discretize") if k in r}
@@ -139,8 +141,11 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
     latents up to t_enc with the model in the loop, under `source_emb` (the prompt that describes `video`; default `text_emb`) at
     guidance `source_scale` (its unconditional branch is `empty_emb` when that scale is not 1), and sampler.decode brings them back
     under `text_emb` at `scale`: the clip itself under the source prompt, a structure-preserving edit under another.  Nothing is
-    drawn on this path, so `seed` may be None."""
+    drawn on this path, so `seed` may be None.  A sampler built with prediction_type="v_prediction" refuses it (NotImplementedError,
+    DDIMSampler.encode), before anything is encoded."""
     if invert:
+        if getattr(sampler, "prediction_type", "epsilon") != "epsilon":
+            sampler._refuse_v_inversion()
         if keep_mask is not None:
             raise ValueError("edit_clips: invert=True inverts the whole clip; `keep_mask` belongs to masked sampling")
         if strength is None:

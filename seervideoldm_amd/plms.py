@@ -98,7 +98,7 @@ class PLMSSampler(DDIMSampler):
                       score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, old_eps=None, t_next=None):
         """plms.py:172-236 -> (x_prev, pred_x0, e_t); e_t is this step's (first) CFG-combined eps, the one old_eps keeps.
-        Launch by launch (seer_cfg_plms_step)."""
+        Launch by launch (seer_cfg_plms_step; for a v-model seer_v_to_eps in front of each)."""
         if use_original_steps or noise_dropout > 0. or repeat_noise or quantize_denoised or score_corrector is not None:
             raise NotImplementedError("only the deterministic PLMS path over the DDIM subsequence is built")
         x = x.to(torch.float32).contiguous()
@@ -112,14 +112,17 @@ class PLMSSampler(DDIMSampler):
             if t_next is None:
                 raise ValueError("the first PLMS step (old_eps empty) needs t_next")
             self._consume_rng(x)
-            x_prov, _, e_t = ops.cfg_plms_step(eps.float().contiguous(), x, self.ddim_coef, index, 0, want_pred_x0=False, **kw)
+            x_prov, _, e_t = self.ops.cfg_plms_step(self._as_eps(eps, x, index, cond_f), x, self.ddim_coef, index, 0,
+                                                    want_pred_x0=False, **kw)
             eps2, _, _ = self._model_output(unet, x_prov, c, t_next, x0_emb, cond_frames, uc, scale)
             self._consume_rng(x)
-            x_prev, pred_x0, _ = ops.cfg_plms_step(eps2.float().contiguous(), x, self.ddim_coef, index, 1, history=[e_t], **kw)
+            # (a v-model's second evaluation was made at x_prov and at t_next = the timestep of entry max(index - 1, 0): that row)
+            x_prev, pred_x0, _ = self.ops.cfg_plms_step(self._as_eps(eps2, x_prov, max(int(index) - 1, 0), cond_f), x, self.ddim_coef,
+                                                        index, 1, history=[e_t], **kw)
         else:
             self._consume_rng(x)
-            x_prev, pred_x0, e_t = ops.cfg_plms_step(eps.float().contiguous(), x, self.ddim_coef, index, len(history) + 1,
-                                                     history=history, **kw)
+            x_prev, pred_x0, e_t = self.ops.cfg_plms_step(self._as_eps(eps, x, index, cond_f), x, self.ddim_coef, index,
+                                                          len(history) + 1, history=history, **kw)
         return x_prev, pred_x0, e_t
 
     def _consume_rng(self, x):

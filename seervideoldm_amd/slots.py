@@ -46,6 +46,11 @@ opens with seer_slot_known_blend, which re-noises a slot's given latents to the 
 its seed and blends them in where the slot's mask says so.  A slot whose mask is all zero -- every plain clip -- is not touched by it,
 so edited and plain clips share a queue, and a plain clip has the bits it has in a queue built without the keyword.
 
+With `prediction_type="v_prediction"` (per sampler object, not per request: the parameterisation belongs to the model) the UNet's output
+is the velocity v, and the step gains one launch between the model and the update, seer_slot_v_to_eps: every slot's rows become eps
+with the slot's own coefficient row -- for a PLMS clip's second evaluation the row below and the provisional latent it was made at.
+It holds in every mode above, under a key of its own, and the promise reads against the solo sampler built with the same keyword.
+
 Out of scope: PLMS with noise or with a mask, DPM-Solver++ with noise, with a mask or from a start level, PLMS and DPM-Solver++ in one
 queue, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
@@ -78,11 +83,13 @@ class SlotSampler:
     stochastic=True); it excludes plms=True as well.  `dpm=True` lets a request choose DPM-Solver++ (submit's `method`, `order`,
     `lower_order_final`, `discretize`): the step's last kernel then carries a sampler per slot, DDIM or DPM-Solver++, over two more
     static buffers, under a key of its own; it excludes plms, stochastic and editing (the solo DPMSolverSampler has no seeded or masked
-    form for a slot to be bit-equal to)."""
+    form for a slot to be bit-equal to).  `prediction_type` "epsilon" (the default: nothing changes) or "v_prediction": what the
+    UNet's output is (train.py:371-376; anything else is its ValueError), in every mode."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
                  model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False,
-                 dpm: bool = False):
+                 dpm: bool = False, prediction_type: str = "epsilon"):
+        self.prediction_type = hip_ops.check_prediction_type(prediction_type)
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -358,6 +365,9 @@ class SlotSampler:
         for name, args in self._front:
             getattr(self.ops, name)(*args)
         eps = model()
+        if self.prediction_type != "epsilon":        # v -> eps, in place on the model's output, per slot
+            phases = dict(state=self._state, x_prov=self._xprov) if self.plms else {}
+            self.ops.slot_v_to_eps(eps, self._x, self._coef, self._step, cond_f=self.f1, out=eps, **phases)
         name, args = self._update
         getattr(self.ops, name)(eps, self._x, self._scale, self._coef, self._step, *args, cond_f=self.f1, x_prev=self._x,
                                 pred_x0=self._pred)
@@ -377,7 +387,8 @@ class SlotSampler:
         model = lambda: eng._forward(self._sample, self._t, ctx, L, self.model_cond_frame)
         G = None
         if not self._capture_refused and capture_engine(unet, self.ops, self.device) is not None:
-            key = (self._kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv)
+            key = (self._kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv,
+                   *(() if self.prediction_type == "epsilon" else (self.prediction_type,)))
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)

@@ -445,3 +445,24 @@ def train_inputs(moments: torch.Tensor, eps_post: Optional[torch.Tensor], noise:
     check(_lib.load().seer_train_inputs(_p(moments), _p(eps_post), _p(noise), _p(timesteps), _p(alphas_cumprod), T, b, Cc, f1, f2,
                                         H * W, float(latent_scale), _p(out), _p(latents), _stream()), "seer_train_inputs")
     return out
+
+
+def velocity_target(latents: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor, alphas_cumprod: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """train.py:373-374, `noise_scheduler.get_velocity(latents, noise, timesteps)` in one launch (seer_velocity_target): per batch row
+    sqrt(a) noise - sqrt(1 - a) latents with a = alphas_cumprod[timesteps[row]].  latents and noise fp32 of one shape [b, ...],
+    timesteps int64 [b], alphas_cumprod fp32 [T].  A timestep outside [0, T) is clamped into the table by the kernel (the trainer's
+    timesteps have passed train_inputs' check by then).  Returns the target (`out`, when given), shaped like noise."""
+    _req(latents, torch.float32, "latents"); _req(noise, torch.float32, "noise"); _req(alphas_cumprod, torch.float32, "alphas_cumprod")
+    _req(timesteps, torch.int64, "timesteps")
+    assert latents.is_contiguous() and noise.is_contiguous() and latents.shape == noise.shape and noise.dim() >= 1
+    assert alphas_cumprod.dim() == 1 and alphas_cumprod.is_contiguous() and timesteps.is_contiguous()
+    b = noise.shape[0]
+    assert timesteps.shape == (b,) and b > 0 and noise.numel() > 0
+    if out is None:
+        out = torch.empty_like(noise)
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.shape == noise.shape
+    check(_lib.load().seer_velocity_target(_p(latents), _p(noise), _p(timesteps), _p(alphas_cumprod), alphas_cumprod.numel(), b,
+                                           noise.numel() // b, _p(out), _stream()), "seer_velocity_target")
+    return out

@@ -163,8 +163,14 @@ def _pack_fstext_fp32(sd: Dict[str, torch.Tensor], num_layers: int) -> "Dict[str
 class SeerTrainer:
     def __init__(self, unet: SeerUNet, fstext: FSTextTransformer, *, lr: float = 1e-4, betas=(0.9, 0.999),
                  weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, gradient_accumulation_steps: int = 1,
-                 text_loss: bool = False, use_8bit_adam: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None):
+                 text_loss: bool = False, use_8bit_adam: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None,
+                 prediction_type: str = "epsilon"):
         self.ops, self.tops = ops, tops
+        # train.py:371-376 (the scheduler's prediction_type): the loss target is the noise, or -- "v_prediction" -- the velocity
+        # sqrt(a) noise - sqrt(1 - a) latents (seer_velocity_target); forward_backward itself does not know which
+        self.prediction_type = hip_ops.check_prediction_type(prediction_type)
+        if self.prediction_type != "epsilon" and not hasattr(tops, "velocity_target"):
+            raise ValueError("prediction_type='v_prediction' needs a training backend with velocity_target (train_ops.velocity_target)")
         # train.py:214-222 / configs/train.yaml:27: AdamW with block-wise quantised 8-bit moments (seer_adamw8_step; this project's
         # own state format, not bitsandbytes').  The clip, the data-parallel averaging and the accumulation do not change.
         self.use_8bit_adam = bool(use_8bit_adam)
@@ -890,15 +896,25 @@ class SeerTrainer:
                    use_graph: bool = False):
         """train.py:355-387 after the VAE encode: DDPM add_noise, concat the conditioning latents, forward, loss, backward,
         clip, AdamW (the optimizer runs every `gradient_accumulation_steps` calls).  alphas_cumprod: the scheduler's table
-        (fp32 [T])."""
-        a = alphas_cumprod.to(latents.device, f32)[timesteps].reshape(-1, 1, 1, 1, 1)
+        (fp32 [T]).  The loss target is the noise, or with prediction_type="v_prediction" the velocity (train.py:371-374)."""
+        acp = alphas_cumprod.to(latents.device, f32)
+        a = acp[timesteps].reshape(-1, 1, 1, 1, 1)
         noisy = a.sqrt() * latents + (1 - a).sqrt() * noise               # DDPMScheduler.add_noise (input preparation)
         x = torch.cat([latents_x0, noisy], 2)
-        loss = self.forward_backward(x, noise, timesteps, text_cond_emb, latents_x0.shape[2], use_graph=use_graph,
+        target = self._loss_target(latents, noise, timesteps, acp)
+        loss = self.forward_backward(x, target, timesteps, text_cond_emb, latents_x0.shape[2], use_graph=use_graph,
                                      on_unet_grads=self.start_unet_allreduce if self.pg is not None else None)
         if self.accumulate():
             self.optimizer_step(lr)
         return loss
+
+    def _loss_target(self, latents, noise, timesteps, acp):
+        """train.py:371-376: the noise, or the velocity of (latents, noise) at the timesteps -- one launch, seer_velocity_target"""
+        if self.prediction_type == "epsilon":
+            return noise
+        dev = noise.device
+        t = torch.as_tensor(timesteps).to(dev, torch.int64).reshape(-1).expand(noise.shape[0]).contiguous()
+        return self.tops.velocity_target(latents.to(dev, f32).contiguous(), noise.to(dev, f32).contiguous(), t, acp.contiguous())
 
     def step_from_batch(self, video: torch.Tensor, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, *,
                         vae, text_encoder, cond_frames: int, alphas_cumprod: torch.Tensor, lr: Optional[float] = None,
@@ -913,7 +929,8 @@ class SeerTrainer:
             model_input   = train_ops.train_inputs(...)   sample, * 0.18215, add_noise, concat  train.py:349-354,364-365
             forward_backward, accumulate, optimizer_step(lr)                                   train.py:344-345,367-387
         ONE encode where the reference makes two: every norm of the VAE and its attention are per image, so the split of the
-        frames over two calls is not semantic.  Epsilon prediction only (train.py:371-372).
+        frames over two calls is not semantic.  The loss target follows the trainer's prediction_type (train.py:371-376): the noise, or
+        -- "v_prediction" -- the velocity, from the clean latents that train_inputs then also writes (its `latents` output).
         Random numbers that are not passed in are drawn as train.py draws them, in its order:
             1. posterior noise of the frames to predict,  torch.randn([b*f2, 4, h, w]) on the device    train.py:349
             2. posterior noise of the conditioning frames, torch.randn([b*f1, 4, h, w]) on the device   train.py:350
@@ -953,10 +970,12 @@ class SeerTrainer:
             timesteps = torch.randint(0, T, (b,), device=dev)                                       # draw 4 (train.py:360-362)
         timesteps = torch.as_tensor(timesteps).to(dev, torch.int64).reshape(b).contiguous()
         acp = alphas_cumprod.to(dev, f32).contiguous()
+        latents = torch.empty_like(noise) if self.prediction_type != "epsilon" else None
         model_input = self.tops.train_inputs(moments.contiguous(), posterior_noise, noise, timesteps, acp, f1,
-                                             _timesteps_in_range=drawn)
+                                             _timesteps_in_range=drawn, **({} if latents is None else dict(latents=latents)))
         self.last_inputs = (model_input, noise, timesteps, text_cond_emb)
-        loss = self.forward_backward(model_input, noise, timesteps, text_cond_emb, f1, use_graph=use_graph,
+        target = self._loss_target(latents, noise, timesteps, acp)
+        loss = self.forward_backward(model_input, target, timesteps, text_cond_emb, f1, use_graph=use_graph,
                                      on_unet_grads=self.start_unet_allreduce if self.pg is not None else None)
         if self.accumulate():
             self.optimizer_step(lr)
