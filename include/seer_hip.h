@@ -492,34 +492,38 @@ int seer_nchw_f32_to_nhwc_bf16(const float* x, int32_t N, int32_t C, int32_t HW,
 int seer_nhwc_bf16_to_nchw_f32(const void* x, int32_t N, int32_t C, int32_t HW, float* y, void* stream);
 
 /* ---- sampler step ------------------------------------------------------------------------ */
+/* One export per kernel: a step kernel's mode is read from which of its pointers are set, each mode keeps its own checks, and a
+ * half-set mode is SEER_EINVAL, never a silent switch.  The schedule index has exactly one source:
+ *   host form    step == NULL and index >= 0;
+ *   device form  step != NULL and index == SEER_INDEX_FROM_STEP: the index is step[1], for a step that is captured WHOLE in one
+ *                hipGraph (kernel arguments are frozen at capture, the step counter must not be).  step: int32[2] in device memory;
+ *                step[0] = index of the next step to run, step[1] = index of the step in flight.
+ * Any other combination is refused, so a forgotten `step` does not run as row 0 from the host.  (seer_known_blend, below, keeps its
+ * older rule: `step` when set, `index` otherwise.) */
+#define SEER_INDEX_FROM_STEP (-1)
+
 /* CFG combine + DDIM update of DDIMSampler.p_sample_ddim (ldm/models/diffusion/ddim_video.py:209-238), fp32:
  *   e   = e_uc + scale*(e_c - e_uc)            (only frames >= cond_f of the UNet output are used)
  *   x0  = (x - sqrt(1-a_t) e)/sqrt(a_t)
  *   x'  = sqrt(a_prev) x0 + sqrt(1-a_prev-sigma^2) e + sigma*noise
  * eps: UNet output [2b (uc then c), C, F_total, HW] fp32 (or [b,...] with scale==1 / e_uc NULL semantics:
  * pass cfg=0); x, x_prev, pred_x0: [b, C, F_pred, HW].  coef: device fp32 [steps][4] = (a_t, a_prev, sigma, sqrt(1-a_t)),
- * row `index` is used (no host->device scalar copies per step, unlike ddim_video.py:219-222). */
-int seer_cfg_ddim_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                       int32_t HW, float scale, const float* coef, int32_t index, const float* x,
-                       const float* noise /* may be NULL when sigma==0 */, float* x_prev, float* pred_x0, void* stream);
-
-/* The same step with its schedule index in device memory, for a p_sample_ddim that is captured WHOLE in one hipGraph (kernel
- * arguments are frozen at capture, the step counter must not be).  step: int32[2]; step[0] = index of the next step to run,
- * step[1] = index of the step in flight.
- *   seer_ddim_step_begin    (ddim_video.py:189,201-203) first kernel of a step: sample[reps*b, C, f1 + F_pred, HW] =
- *                           cat([x0_emb, x], frames) repeated `reps` times (2 = the [uc, c] CFG pair), t_out[reps*b] =
- *                           t_table[step[0]], and step[1] = step[0];
- *   seer_cfg_ddim_step_dev  last kernel: seer_cfg_ddim_step with index = step[1]; then step[0] = index - 1.  x_prev may be x.
- *                           A counter that ran past the schedule's end, step[1] < 0 (a replay after the chain's last step), still
- *                           gives step[0] = index - 1, but reads no coefficient row and writes no element of x_prev or pred_x0.
+ * row `index` is used (no host->device scalar copies per step, unlike ddim_video.py:219-222).  x_prev may be x; pred_x0 may be NULL.
+ *   index source  host form, or device form: the last kernel of a captured step, which then writes step[0] = index - 1.  A counter
+ *                 that ran past the schedule's end, step[1] < 0 (a replay after the chain's last step), still gives step[0] =
+ *                 index - 1, but reads no coefficient row and writes no element of x_prev or pred_x0.
+ *   noise source  at most one of `noise` (a tensor shaped like x; NULL when sigma == 0) and `seeds` ("seeded noise" below, which
+ *                 alone reads `temperature`, bounds the clip and asks for aligned pointers); both set is SEER_EINVAL.
+ * seer_ddim_step_begin (ddim_video.py:189,201-203) is the first kernel of a captured step: sample[reps*b, C, f1 + F_pred, HW] =
+ * cat([x0_emb, x], frames) repeated `reps` times (2 = the [uc, c] CFG pair), t_out[reps*b] = t_table[step[0]], and step[1] = step[0].
  * No kernel reads and writes the same word, so replays of the captured step walk the schedule downwards on their own; the host
  * writes step[0] only to start a chain. */
+int seer_cfg_ddim_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale,
+                       const float* coef, int32_t index, int32_t* step, const float* x, const float* noise, const uint32_t* seeds,
+                       float temperature, float* x_prev, float* pred_x0, void* stream);
 int seer_ddim_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, int32_t b, int32_t reps, int32_t C,
                          int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t* step, float* sample,
                          int64_t* t_out, void* stream);
-int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                           float scale, const float* coef, int32_t* step, const float* x, const float* noise, float* x_prev,
-                           float* pred_x0, void* stream);
 
 /* The captured step over SLOTS (continuous batching, seervideoldm_amd/slots.py): the two kernels above with `slots` in the place of
  * b and everything a replay must not freeze held per slot in device memory.  Row r of a [reps*slots, ...] tensor belongs to slot
@@ -528,19 +532,24 @@ int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
  *   seer_slot_step_begin     for every slot s: index = step[s][0], then step[s][1] = index; the sample rows of slot s =
  *                            cat([x0_emb[s], x[s]], frames), `reps` (1 or 2) times; t_out[rep*slots + s] = t_table[s][max(index, 0)].
  *                            An idle slot (index < 0) gets finite rows as long as its x / x0_emb are (the host zeroes them).
+ *                            x_prov and state are NULL both, or set both: a sampler per slot, "a SAMPLER per slot" below.
  *   seer_slot_cfg_ddim_step  for every slot s: index = step[s][1].  index >= 0: the update of seer_cfg_ddim_step with cfg = 1,
- *                            scale[s], row `index` of coef[s] and no noise term (eta = 0) -- the same device code, so an element gets
- *                            the bits seer_cfg_ddim_step gives it -- then step[s][0] = index - 1.  index < 0 (or >= nsched, which no
+ *                            scale[s] and row `index` of coef[s] -- the same device code, so an element gets the bits
+ *                            seer_cfg_ddim_step gives it -- then step[s][0] = index - 1.  index < 0 (or >= nsched, which no
  *                            schedule produces): nothing of that slot is written, neither x_prev nor pred_x0 nor step.
+ *                            seeds and temperature are NULL both (eta = 0, no noise term) or set both ("seeded noise" below).
  *                            x_prev may be x; pred_x0 may be NULL.
  * No kernel reads and writes the same word: replays walk every slot's schedule with no host-written scalar; the host writes
  * step[s][0] only when it fills slot s.  Every pointer must be 4-byte aligned and no more (the int64 tables move as 32-bit words);
- * SEER_EINVAL otherwise, and for slots < 1, nsched < 1, reps outside {1, 2}, cond_f >= F_total, a NULL pointer. */
-int seer_slot_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, int32_t slots, int32_t reps, int32_t C,
-                         int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched, int32_t* step,
-                         float* sample, int64_t* t_out, void* stream);
+ * SEER_EINVAL otherwise, and for slots < 1, nsched < 1, reps outside {1, 2}, cond_f >= F_total, a NULL required pointer, one of a
+ * pointer pair without the other. */
+int seer_slot_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, const float* x_prov /* NULL with state */,
+                         int32_t slots, int32_t reps, int32_t C, int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table,
+                         int32_t nsched, int32_t* step, int32_t* state /* NULL: no sampler per slot */, float* sample, int64_t* t_out,
+                         void* stream);
 int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                            const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x, float* x_prev,
+                            const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
+                            const uint32_t* seeds /* NULL: eta = 0 */, const float* temperature /* NULL with seeds */, float* x_prev,
                             float* pred_x0, void* stream);
 
 /* DDIM inversion (CompVis ldm/models/diffusion/ddim.py, encode(); eta = 0 by definition): the same CFG combine, then the update one
@@ -548,22 +557,18 @@ int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t 
  *   x0     = (x - sqrt(1-a_prev) e)/sqrt(a_prev)
  *   x_next = sqrt(a_t) x0 + sqrt(1-a_t) e          (sqrt(1-a_t) = column 3 of the row; sigma, column 2, is not read)
  * eps, coef and the shapes as in seer_cfg_ddim_step; x_next may be x; pred_x0 (= x0) may be NULL: it is then not written.
- *   seer_cfg_ddim_invert_step      row `index` of coef, from the host.
- *   seer_cfg_ddim_invert_step_dev  last kernel of a captured inversion step behind seer_ddim_step_begin: index = step[1], then
- *                                  step[0] = index + 1 -- replays walk the schedule upwards.  limit: int32[1] in DEVICE memory, the
- *                                  number of rows the chain may use (the arguments of a replay are frozen, and the rows of a static
- *                                  table beyond the schedule hold a_prev = 0, which the update divides by).  For index < 0 or
- *                                  index >= limit[0] step[0] is written all the same, but no coefficient row is read and no element
- *                                  of x_next or pred_x0 written; limit[0] = 0 makes a launch write nothing but that word.
- * No kernel reads and writes the same word.  SEER_EINVAL for a NULL required pointer (eps, coef, x, x_next; step and limit),
- * b <= 0, non-positive extents, cond_f < 0 or >= F_total, index < 0 from the host, a pointer that is not 4-byte aligned, a grid
- * beyond one dimension. */
+ *   host form    row `index` of coef; limit is NULL.
+ *   device form  last kernel of a captured inversion step behind seer_ddim_step_begin: index = step[1], then step[0] = index + 1 --
+ *                replays walk the schedule upwards.  limit: int32[1] in DEVICE memory, the number of rows the chain may use (the
+ *                arguments of a replay are frozen, and the rows of a static table beyond the schedule hold a_prev = 0, which the
+ *                update divides by).  For index < 0 or index >= limit[0] step[0] is written all the same, but no coefficient row is
+ *                read and no element of x_next or pred_x0 written; limit[0] = 0 makes a launch write nothing but that word.
+ * No kernel reads and writes the same word.  SEER_EINVAL for a NULL required pointer (eps, coef, x, x_next), an index source that
+ * is neither form, limit without step or step without limit, b <= 0, non-positive extents, cond_f < 0 or >= F_total, a pointer
+ * that is not 4-byte aligned, a grid beyond one dimension. */
 int seer_cfg_ddim_invert_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                              float scale, const float* coef, int32_t index, const float* x, float* x_next,
-                              float* pred_x0 /* NULL: not written */, void* stream);
-int seer_cfg_ddim_invert_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                                  float scale, const float* coef, int32_t* step, const int32_t* limit, const float* x,
-                                  float* x_next, float* pred_x0, void* stream);
+                              float scale, const float* coef, int32_t index, int32_t* step, const int32_t* limit, const float* x,
+                              float* x_next, float* pred_x0 /* NULL: not written */, void* stream);
 
 /* ---- seeded noise: the DDIM step with eta > 0 and no noise tensor ------------------------------------------------------------
  * A counter-based generator, Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), runs
@@ -582,30 +587,16 @@ int seer_cfg_ddim_invert_step_dev(const float* eps, int32_t cfg, int32_t b, int3
  *                       that any counter can be asked for; the samplers' streams have a zero high word.
  *   seer_philox_normal  out[0 .. n-1] = the first n normals of (seed, stream, index), 0 < n < 2^31; nothing is written past
  *                       out[n-1].  The start code of a seeded clip is stream 0, index 0.
- *   seer_cfg_ddim_step_rng / seer_cfg_ddim_step_rng_dev
- *                       seer_cfg_ddim_step / seer_cfg_ddim_step_dev with seeds (one pair per batch row) and temperature in the place
- *                       of noise: where row `index` of coef has sigma != 0, element e of row bi gets stream-1 noise of seeds[bi] at
- *                       that index -- the bits of seer_cfg_ddim_step given noise = temperature * seer_philox_normal(seed, 1, index);
- *                       where sigma == 0 nothing is drawn and the bits are seer_cfg_ddim_step's with noise = NULL.  _dev: index =
- *                       step[1], then step[0] = index - 1; an index < 0 writes no latent.  x_prev may be x; pred_x0 may be NULL.
- *   seer_slot_cfg_ddim_step_rng
- *                       seer_slot_cfg_ddim_step with seeds uint32 [slots][2] and temperature fp32 [slots] in device memory; sigma is
- *                       column 2 of the slot's own coef rows.  An idle slot (index < 0 or >= nsched) writes nothing.  Its first
- *                       kernel is seer_slot_step_begin, unchanged.
- * SEER_EINVAL as in the entry points they restate (NULL required pointers, non-positive extents, cond_f >= F_total, a pointer that
- * is not 4-byte aligned), and for a clip of C * F_pred * HW >= 2^31 elements. */
+ *   seer_cfg_ddim_step with `seeds` (one pair per batch row) and `temperature`, `noise` NULL
+ *                       where row `index` of coef has sigma != 0, element e of row bi gets stream-1 noise of seeds[bi] at that
+ *                       index -- the bits of the same call given noise = temperature * seer_philox_normal(seed, 1, index); where
+ *                       sigma == 0 nothing is drawn and the bits are those of noise = NULL.  Either index source.
+ *   seer_slot_cfg_ddim_step with `seeds` uint32 [slots][2] and `temperature` fp32 [slots] in device memory
+ *                       sigma is column 2 of the slot's own coef rows.  An idle slot (index < 0 or >= nsched) writes nothing.
+ * With seeds set, SEER_EINVAL also for a pointer that is not 4-byte aligned and for a clip of C * F_pred * HW >= 2^31 elements. */
 int seer_philox_u32(uint64_t seed, uint64_t stream, uint32_t index, uint64_t first_block, int64_t n_blocks, uint32_t* out,
                     void* hip_stream);
 int seer_philox_normal(uint64_t seed, uint32_t stream, uint32_t index, int64_t n, float* out, void* hip_stream);
-int seer_cfg_ddim_step_rng(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                           float scale, const float* coef, int32_t index, const float* x, const uint32_t* seeds, float temperature,
-                           float* x_prev, float* pred_x0, void* stream);
-int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                               float scale, const float* coef, int32_t* step, const float* x, const uint32_t* seeds,
-                               float temperature, float* x_prev, float* pred_x0, void* stream);
-int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                                const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
-                                const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0, void* stream);
 
 /* ---- given latents: masked sampling and stochastic_encode (CompVis ldm/models/diffusion/ddim.py:144-147, 207-221) --------------
  * q(e) = sqrtf(a_t) * x0[e] + s1m * n[e]: the given latent x0 noised to the level of coefficient row `index` (a_t = column 0, s1m =
@@ -646,14 +637,14 @@ int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int3
                        const float* h2, const float* h3, float* x_prev, float* pred_x0, float* e_out, void* stream);
 
 /* The same update for a step captured whole in one hipGraph (seer_ddim_step_begin -> UNet -> this kernel): index = step[1], then
- * step[0] = index - 1, as seer_cfg_ddim_step_dev.  The history is a ring of three slots, ring fp32 [3][b*C*F_pred*HW].
+ * step[0] = index - 1, as seer_cfg_ddim_step's device form.  The history is a ring of three slots, ring fp32 [3][b*C*F_pred*HW].
  * ring_state int32[4] = (valid, newest) for even indices, then (valid, newest) for odd ones: a step reads the pair of its own
  * index's parity -- valid in 0..3 earlier e, h1 = slot newest, h2 = slot (newest+2)%3, h3 = slot (newest+1)%3 -- runs order 0
  * for valid = 0 and order valid+1 otherwise, stores e into slot s = (newest+1)%3 (the oldest slot once all three are valid), and
  * one thread writes (min(valid+1, 3), s) into the pair of parity (index-1).  No kernel reads and writes the same word, so replays
  * walk the schedule and the ring with no host-written scalars; the host writes step[0] and the pair of the first index to start
  * a chain.  A pair outside those ranges is read as (0, 2).  x may alias x_prev.
- * step[1] < 0, as in seer_cfg_ddim_step_dev: step[0] and the pair of parity (index-1) are written as above, no coefficient row is
+ * step[1] < 0, as in seer_cfg_ddim_step: step[0] and the pair of parity (index-1) are written as above, no coefficient row is
  * read and no element of x_prev, pred_x0 or the ring is written. */
 int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                            float scale, const float* coef, int32_t* step, float* ring, int32_t* ring_state, const float* x,
@@ -671,29 +662,27 @@ int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, 
  *   word 2  c_x = sigma_t / sigma_s        word 3  c_D1 = -alpha_t (exp(-h) - 1)     order 1: x_prev = word2 x + word3 D
  *   word 4  c_D2 = c_D1 (1 + 1/(2r))       word 5  c_Dprev = -c_D1 / (2r)            order 2: x_prev = word2 x + word4 D + word5 d_prev
  * The top entry of a schedule has no entry above it, so no r: its words 4 and 5 are (c_D1, 0), and a chain never runs it at order 2.
- *   seer_cfg_dpm_step      row `index` and `order` (1 or 2) from the host.  d_prev is read at order 2 only (NULL or any contents, NaN
- *                          included, at order 1).  x_prev may be x and pred_x0 (NULL: not written) may be d_prev: every thread reads
- *                          its element of each before it writes it.
- *   seer_cfg_dpm_step_dev  last kernel of a step captured whole in one hipGraph behind seer_ddim_step_begin: index = step[1], then
- *                          step[0] = index - 1.  d_hist [b, C, F_pred, HW] is history and output at once: the D of the step before
- *                          is read from it (order 2 only) and this step's D written over it.  state int32[4] in device memory =
- *                          (history valid for an even index, history valid for an odd index, the sampler's order 1 or 2, nonzero
- *                          when a schedule's final step -- index 0 -- is first order).  A step reads the valid word of its own
- *                          index's parity and runs order 2 when that word is 1, state[2] is 2 and not (index == 0 and state[3] !=
- *                          0), else order 1; one thread writes the valid word of parity (index - 1): 1 when this launch stored a D,
- *                          0 when it did not.  state[2] and state[3] are only read, so no kernel reads and writes the same word and
- *                          replays walk a schedule with no host-written scalar: to start a chain the host writes step[0] and zeroes
- *                          state[0..1]; state[2..3] change with the sampler's settings and the schedule only.  An index outside
- *                          0 .. nsched - 1: the two words are written all the same, no table row is read and no element written.
- * SEER_EINVAL for a NULL required pointer (eps, x, coef, x_prev; d_prev at order 2; step, state, d_hist), b <= 0, non-positive
- * extents, cond_f < 0 or >= F_total, nsched < 1, from the host an index outside 0 .. nsched - 1 or an order other than 1 and 2, a
- * pointer that is not 4-byte aligned, a grid beyond one dimension. */
+ *   host form    row `index` and `order` (1 or 2); state is NULL.  d_prev is read at order 2 only (NULL or any contents, NaN
+ *                included, at order 1).  x_prev may be x and pred_x0 (NULL: not written) may be d_prev: every thread reads its
+ *                element of each before it writes it.
+ *   device form  last kernel of a step captured whole in one hipGraph behind seer_ddim_step_begin: index = step[1], then step[0] =
+ *                index - 1; `order` is not read and d_prev is NULL.  pred_x0 [b, C, F_pred, HW], required, is history and output at
+ *                once: the D of the step before is read from it (order 2 only) and this step's D written over it.  state int32[4]
+ *                in device memory = (history valid for an even index, history valid for an odd index, the sampler's order 1 or 2,
+ *                nonzero when a schedule's final step -- index 0 -- is first order).  A step reads the valid word of its own
+ *                index's parity and runs order 2 when that word is 1, state[2] is 2 and not (index == 0 and state[3] != 0), else
+ *                order 1; one thread writes the valid word of parity (index - 1): 1 when this launch stored a D, 0 when it did
+ *                not.  state[2] and state[3] are only read, so no kernel reads and writes the same word and replays walk a
+ *                schedule with no host-written scalar: to start a chain the host writes step[0] and zeroes state[0..1];
+ *                state[2..3] change with the sampler's settings and the schedule only.  An index outside 0 .. nsched - 1: the two
+ *                words are written all the same, no table row is read and no element written.
+ * SEER_EINVAL for a NULL required pointer (eps, x, coef, x_prev; d_prev at order 2; pred_x0 in the device form), an index source
+ * that is neither form, state without step or step without state, d_prev in the device form, b <= 0, non-positive extents, cond_f
+ * < 0 or >= F_total, nsched < 1, from the host an index >= nsched or an order other than 1 and 2, a pointer that is not 4-byte
+ * aligned, a grid beyond one dimension. */
 int seer_cfg_dpm_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale,
-                      const float* x, const float* coef, int32_t nsched, int32_t index, int32_t order, const float* d_prev,
-                      float* x_prev, float* pred_x0 /* NULL: not written */, void* stream);
-int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                          float scale, const float* x, const float* coef, int32_t nsched, int32_t* step, int32_t* state,
-                          float* x_prev, float* d_hist, void* stream);
+                      const float* x, const float* coef, int32_t nsched, int32_t index, int32_t order, int32_t* step, int32_t* state,
+                      const float* d_prev, float* x_prev, float* pred_x0, void* stream);
 
 /* The captured step over slots with a SAMPLER per slot: DDIM and PLMS clips side by side in one step (slots.py, plms=True).  The
  * buffers of the two slot entry points above, and per slot in device memory
@@ -703,7 +692,8 @@ int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, i
  *   x_prov  fp32 [slots][C*F_pred*HW]: the provisional latent of a PLMS clip's first step.
  * phase 0 = a DDIM clip, for all its steps; 1 = a PLMS clip's first step, first evaluation; 2 = its second evaluation; 3 = every
  * later PLMS step.  A clip of n schedule entries takes n calls of the pair with phase 0, n + 1 with PLMS.
- *   seer_slot_plms_step_begin  seer_slot_step_begin, and for every slot s: the in-flight words of state[s] = its next words; in
+ *   seer_slot_step_begin with x_prov and state
+ *                              for every slot s as above, and the in-flight words of state[s] = its next words; in
  *                              phase 2 the sample rows come from x_prov[s] instead of x[s] and t_out is t_table[s][max(index - 1,
  *                              0)], the NEXT timestep (plms.py:145).  An idle slot is treated the same way (finite rows as long as
  *                              x, x0_emb and x_prov are).
@@ -727,15 +717,12 @@ int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, i
  * the update reads in-flight words and writes next words.  The host writes step[s][0] and the next words of state[s] -- (1, 0, 2)
  * for PLMS, (0, 0, 2) for DDIM -- only when it fills slot s.  Every pointer must be 4-byte aligned and no more; SEER_EINVAL
  * otherwise, for everything the two entry points above refuse, for a NULL state, ring or x_prov, and for x_prov == x. */
-int seer_slot_plms_step_begin(const float* x0_emb /* NULL iff f1 == 0 */, const float* x, const float* x_prov, int32_t slots,
-                              int32_t reps, int32_t C, int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table,
-                              int32_t nsched, int32_t* step, int32_t* state, float* sample, int64_t* t_out, void* stream);
 int seer_slot_cfg_plms_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                             const float* scale, const float* coef, int32_t nsched, int32_t* step, int32_t* state, float* ring,
                             const float* x, float* x_prov, float* x_prev, float* pred_x0, void* stream);
 
 /* The captured step over slots with DDIM and DPM-Solver++ clips side by side (slots.py, dpm=True): the per-slot form of
- * seer_cfg_dpm_step_dev, as seer_slot_cfg_ddim_step is of seer_cfg_ddim_step_dev.  Its first kernel is seer_slot_step_begin,
+ * seer_cfg_dpm_step's device form, as seer_slot_cfg_ddim_step is of seer_cfg_ddim_step's.  Its first kernel is seer_slot_step_begin,
  * unchanged: DPM-Solver++ needs no provisional latent and no second evaluation.  Per slot in device memory, beside scale[s],
  * coef[s] (fp32 [slots][nsched][4], the DDIM rows) and step[s][0..1] of seer_slot_cfg_ddim_step:
  *   dpm_coef  fp32 [slots][nsched][6]: a DPM table per slot, the six words per row of seer_cfg_dpm_step;
@@ -770,22 +757,20 @@ int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C, int32_t F
  *   v, out  fp32 [reps * b, C, F_total, HW], reps 1 (no CFG) or 2 (uc rows, then c rows); only frames >= cond_f are read or written (the
  *           conditioning frames of a model output may hold anything, NaN included); out may be v;
  *   x       fp32 [b, C, F_total - cond_f, HW], the latent the model was evaluated at: output row r reads x[r mod b].
- *   seer_v_to_eps      row `index` from the host.
- *   seer_v_to_eps_dev  inside a captured step, between seer_ddim_step_begin and the update: index = step[1], the word the begin kernel
- *                      latched.  It is only read -- this kernel writes NO counter word, so "no kernel reads and writes the same word"
- *                      holds for the step as before.  An index outside 0 .. nsched - 1 reads no row and writes no element.
+ *   seer_v_to_eps      host form: row `index`.  Device form, inside a captured step between seer_ddim_step_begin and the update:
+ *                      index = step[1], the word the begin kernel latched.  It is only read -- this kernel writes NO counter word,
+ *                      so "no kernel reads and writes the same word" holds for the step as before.  An index outside 0 .. nsched - 1
+ *                      reads no row and writes no element.
  *   seer_slot_v_to_eps over slots, CFG on: rows s and slots + s read x[s], row step[s][1] of coef[s] (fp32 [slots][nsched][4]).  With
- *                      `state` (int32 [slots][8] of seer_slot_plms_step_begin; x_prov then required, NULL both otherwise) a slot whose
+ *                      `state` (int32 [slots][8] of seer_slot_step_begin; x_prov then required, NULL both otherwise) a slot whose
  *                      IN-FLIGHT phase word (state[s][4]) is 2 was evaluated at x_prov[s] and t_table[max(index - 1, 0)]: it reads
  *                      x_prov[s] and row max(index - 1, 0).  An idle slot, or a counter outside the table, leaves its rows untouched.
  *                      No step or state word is written.
  * SEER_EINVAL, nothing launched: a NULL required pointer, reps outside {1, 2}, b <= 0, slots outside 1 .. 4, non-positive extents,
- * cond_f outside 0 .. F_total - 1, nsched < 1, a host index outside 0 .. nsched - 1, state without x_prov or the reverse, x_prov == x, a
- * pointer that is not 4-byte aligned, a grid beyond one dimension. */
+ * cond_f outside 0 .. F_total - 1, nsched < 1, an index source that is neither form, a host index >= nsched, state without x_prov or
+ * the reverse, x_prov == x, a pointer that is not 4-byte aligned, a grid beyond one dimension. */
 int seer_v_to_eps(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, const float* coef,
-                  int32_t nsched, int32_t index, const float* x, float* out, void* stream);
-int seer_v_to_eps_dev(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                      const float* coef, int32_t nsched, const int32_t* step, const float* x, float* out, void* stream);
+                  int32_t nsched, int32_t index, const int32_t* step, const float* x, float* out, void* stream);
 int seer_slot_v_to_eps(const float* v, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, const float* coef,
                        int32_t nsched, const int32_t* step, const int32_t* state /* NULL: no sampler per slot */, const float* x,
                        const float* x_prov /* NULL with state */, float* out, void* stream);

@@ -5,8 +5,9 @@
 The fixture pins the bits of the sampler-step kernels (csrc/sampler_step.hip): tests/test_gpu_step_parent.py compares the library
 under test against it, every form of a case against the one recorded result.  It is recorded on the GPU from the PARENT of a
 change to those kernels -- a library built from a checkout of that commit, named by SEER_HIP_LIB -- never from the code under
-test, which is why the variable has to be set.  The Python side (ops.py) is the tree's own: the entry points and their arguments
-are the same on both sides of such a change.
+test, which is why the variable has to be set.  The Python side (ops.py) is the tree's own, so the parent library must be of the
+tree's ABI: a change that renames an entry point or moves its arguments (ABI 27 folded the sampler step's twins) cannot be
+recorded across, and the fixture in the tree stays as it was recorded.
 
 What every form of a case shares is taken from the case's first form; the forms are also compared among themselves here, and a
 parent whose forms disagree is reported and not recorded."""

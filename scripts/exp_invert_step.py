@@ -2,7 +2,7 @@
 with closed-form weights), guidance 7.5:
 
   * the captured DDIM step of `sample` (the deterministic "step" graph: the path of bench.py), the captured inversion step of `encode`
-    ("invert": the same UNet graph with seer_cfg_ddim_invert_step_dev as its last kernel) and `encode` launch by launch
+    ("invert": the same UNet graph with seer_cfg_ddim_invert_step in its device form as its last kernel) and `encode` launch by launch
     (unet.use_graph off).  The variants alternate inside one process; a step's time is the median over the steps of a chain after the
     first (device events recorded by `callback`), a variant's figure the median over the chains, with the spread printed;
   * the round trip encode -> decode on the mini UNet of the sampler tests (closed-form weights, no guidance, the whole schedule) at

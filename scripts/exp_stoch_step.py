@@ -3,7 +3,7 @@ UNet with closed-form weights), S = 30, unet.use_graph on:
 
   * unseeded, eta = 0.5: every step launch by launch around the UNet's own graph, a torch.randn between two UNet evaluations
     (what DDIMSampler did before `seed` existed, and still does without one);
-  * seeded, eta = 0.5: ONE replay per step, the noise drawn inside seer_cfg_ddim_step_rng_dev;
+  * seeded, eta = 0.5: ONE replay per step, the noise drawn inside seer_cfg_ddim_step (seeds, device index);
   * eta = 0, unseeded: the deterministic captured step, for scale.
 
 The variants alternate inside one process; a step's time is the median over the steps of a sample after the first (device events

@@ -13,7 +13,7 @@ _PKG = Path(__file__).resolve().parent
 _LIB_PATH = _PKG / "lib" / "libseer_hip.so"
 _lib = None
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 SEER_GEMM_PLAIN = 0
 SEER_GEMM_CONV3X3 = 1
@@ -26,6 +26,7 @@ SEER_EPI_COLSCALE = 32
 SEER_EPI_F16 = 64
 SEER_EPI_QUICKGELU = 128
 SEER_ENOSYS = -38
+SEER_INDEX_FROM_STEP = -1      # `index` of a sampler-step call whose index is step[1] in device memory (include/seer_hip.h)
 SEER_DT_BF16, SEER_DT_F16 = 0, 1
 SEER_ATTN_Q_PRESCALED = 1
 SEER_ATTN_F16 = 2
@@ -159,32 +160,24 @@ SIGNATURES = {
     "seer_cast_f32": ([_vp, _i64, _vp, _i32, _vp], C.c_int),
     "seer_nchw_f32_to_nhwc_bf16": ([_vp, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "seer_nhwc_bf16_to_nchw_f32": ([_vp, _i32, _i32, _i32, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_ddim_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
     "seer_ddim_step_begin": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_invert_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_invert_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_slot_step_begin": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_slot_cfg_ddim_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_ddim_invert_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_slot_step_begin": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_slot_cfg_ddim_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_philox_u32": ([_u64, _u64, _u32, _u64, _i64, _vp, _vp], C.c_int),
     "seer_philox_normal": ([_u64, _u32, _u32, _i64, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_ddim_step_rng_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp], C.c_int),
-    "seer_slot_cfg_ddim_step_rng": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_q_sample": ([_vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_known_blend": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_known_blend": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp], C.c_int),
-    "seer_slot_plms_step_begin": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_cfg_plms_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
                                 C.c_int),
     "seer_slot_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_cfg_plms_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp], C.c_int),
     "seer_cfg_plms_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_cfg_dpm_step_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp], C.c_int),
-    "seer_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp], C.c_int),
-    "seer_v_to_eps_dev": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_clamp01": ([_vp, _i64, _vp], C.c_int),
     "seer_gaussian_sample": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),

@@ -512,7 +512,11 @@ __global__ void slot_known_blend_kernel(float* x, const float* __restrict__ mask
                    i);
 }
 
-// ---- host side: every export states its own NULL and range conditions, then launches through launch_per_element -----------------------
+// ---- host side: every export states its own NULL and range conditions, then launches through launch_per_element.  One export per
+// kernel: the mode is read from which pointers are set, each mode keeps its own checks, and a half-set mode is refused ---------------
+// exactly one index source: the host's `index` with no step words, or the step words with index == SEER_INDEX_FROM_STEP
+inline bool index_source_ok(int32_t index, const void* step) { return step ? index == SEER_INDEX_FROM_STEP : index >= 0; }
+
 // the latent a step updates, [rows, C, F_total - cond_f, HW]
 inline bool update_shape_ok(int32_t C, int32_t F_total, int32_t cond_f, int32_t HW) {
     return C > 0 && HW > 0 && cond_f >= 0 && cond_f < F_total;
@@ -533,8 +537,10 @@ inline int64_t elements(int32_t rows, int32_t C, int64_t F, int32_t HW) { return
 // one thread per element, 256 to a block.  `aligned`: the pointers (NULL passes) the export refuses unless they are 4-byte aligned --
 // the slot, seeded and given-latents kernels rely on that and no more, the int64 tables included.  A grid beyond one dimension is
 // refused.
+using Pointers = std::initializer_list<const void*>;
+
 template <typename... P, typename... A>
-int launch_per_element(void (*kernel)(P...), int64_t n, std::initializer_list<const void*> aligned, void* stream, A... args) {
+int launch_per_element(void (*kernel)(P...), int64_t n, Pointers aligned, void* stream, A... args) {
     for (const void* p : aligned)
         if (reinterpret_cast<uintptr_t>(p) & 3) return SEER_EINVAL;
     const int64_t blocks = (n + 255) / 256;
@@ -546,12 +552,17 @@ int launch_per_element(void (*kernel)(P...), int64_t n, std::initializer_list<co
 
 }  // namespace
 
+// at most one of noise and seeds; the seeded mode alone bounds the clip and asks for aligned pointers, and it alone reads temperature
 extern "C" int seer_cfg_ddim_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                  int32_t HW, float scale, const float* coef, int32_t index, const float* x,
-                                  const float* noise, float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !coef || !x || !x_prev || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || index < 0) return SEER_EINVAL;
-    return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW), {}, stream, eps, cfg, b, C, F_total, cond_f, HW,
-                              scale, coef, index, nullptr, x, noise, nullptr, 0.f, x_prev, pred_x0);
+                                  int32_t HW, float scale, const float* coef, int32_t index, int32_t* step, const float* x,
+                                  const float* noise, const uint32_t* seeds, float temperature, float* x_prev, float* pred_x0,
+                                  void* stream) {
+    if (!eps || !coef || !x || !x_prev || b <= 0 || !index_source_ok(index, step) || (noise && seeds) ||
+        !(seeds ? philox_clip_ok(C, F_total, cond_f, HW) : update_shape_ok(C, F_total, cond_f, HW)))
+        return SEER_EINVAL;
+    return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW),
+                              seeds ? Pointers{eps, coef, step, x, seeds, x_prev, pred_x0} : Pointers{}, stream, eps, cfg, b, C, F_total,
+                              cond_f, HW, scale, coef, step ? 0 : index, step, x, noise, seeds, seeds ? temperature : 0.f, x_prev, pred_x0);
 }
 
 extern "C" int seer_ddim_step_begin(const float* x0_emb, const float* x, int32_t b, int32_t reps, int32_t C, int32_t f1,
@@ -563,45 +574,15 @@ extern "C" int seer_ddim_step_begin(const float* x0_emb, const float* x, int32_t
                               t_table, step, sample, t_out);
 }
 
-extern "C" int seer_cfg_ddim_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                      int32_t HW, float scale, const float* coef, int32_t* step, const float* x,
-                                      const float* noise, float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !coef || !step || !x || !x_prev || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
-    return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW), {}, stream, eps, cfg, b, C, F_total, cond_f, HW,
-                              scale, coef, 0, step, x, noise, nullptr, 0.f, x_prev, pred_x0);
-}
-
-extern "C" int seer_cfg_ddim_step_rng(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                      int32_t HW, float scale, const float* coef, int32_t index, const float* x,
-                                      const uint32_t* seeds, float temperature, float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !coef || !x || !seeds || !x_prev || b <= 0 || !philox_clip_ok(C, F_total, cond_f, HW) || index < 0) return SEER_EINVAL;
-    return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, x, seeds, x_prev, pred_x0}, stream, eps,
-                              cfg, b, C, F_total, cond_f, HW, scale, coef, index, nullptr, x, nullptr, seeds, temperature, x_prev,
-                              pred_x0);
-}
-
-extern "C" int seer_cfg_ddim_step_rng_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                          int32_t HW, float scale, const float* coef, int32_t* step, const float* x,
-                                          const uint32_t* seeds, float temperature, float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !coef || !step || !x || !seeds || !x_prev || b <= 0 || !philox_clip_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
-    return launch_per_element(cfg_ddim_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, step, x, seeds, x_prev, pred_x0}, stream,
-                              eps, cfg, b, C, F_total, cond_f, HW, scale, coef, 0, step, x, nullptr, seeds, temperature, x_prev, pred_x0);
-}
-
+// the device form carries its limit word, the host form has none
 extern "C" int seer_cfg_ddim_invert_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                         int32_t HW, float scale, const float* coef, int32_t index, const float* x, float* x_next,
-                                         float* pred_x0, void* stream) {
-    if (!eps || !coef || !x || !x_next || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || index < 0) return SEER_EINVAL;
-    return launch_per_element(cfg_ddim_invert_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, x, x_next, pred_x0}, stream, eps,
-                              cfg, b, C, F_total, cond_f, HW, scale, coef, index, nullptr, nullptr, x, x_next, pred_x0);
-}
-
-extern "C" int seer_cfg_ddim_invert_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
-                                             int32_t HW, float scale, const float* coef, int32_t* step, const int32_t* limit,
-                                             const float* x, float* x_next, float* pred_x0, void* stream) {
-    if (!eps || !coef || !step || !limit || !x || !x_next || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
+                                         int32_t HW, float scale, const float* coef, int32_t index, int32_t* step,
+                                         const int32_t* limit, const float* x, float* x_next, float* pred_x0, void* stream) {
+    if (!eps || !coef || !x || !x_next || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || !index_source_ok(index, step) ||
+        (limit != nullptr) != (step != nullptr))
+        return SEER_EINVAL;
     return launch_per_element(cfg_ddim_invert_kernel, elements(b, C, F_total - cond_f, HW), {eps, coef, step, limit, x, x_next, pred_x0},
-                              stream, eps, cfg, b, C, F_total, cond_f, HW, scale, coef, 0, step, limit, x, x_next, pred_x0);
+                              stream, eps, cfg, b, C, F_total, cond_f, HW, scale, coef, step ? 0 : index, step, limit, x, x_next, pred_x0);
 }
 
 extern "C" int seer_cfg_plms_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f,
@@ -624,43 +605,26 @@ extern "C" int seer_cfg_plms_step_dev(const float* eps, int32_t cfg, int32_t b, 
                               scale, coef, step, ring, ring_state, x, x_prev, pred_x0);
 }
 
+// host form: `order` 1 or 2, d_prev at order 2.  Device form: step and state, and pred_x0 is the history -- the kernel reads it as
+// d_prev and takes its order from state
 extern "C" int seer_cfg_dpm_step(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                                  float scale, const float* x, const float* coef, int32_t nsched, int32_t index, int32_t order,
-                                 const float* d_prev, float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !x || !coef || !x_prev || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || nsched < 1 || index < 0 ||
-        index >= nsched || (order != 1 && order != 2) || (order == 2 && !d_prev))
+                                 int32_t* step, int32_t* state, const float* d_prev, float* x_prev, float* pred_x0, void* stream) {
+    if (!eps || !x || !coef || !x_prev || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || nsched < 1 ||
+        !index_source_ok(index, step) || (state != nullptr) != (step != nullptr) ||
+        (step ? !pred_x0 || d_prev : index >= nsched || (order != 1 && order != 2) || (order == 2 && !d_prev)))
         return SEER_EINVAL;
-    return launch_per_element(cfg_dpm_kernel, elements(b, C, F_total - cond_f, HW), {eps, x, coef, d_prev, x_prev, pred_x0}, stream, eps,
-                              cfg, b, C, F_total, cond_f, HW, scale, coef, nsched, index, order, nullptr, nullptr, x, d_prev, x_prev,
-                              pred_x0);
+    return launch_per_element(cfg_dpm_kernel, elements(b, C, F_total - cond_f, HW), {eps, x, coef, step, state, d_prev, x_prev, pred_x0},
+                              stream, eps, cfg, b, C, F_total, cond_f, HW, scale, coef, nsched, step ? 0 : index, step ? 1 : order, step,
+                              state, x, step ? pred_x0 : d_prev, x_prev, pred_x0);
 }
 
-extern "C" int seer_cfg_dpm_step_dev(const float* eps, int32_t cfg, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                                     float scale, const float* x, const float* coef, int32_t nsched, int32_t* step, int32_t* state,
-                                     float* x_prev, float* d_hist, void* stream) {
-    if (!eps || !x || !coef || !step || !state || !x_prev || !d_hist || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) ||
-        nsched < 1)
-        return SEER_EINVAL;
-    return launch_per_element(cfg_dpm_kernel, elements(b, C, F_total - cond_f, HW), {eps, x, coef, step, state, x_prev, d_hist}, stream,
-                              eps, cfg, b, C, F_total, cond_f, HW, scale, coef, nsched, 0, 1, step, state, x, d_hist, x_prev, d_hist);
-}
-
-extern "C" int seer_slot_step_begin(const float* x0_emb, const float* x, int32_t slots, int32_t reps, int32_t C, int32_t f1,
-                                    int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched, int32_t* step, float* sample,
-                                    int64_t* t_out, void* stream) {
-    if (!x || !t_table || !step || !sample || !t_out || slots < 1 || nsched < 1 || (reps != 1 && reps != 2) ||
-        !begin_shape_ok(x0_emb, C, f1, F_pred, HW))
-        return SEER_EINVAL;
-    return launch_per_element(slot_assemble_kernel, elements(slots, C, (int64_t)f1 + F_pred, HW),
-                              {x0_emb, x, t_table, step, sample, t_out}, stream, x0_emb, x, nullptr, slots, reps, C, f1, F_pred, HW,
-                              reinterpret_cast<const int*>(t_table), nsched, step, nullptr, sample, reinterpret_cast<int*>(t_out));
-}
-
-extern "C" int seer_slot_plms_step_begin(const float* x0_emb, const float* x, const float* x_prov, int32_t slots, int32_t reps,
-                                         int32_t C, int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched,
-                                         int32_t* step, int32_t* state, float* sample, int64_t* t_out, void* stream) {
-    if (!x || !x_prov || !t_table || !step || !state || !sample || !t_out || slots < 1 || nsched < 1 || (reps != 1 && reps != 2) ||
-        !begin_shape_ok(x0_emb, C, f1, F_pred, HW) || x_prov == x)
+// x_prov and state go together (NULL both: every slot is read as phase 0)
+extern "C" int seer_slot_step_begin(const float* x0_emb, const float* x, const float* x_prov, int32_t slots, int32_t reps, int32_t C,
+                                    int32_t f1, int32_t F_pred, int32_t HW, const int64_t* t_table, int32_t nsched, int32_t* step,
+                                    int32_t* state, float* sample, int64_t* t_out, void* stream) {
+    if (!x || !t_table || !step || !sample || !t_out || (x_prov != nullptr) != (state != nullptr) || slots < 1 || nsched < 1 ||
+        (reps != 1 && reps != 2) || !begin_shape_ok(x0_emb, C, f1, F_pred, HW) || x_prov == x)
         return SEER_EINVAL;
     return launch_per_element(slot_assemble_kernel, elements(slots, C, (int64_t)f1 + F_pred, HW),
                               {x0_emb, x, x_prov, t_table, step, state, sample, t_out}, stream, x0_emb, x, x_prov, slots, reps, C, f1,
@@ -668,22 +632,13 @@ extern "C" int seer_slot_plms_step_begin(const float* x0_emb, const float* x, co
                               reinterpret_cast<int*>(t_out));
 }
 
+// seeds and temperature go together (NULL both: eta = 0); the seeded mode alone bounds the clip
 extern "C" int seer_slot_cfg_ddim_step(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
                                        const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
-                                       float* x_prev, float* pred_x0, void* stream) {
-    if (!eps || !scale || !coef || !step || !x || !x_prev || slots < 1 || nsched < 1 || !update_shape_ok(C, F_total, cond_f, HW))
-        return SEER_EINVAL;
-    return launch_per_element(slot_cfg_ddim_kernel, elements(slots, C, (int64_t)F_total - cond_f, HW),
-                              {eps, scale, coef, step, x, x_prev, pred_x0}, stream, eps, slots, C, F_total, cond_f, HW, scale, coef,
-                              nsched, step, x, nullptr, nullptr, x_prev, pred_x0);
-}
-
-extern "C" int seer_slot_cfg_ddim_step_rng(const float* eps, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                                           const float* scale, const float* coef, int32_t nsched, int32_t* step, const float* x,
-                                           const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0,
-                                           void* stream) {
-    if (!eps || !scale || !coef || !step || !x || !seeds || !temperature || !x_prev || slots < 1 || nsched < 1 ||
-        !philox_clip_ok(C, F_total, cond_f, HW))
+                                       const uint32_t* seeds, const float* temperature, float* x_prev, float* pred_x0,
+                                       void* stream) {
+    if (!eps || !scale || !coef || !step || !x || !x_prev || (seeds != nullptr) != (temperature != nullptr) || slots < 1 ||
+        nsched < 1 || !(seeds ? philox_clip_ok(C, F_total, cond_f, HW) : update_shape_ok(C, F_total, cond_f, HW)))
         return SEER_EINVAL;
     return launch_per_element(slot_cfg_ddim_kernel, elements(slots, C, (int64_t)F_total - cond_f, HW),
                               {eps, scale, coef, step, x, seeds, temperature, x_prev, pred_x0}, stream, eps, slots, C, F_total, cond_f,
@@ -716,21 +671,13 @@ extern "C" int seer_slot_cfg_dpm_step(const float* eps, int32_t slots, int32_t C
 
 // v-prediction: the model output converted to eps in front of an update kernel; reps 1 (no CFG) or 2 (the [uc | c] pair); out may be v
 extern "C" int seer_v_to_eps(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                             const float* coef, int32_t nsched, int32_t index, const float* x, float* out, void* stream) {
+                             const float* coef, int32_t nsched, int32_t index, const int32_t* step, const float* x, float* out,
+                             void* stream) {
     if (!v || !coef || !x || !out || (reps != 1 && reps != 2) || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || nsched < 1 ||
-        index < 0 || index >= nsched)
-        return SEER_EINVAL;
-    return launch_per_element(v_to_eps_kernel, reps * elements(b, C, (int64_t)F_total - cond_f, HW), {v, coef, x, out}, stream, v, reps, b,
-                              C, F_total, cond_f, HW, coef, nsched, index, nullptr, x, out);
-}
-
-extern "C" int seer_v_to_eps_dev(const float* v, int32_t reps, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
-                                 const float* coef, int32_t nsched, const int32_t* step, const float* x, float* out, void* stream) {
-    if (!v || !coef || !step || !x || !out || (reps != 1 && reps != 2) || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) ||
-        nsched < 1)
+        !index_source_ok(index, step) || index >= nsched)
         return SEER_EINVAL;
     return launch_per_element(v_to_eps_kernel, reps * elements(b, C, (int64_t)F_total - cond_f, HW), {v, coef, step, x, out}, stream, v,
-                              reps, b, C, F_total, cond_f, HW, coef, nsched, 0, step, x, out);
+                              reps, b, C, F_total, cond_f, HW, coef, nsched, step ? 0 : index, step, x, out);
 }
 
 // state and x_prov go together (NULL both: every slot is read as phase 0); slots 1..4 as in the slot updates' widest form

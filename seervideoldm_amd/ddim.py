@@ -12,7 +12,7 @@ The reference draws `torch.randn(x.shape)` every step even when sigma == 0 (ddim
 multi-sample run consumes the device RNG stream identically.
 
 `sample(..., seed=)` (an int, or one int per batch row) replaces every draw by a counter-based generator inside the kernels (DESIGN.md,
-"Seeded noise"): the start code is seer_philox_normal of the row's seed, the noise of a step is drawn by seer_cfg_ddim_step_rng from
+"Seeded noise"): the start code is seer_philox_normal of the row's seed, the noise of a step is drawn by seer_cfg_ddim_step from
 (seed, schedule index, element).  Nothing comes from torch's generator, the captured step is taken for eta > 0 too, and a row's
 noise does not depend on the batch it is in.
 
@@ -27,7 +27,7 @@ counter runs upward to a limit word in device memory, DESIGN.md "Editing"), so t
 
 `DDIMSampler(device, prediction_type="v_prediction")` samples a model fine-tuned on the velocity target (train.py:373-374): the UNet's
 output is then v = sqrt(a) eps - sqrt(1 - a) x0, and ONE more elementwise kernel (seer_v_to_eps; in the captured step one more node,
-seer_v_to_eps_dev) turns it into eps = sqrt(a) v + sqrt(1 - a) x_t in front of the step's last kernel, with the coefficient row that
+seer_v_to_eps) turns it into eps = sqrt(a) v + sqrt(1 - a) x_t in front of the step's last kernel, with the coefficient row that
 kernel reads.  Everything behind it -- CFG, eta > 0, seeds, mask / x0, decode, stochastic_encode -- acts on eps or on latents and is
 unchanged.  `encode` is refused for such a model (see there).  With the default "epsilon" nothing new is launched or allocated.
 """
@@ -406,11 +406,11 @@ class DDIMSampler(object):
 
     # ---- the captured step -----------------------------------------------------------------------------------------
     def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1., known=None):
-        """One p_sample_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_step_dev):
+        """One p_sample_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_step):
         no torch kernel between two UNet evaluations except the reference's per-step RNG draw, no host-written scalars -- the
         schedule index lives in device memory and the captured step counts it down itself.  Returns None when this step cannot
         take the path (sharded model, capture refused): the caller then runs the launches one by one.  With `seeds` the last kernel
-        is seer_cfg_ddim_step_rng_dev and the step draws nothing, at any eta.  With `known` (seeded only) seer_known_blend is the
+        is the same entry point given seeds and the step draws nothing, at any eta.  With `known` (seeded only) seer_known_blend is the
         step's first node, over static copies of the mask and the given latents."""
         kind = "step" if seeds is None else "step-rng" if known is None else "step-mask"
         G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, kind, None if seeds is None else float(temperature))
@@ -425,7 +425,7 @@ class DDIMSampler(object):
         return self._replay_step(G, x, index, draw=seeds is None)
 
     def _invert_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, limit):
-        """One p_invert_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_invert_step_dev).
+        """One p_invert_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_invert_step).
         The captured step counts its index UPWARD and stops writing at the limit word of its static buffers; at the start of a chain
         the host writes those two words, step[0] and limit[0], and nothing after.  None when the step cannot be captured."""
         G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "invert")

@@ -21,7 +21,7 @@ DDIMSampler.make_schedule's, over the 'uniform' stride or -- discretize="logsnr"
 
 Kernels: CFG combine + update are one fused HIP kernel (seer_cfg_dpm_step; include/seer_hip.h) that reads six host-computed words per
 schedule entry and evaluates no exp or log.  With `unet.use_graph` on an unsharded SeerUNet EVERY step, the first included, is one
-hipGraph replay -- seer_ddim_step_begin, the UNet, seer_cfg_dpm_step_dev -- captured by DDIMSampler's machinery under the kind "dpm";
+hipGraph replay -- seer_ddim_step_begin, the UNet, seer_cfg_dpm_step -- captured by DDIMSampler's machinery under the kind "dpm";
 the history is the step's own pred_x0 buffer, and the kernel picks its order from words in device memory, so a chain of replays needs
 no host-written scalar after its first step.
 
@@ -210,7 +210,7 @@ class DPMSolverSampler(DDIMSampler):
         return self._replay_step(G, x, index)
 
 
-# ---- the captured step: DDIMSampler's, with the DPM table and four state words, and seer_cfg_dpm_step_dev as its last kernel ---------
+# ---- the captured step: DDIMSampler's, with the DPM table and four state words, and seer_cfg_dpm_step as its last kernel -------------
 def _dpm_buffers(x):
     """the table is made by the step's first run (the warm-up, outside the capture), where G["coef"], whose row count it shares, exists"""
     return dict(dpm_coef=None, dpm_state=torch.zeros((4,), device=x.device, dtype=torch.int32), dpm_words=None)

@@ -11,7 +11,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import AttnDesc, GemmDesc, check
+from ._lib import SEER_INDEX_FROM_STEP, AttnDesc, GemmDesc, check
 
 bf16 = torch.bfloat16
 
@@ -995,14 +995,21 @@ def _req_pred(pred_x0: Optional[torch.Tensor], x: torch.Tensor) -> None:
         assert pred_x0.is_contiguous() and pred_x0.shape == x.shape
 
 
+def _cfg_ddim(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, cfg, scale, cond_f, x_prev, pred_x0, *,
+              index=SEER_INDEX_FROM_STEP, step=None, noise=None, seeds=None, temperature=0.) -> None:
+    """seer_cfg_ddim_step for cfg_ddim_step and its _dev, _rng, _rng_dev forms: index from the host or `step`, noise or `seeds`"""
+    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
+    check(_lib.load().seer_cfg_ddim_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), _p(step),
+                                         _p(x), _p(noise), _p(seeds), float(temperature), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_cfg_ddim_step")
+
+
 def cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *, cfg: bool, scale: float,
                   cond_f: int, noise: Optional[torch.Tensor] = None, want_pred_x0=True):
     """eps [2b or b, C, F_total, h, w] fp32 ; x [b, C, F_pred, h, w] fp32 -> (x_prev, pred_x0)."""
-    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f)
     x_prev = torch.empty_like(x)
     pred = torch.empty_like(x) if want_pred_x0 else None
-    check(_lib.load().seer_cfg_ddim_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), index,
-                                         _p(x), _p(noise), _p(x_prev), _p(pred), _stream()), "seer_cfg_ddim_step")
+    _cfg_ddim(eps, x, coef, cfg, scale, cond_f, x_prev, pred, index=index, noise=noise)
     return x_prev, pred
 
 
@@ -1019,9 +1026,7 @@ def ddim_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: to
 def cfg_ddim_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *, cfg: bool, scale: float,
                       cond_f: int, x_prev: torch.Tensor, pred_x0: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None):
     """last kernel of a captured sampler step: cfg_ddim_step with index = step[1], then step[0] = index - 1; x_prev may be x"""
-    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
-    check(_lib.load().seer_cfg_ddim_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step), _p(x),
-                                             _p(noise), _p(x_prev), _p(pred_x0), _stream()), "seer_cfg_ddim_step_dev")
+    _cfg_ddim(eps, x, coef, cfg, scale, cond_f, x_prev, pred_x0, step=step, noise=noise)
 
 
 def cfg_ddim_invert_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *, cfg: bool, scale: float,
@@ -1035,8 +1040,8 @@ def cfg_ddim_invert_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor,
     if not 0 <= int(index) < coef.shape[0]:
         raise ValueError(f"index {index}: the table has {coef.shape[0]} rows")
     pred = torch.empty_like(x) if want_pred_x0 else None
-    check(_lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), _p(x),
-                                                _p(x_next), _p(pred), _stream()), "seer_cfg_ddim_invert_step")
+    check(_lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), None,
+                                                None, _p(x), _p(x_next), _p(pred), _stream()), "seer_cfg_ddim_invert_step")
     return x_next, pred
 
 
@@ -1048,9 +1053,9 @@ def cfg_ddim_invert_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Ten
     _req(limit, torch.int32, "limit")
     assert step.numel() >= 2 and limit.numel() >= 1 and x_next.dtype == torch.float32
     _req_pred(pred_x0, x)
-    check(_lib.load().seer_cfg_ddim_invert_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step),
-                                                    _p(limit), _p(x), _p(x_next), _p(pred_x0), _stream()),
-          "seer_cfg_ddim_invert_step_dev")
+    check(_lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef),
+                                                SEER_INDEX_FROM_STEP, _p(step), _p(limit), _p(x), _p(x_next), _p(pred_x0),
+                                                _stream()), "seer_cfg_ddim_invert_step")
 
 
 def slot_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: torch.Tensor, step: torch.Tensor, reps: int,
@@ -1059,8 +1064,8 @@ def slot_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, t_table: to
     and a counter pair per slot; row rep * slots + s of sample / t_out is slot s (include/seer_hip.h, seer_slot_step_begin)"""
     f1 = _req_begin(x0_emb, x, t_table, step, reps, sample, t_out, per_slot=True)
     slots, Cc, Fp, h, w = x.shape
-    check(_lib.load().seer_slot_step_begin(_p(x0_emb), _p(x), slots, reps, Cc, f1, Fp, h * w, _p(t_table), t_table.shape[1],
-                                           _p(step), _p(sample), _p(t_out), _stream()), "seer_slot_step_begin")
+    check(_lib.load().seer_slot_step_begin(_p(x0_emb), _p(x), None, slots, reps, Cc, f1, Fp, h * w, _p(t_table), t_table.shape[1],
+                                           _p(step), None, _p(sample), _p(t_out), _stream()), "seer_slot_step_begin")
 
 
 def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *,
@@ -1072,7 +1077,7 @@ def slot_cfg_ddim_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, 
     _req_slot_tables(slots, coef, step, scale)
     _req_pred(pred_x0, x)
     check(_lib.load().seer_slot_cfg_ddim_step(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
-                                              _p(x), _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
+                                              _p(x), None, None, _p(x_prev), _p(pred_x0), _stream()), "seer_slot_cfg_ddim_step")
 
 
 # ---- seeded noise (include/seer_hip.h, "seeded noise"): Philox4x32-10 inside the kernels ------------------------------------------
@@ -1121,12 +1126,10 @@ def cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, in
     sigma * (temperature * normal e of (seeds[bi], stream 1, index)).  x_prev may be x.  -> (x_prev, pred_x0)"""
     if x_prev is None:
         x_prev = torch.empty_like(x)
-    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, x_prev=x_prev)
     assert x_prev.dtype == torch.float32
-    _req_seeds(seeds, b)
+    _req_seeds(seeds, x.shape[0])
     pred = torch.empty_like(x) if want_pred_x0 else None
-    check(_lib.load().seer_cfg_ddim_step_rng(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), int(index), _p(x),
-                                             _p(seeds), float(temperature), _p(x_prev), _p(pred), _stream()), "seer_cfg_ddim_step_rng")
+    _cfg_ddim(eps, x, coef, cfg, scale, cond_f, x_prev, pred, index=index, seeds=seeds, temperature=temperature)
     return x_prev, pred
 
 
@@ -1134,28 +1137,25 @@ def cfg_ddim_step_rng_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor
                           cfg: bool, scale: float, cond_f: int, temperature: float, x_prev: torch.Tensor,
                           pred_x0: Optional[torch.Tensor]) -> None:
     """last kernel of a captured seeded step: cfg_ddim_step_rng with index = step[1], then step[0] = index - 1; x_prev may be x"""
-    b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
     assert step.numel() >= 2
-    _req_seeds(seeds, b)
-    check(_lib.load().seer_cfg_ddim_step_rng_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(coef), _p(step), _p(x),
-                                                 _p(seeds), float(temperature), _p(x_prev), _p(pred_x0), _stream()),
-          "seer_cfg_ddim_step_rng_dev")
+    _req_seeds(seeds, x.shape[0])
+    _cfg_ddim(eps, x, coef, cfg, scale, cond_f, x_prev, pred_x0, step=step, seeds=seeds, temperature=temperature)
 
 
 def slot_cfg_ddim_step_rng(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
                            seeds: torch.Tensor, temperature: torch.Tensor, *, cond_f: int, x_prev: torch.Tensor,
                            pred_x0: Optional[torch.Tensor]) -> None:
     """slot_cfg_ddim_step with seeded noise: seeds int32 [slots, 2] and temperature fp32 [slots] in device memory; a slot whose coef
-    row has sigma == 0 runs the deterministic update (include/seer_hip.h, seer_slot_cfg_ddim_step_rng)"""
+    row has sigma == 0 runs the deterministic update (include/seer_hip.h, seer_slot_cfg_ddim_step)"""
     slots, Cc, Ft, HW = _req_update(eps, x, coef, cfg=True, cond_f=cond_f, step=step, x_prev=x_prev)
     _req_slot_tables(slots, coef, step, scale)
     _req(temperature, torch.float32, "temperature")
     assert temperature.is_contiguous() and temperature.numel() == slots
     _req_seeds(seeds, slots)
     _req_pred(pred_x0, x)
-    check(_lib.load().seer_slot_cfg_ddim_step_rng(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
-                                                  _p(x), _p(seeds), _p(temperature), _p(x_prev), _p(pred_x0), _stream()),
-          "seer_slot_cfg_ddim_step_rng")
+    check(_lib.load().seer_slot_cfg_ddim_step(_p(eps), slots, Cc, Ft, cond_f, HW, _p(scale), _p(coef), coef.shape[1], _p(step),
+                                              _p(x), _p(seeds), _p(temperature), _p(x_prev), _p(pred_x0), _stream()),
+          "seer_slot_cfg_ddim_step")
 
 
 # ---- given latents (include/seer_hip.h, "given latents"): masked sampling and stochastic_encode ------------------------------------
@@ -1246,13 +1246,13 @@ def slot_plms_step_begin(x0_emb: Optional[torch.Tensor], x: torch.Tensor, x_prov
                          step: torch.Tensor, state: torch.Tensor, reps: int, sample: torch.Tensor, t_out: torch.Tensor) -> None:
     """slot_step_begin with a sampler per slot: state int32 [slots, 8] holds (phase, valid, newest) of the next step in words 0..2
     and receives them in words 4..6; a slot in phase 2 (the second evaluation of a PLMS clip's first step) takes its rows from
-    x_prov and the next timestep of its table (include/seer_hip.h, seer_slot_plms_step_begin)"""
+    x_prov and the next timestep of its table (include/seer_hip.h, seer_slot_step_begin)"""
     f1 = _req_begin(x0_emb, x, t_table, step, reps, sample, t_out, per_slot=True)
     slots, Cc, Fp, h, w = x.shape
     _req_slot_plms(x, state, x_prov)
-    check(_lib.load().seer_slot_plms_step_begin(_p(x0_emb), _p(x), _p(x_prov), slots, reps, Cc, f1, Fp, h * w, _p(t_table),
-                                                t_table.shape[1], _p(step), _p(state), _p(sample), _p(t_out), _stream()),
-          "seer_slot_plms_step_begin")
+    check(_lib.load().seer_slot_step_begin(_p(x0_emb), _p(x), _p(x_prov), slots, reps, Cc, f1, Fp, h * w, _p(t_table),
+                                           t_table.shape[1], _p(step), _p(state), _p(sample), _p(t_out), _stream()),
+          "seer_slot_step_begin")
 
 
 def slot_cfg_plms_step(eps: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor,
@@ -1343,7 +1343,7 @@ def cfg_dpm_step(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: 
             _req(tt, torch.float32, name)
             assert tt.is_contiguous() and tt.shape == x.shape
     check(_lib.load().seer_cfg_dpm_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(x), _p(coef), nsched, int(index),
-                                        order, _p(d_prev), _p(x_prev), _p(pred), _stream()), "seer_cfg_dpm_step")
+                                        order, None, None, _p(d_prev), _p(x_prev), _p(pred), _stream()), "seer_cfg_dpm_step")
     return x_prev, pred
 
 
@@ -1351,14 +1351,15 @@ def cfg_dpm_step_dev(eps: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, ste
                      scale: float, cond_f: int, x_prev: torch.Tensor, d_hist: torch.Tensor) -> None:
     """last kernel of a captured DPM-Solver++ step: cfg_dpm_step with index = step[1] and the order taken from state int32[4] =
     (history valid by index parity, twice; the sampler's order; final step first order); d_hist holds the step before's pred_x0 and
-    receives this step's; step[0] = index - 1; x_prev may be x (include/seer_hip.h, seer_cfg_dpm_step_dev)"""
+    receives this step's; step[0] = index - 1; x_prev may be x (include/seer_hip.h, seer_cfg_dpm_step)"""
     b, Cc, Ft, HW = _req_update(eps, x, coef, cfg=cfg, cond_f=cond_f, step=step, x_prev=x_prev)
     nsched = _req_dpm_table(coef)
     _req(state, torch.int32, "state"); _req(d_hist, torch.float32, "d_hist")
     assert step.numel() >= 2 and state.is_contiguous() and state.numel() >= 4
     assert d_hist.is_contiguous() and d_hist.shape == x.shape and x_prev.dtype == torch.float32
-    check(_lib.load().seer_cfg_dpm_step_dev(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(x), _p(coef), nsched, _p(step),
-                                            _p(state), _p(x_prev), _p(d_hist), _stream()), "seer_cfg_dpm_step_dev")
+    check(_lib.load().seer_cfg_dpm_step(_p(eps), int(cfg), b, Cc, Ft, cond_f, HW, float(scale), _p(x), _p(coef), nsched,
+                                        SEER_INDEX_FROM_STEP, 0, _p(step), _p(state), None, _p(x_prev), _p(d_hist), _stream()),
+          "seer_cfg_dpm_step")
 
 
 SLOT_DPM_STATE_WORDS = 4    # int32 words of a slot's state in slot_cfg_dpm_step: (valid even, valid odd, sampler, final step first order)
@@ -1420,7 +1421,7 @@ def v_to_eps(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *
     reps, b, Cc, Ft, HW, out = _req_v(v, x, coef, cond_f, out)
     if not 0 <= int(index) < coef.shape[0]:
         raise ValueError(f"index {index}: the table has {coef.shape[0]} rows")
-    check(_lib.load().seer_v_to_eps(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], int(index), _p(x), _p(out),
+    check(_lib.load().seer_v_to_eps(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], int(index), None, _p(x), _p(out),
                                     _stream()), "seer_v_to_eps")
     return out
 
@@ -1428,12 +1429,12 @@ def v_to_eps(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, index: int, *
 def v_to_eps_dev(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *, cond_f: int,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """v_to_eps inside a captured step, between ddim_step_begin and the update: index = step[1], which is only read; an index
-    outside the table writes nothing (seer_v_to_eps_dev)"""
+    outside the table writes nothing (seer_v_to_eps, device form)"""
     reps, b, Cc, Ft, HW, out = _req_v(v, x, coef, cond_f, out)
     _req(step, torch.int32, "step")
     assert step.numel() >= 2 and coef.dim() == 2
-    check(_lib.load().seer_v_to_eps_dev(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], _p(step), _p(x), _p(out),
-                                        _stream()), "seer_v_to_eps_dev")
+    check(_lib.load().seer_v_to_eps(_p(v), reps, b, Cc, Ft, cond_f, HW, _p(coef), coef.shape[0], SEER_INDEX_FROM_STEP, _p(step),
+                                    _p(x), _p(out), _stream()), "seer_v_to_eps")
     return out
 
 

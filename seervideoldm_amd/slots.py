@@ -6,7 +6,7 @@ the scale is frozen into the captured graph, and a batch starts and ends togethe
 
     seer_slot_step_begin  ->  the UNet over [uc rows | c rows] of all slots  ->  seer_slot_cfg_ddim_step
 
-With `plms=True` the sampler is chosen per request: the step is seer_slot_plms_step_begin -> the UNet -> seer_slot_cfg_plms_step, and
+With `plms=True` the sampler is chosen per request: the step is seer_slot_step_begin -> the UNet -> seer_slot_cfg_plms_step, and
 every slot also has a phase word, a 3-entry ring of earlier eps and a provisional latent in device memory.  A DDIM clip (phase 0)
 runs as above.  A PLMS clip of n schedule entries occupies its slot for n + 1 steps: its first step evaluates twice -- phase 1 at
 (x, t) writes the provisional latent and keeps e, phase 2 evaluates at (x_prov, t_next) and applies the mean of the two to x --
@@ -25,8 +25,8 @@ and combines it with scale 1: not the same bits.  Without the invariant mode a s
 kernels, results within the layout tolerance.  The captured step and the launch-by-launch step give the same bits in either mode.
 The reference's per-step RNG draw (ddim_video.py:234) has no counterpart here: nothing consumes the device RNG stream.
 
-With `stochastic=True` a request may carry eta > 0, a seed and a temperature: the step's last kernel is seer_slot_cfg_ddim_step_rng,
-which draws a slot's noise itself from (the slot's seed, its schedule index, the element) -- a counter-based generator (DESIGN.md,
+With `stochastic=True` a request may carry eta > 0, a seed and a temperature: the step's last kernel is given the slots' seeds
+and draws a slot's noise itself from (the slot's seed, its schedule index, the element) -- a counter-based generator (DESIGN.md,
 "Seeded noise"), so nothing is drawn between launches, nothing is frozen into the graph and the noise of a clip does not depend on
 its slot or its neighbours.  Each slot also has a seed pair and a temperature in device memory, and its coefficient rows carry the
 sigma of its own eta.  The promise above then holds for a seeded clip against DDIMSampler.sample(..., eta=, seed=, x_T=None).

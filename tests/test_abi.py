@@ -40,11 +40,14 @@ def test_binding_matches_header(lib_path):
 
 
 def test_one_entry_point_per_kernel(lib_path):
-    """no `_dt` / `_pre` twin is declared, and the library exports no seer_* symbol beyond the header's: the forwarders of
-    ABI <= 25 are gone, not merely undeclared"""
+    """no `_dt` / `_pre` twin is declared, none of the sampler step's `_dev` / `_rng` twins of ABI <= 26 either, and the library
+    exports no seer_* symbol beyond the header's: the forwarders of ABI <= 25 are gone, not merely undeclared"""
     import subprocess
     names = _declared()
     assert not [n for n in names if n.endswith(("_dt", "_pre"))]
+    assert not set(names) & {"seer_cfg_ddim_step_dev", "seer_cfg_ddim_step_rng", "seer_cfg_ddim_step_rng_dev",
+                             "seer_cfg_ddim_invert_step_dev", "seer_cfg_dpm_step_dev", "seer_v_to_eps_dev", "seer_slot_plms_step_begin",
+                             "seer_slot_cfg_ddim_step_rng"}
     out = subprocess.run(["nm", "-D", "--defined-only", str(lib_path)], capture_output=True, text=True, check=True).stdout
     exported = sorted({l.split()[-1] for l in out.splitlines() if l.split() and l.split()[-1].startswith("seer_")})
     assert exported == names

@@ -285,8 +285,8 @@ def test_surface():
     from seervideoldm_amd.ddim import STEP_KINDS
     import seervideoldm_amd
     assert "DPMSolverSampler" in seervideoldm_amd.__all__
-    assert {"seer_cfg_dpm_step", "seer_cfg_dpm_step_dev"} <= set(_lib.SIGNATURES)
-    assert _lib.ABI_VERSION == 26                        # declarations only: no struct changed
+    assert "seer_cfg_dpm_step" in _lib.SIGNATURES
+    assert _lib.ABI_VERSION == 27                        # declarations only: no struct changed
     assert callable(ops.cfg_dpm_step) and callable(ops.cfg_dpm_step_dev) and ops.DPM_ROW_WORDS == 6
     assert "dpm" in STEP_KINDS
     ours, theirs = inspect.signature(DPMSolverSampler.sample).parameters, inspect.signature(DDIMSampler.sample).parameters
@@ -374,22 +374,25 @@ def test_ddim_sample_and_generate_clips_drive_it(monkeypatch):
 
 # ---- 7. the entry points' refusals ----------------------------------------------------------------------------------------------------
 def refusal_cases(P, W):
-    """(entry point, arguments without the stream, what is wrong) for every refusal of the two entry points.  P stands for every fp32
+    """(entry point, arguments without the stream, what is wrong) for every refusal of the entry point's two forms.  P stands for every fp32
     buffer and W for the two int32 ones; both are 4-byte aligned and non-NULL (tests/test_gpu_dpm.py passes real ones)"""
-    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=96, scale=7.5, x=P, coef=P, nsched=10, index=3, order=2, d_prev=P,
-                x_prev=P, pred_x0=P)
+    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=96, scale=7.5, x=P, coef=P, nsched=10, index=3, order=2, step=None, state=None,
+                d_prev=P, x_prev=P, pred_x0=P)
     for kw in (dict(eps=None), dict(x=None), dict(coef=None), dict(x_prev=None), dict(d_prev=None), dict(b=0), dict(b=-1), dict(C=0),
                dict(HW=0), dict(HW=-4), dict(cond_f=-1), dict(cond_f=5), dict(cond_f=6), dict(F_total=0, cond_f=0), dict(nsched=0),
                dict(index=-1), dict(index=10), dict(index=11), dict(order=0), dict(order=3), dict(order=-1), dict(eps=P + 2),
                dict(x=P + 2), dict(coef=P + 1), dict(d_prev=P + 2), dict(x_prev=P + 3), dict(pred_x0=P + 2),
-               dict(b=1 << 16, C=1 << 16, F_total=1 << 8, cond_f=0, HW=1)):                  # 2^40 elements: a grid beyond one dimension
+               dict(b=1 << 16, C=1 << 16, F_total=1 << 8, cond_f=0, HW=1),                   # 2^40 elements: a grid beyond one dimension
+               dict(state=W), dict(step=W)):                                                 # a half-set device form
         yield "seer_cfg_dpm_step", tuple({**good, **kw}.values()), kw
-    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=96, scale=7.5, x=P, coef=P, nsched=10, step=W, state=W, x_prev=P,
-                d_hist=P)
-    for kw in (dict(eps=None), dict(x=None), dict(coef=None), dict(step=None), dict(state=None), dict(x_prev=None), dict(d_hist=None),
+    # the device form: pred_x0 is the history (d_hist of ABI <= 26)
+    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=96, scale=7.5, x=P, coef=P, nsched=10, index=-1, order=0, step=W, state=W,
+                d_prev=None, x_prev=P, pred_x0=P)
+    for kw in (dict(eps=None), dict(x=None), dict(coef=None), dict(step=None), dict(state=None), dict(x_prev=None), dict(pred_x0=None),
                dict(b=0), dict(C=0), dict(HW=0), dict(cond_f=-1), dict(cond_f=5), dict(nsched=0), dict(nsched=-3), dict(eps=P + 2),
-               dict(x=P + 1), dict(coef=P + 2), dict(step=W + 2), dict(state=W + 1), dict(x_prev=P + 2), dict(d_hist=P + 3)):
-        yield "seer_cfg_dpm_step_dev", tuple({**good, **kw}.values()), kw
+               dict(x=P + 1), dict(coef=P + 2), dict(step=W + 2), dict(state=W + 1), dict(x_prev=P + 2), dict(pred_x0=P + 3),
+               dict(index=3), dict(d_prev=P)):
+        yield "seer_cfg_dpm_step", tuple({**good, **kw}.values()), kw
 
 
 def test_kernel_entry_points_refuse_bad_arguments_before_any_launch():

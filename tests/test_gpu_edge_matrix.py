@@ -1,6 +1,6 @@
 """csrc/elementwise.hip -- rotary, timestep embedding, seer_linear_smallm, seer_conv_in / seer_conv_out, cast and layout,
 seer_conv1x1_nchw_f32, seer_clamp01 and seer_gaussian_sample -- and the DDIM step boundary of csrc/sampler_step.hip
-(seer_ddim_step_begin, seer_cfg_ddim_step, seer_cfg_ddim_step_dev), tested exactly, per owner and at their edges: the second half of part 5 of the series (the first is
+(seer_ddim_step_begin, seer_cfg_ddim_step in its host and device forms), tested exactly, per owner and at their edges: the second half of part 5 of the series (the first is
 test_gpu_norm_matrix.py).  The two PLMS entry points are left to test_gpu_plms.py, which holds them to 1e-6 per order.
 
 0. Pure data movement bit for bit into guarded arenas: layout conversion, cast (ties, +-0, +-inf, NaN, fp16 overflow, subnormals)
@@ -231,9 +231,9 @@ def _cfg_step(eps, x, noise, coef, index, cfg, scale, case, pred=True, dev_form=
     if dev_form:
         step = torch.tensor([77, index], dtype=i32, device=device)
         xp[:n] = x.reshape(-1)                                            # x_prev aliases x
-        rc = _L().seer_cfg_ddim_step_dev(_p(eps), int(cfg), b, C, Ft, cond_f, HW, scale, _p(coef), _p(step), _p(xp), _p(noise), _p(xp), _p(px), _s())
+        rc = _L().seer_cfg_ddim_step(_p(eps), int(cfg), b, C, Ft, cond_f, HW, scale, _p(coef), -1, _p(step), _p(xp), _p(noise), None, 0.0, _p(xp), _p(px), _s())
     else:
-        rc = _L().seer_cfg_ddim_step(_p(eps), int(cfg), b, C, Ft, cond_f, HW, scale, _p(coef), index, _p(x), _p(noise), _p(xp), _p(px), _s())
+        rc = _L().seer_cfg_ddim_step(_p(eps), int(cfg), b, C, Ft, cond_f, HW, scale, _p(coef), index, None, _p(x), _p(noise), None, 0.0, _p(xp), _p(px), _s())
     assert rc == 0, rc
     torch.cuda.synchronize()
     _guard_holds(xp, n, "x_prev")
@@ -418,18 +418,18 @@ def test_edge_refusals(device):
         ("conv_out y NULL", L.seer_conv_out, (W, 1, 8, 1, 3, 3, X, None, 4, None, 0), EINVAL),
         ("conv_out W = 0", L.seer_conv_out, (W, 1, 8, 1, 3, 0, X, None, 4, Y, 0), EINVAL),
         ("conv_out weights above 160 KiB of LDS", L.seer_conv_out, (W, 1, 1280, 1, 3, 3, X, None, 4, Y, 0), EINVAL),
-        # seer_cfg_ddim_step(eps, cfg, b, C, F_total, cond_f, HW, scale, coef, index, x, noise, x_prev, pred_x0)
-        ("cfg_ddim F_total == cond_f", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 2, 8, 7.5, X, 0, X, None, Y, None), EINVAL),
-        ("cfg_ddim cond_f < 0", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, -1, 8, 7.5, X, 0, X, None, Y, None), EINVAL),
-        ("cfg_ddim index < 0", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, X, -1, X, None, Y, None), EINVAL),
-        ("cfg_ddim b = 0", L.seer_cfg_ddim_step, (X, 1, 0, 4, 2, 1, 8, 7.5, X, 0, X, None, Y, None), EINVAL),
-        ("cfg_ddim eps NULL", L.seer_cfg_ddim_step, (None, 1, 1, 4, 2, 1, 8, 7.5, X, 0, X, None, Y, None), EINVAL),
-        ("cfg_ddim coef NULL", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, None, 0, X, None, Y, None), EINVAL),
-        ("cfg_ddim x_prev NULL", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, X, 0, X, None, None, None), EINVAL),
-        # seer_cfg_ddim_step_dev(eps, cfg, b, C, F_total, cond_f, HW, scale, coef, step, x, noise, x_prev, pred_x0)
-        ("cfg_ddim_dev F_total == cond_f", L.seer_cfg_ddim_step_dev, (X, 1, 1, 4, 2, 2, 8, 7.5, X, I, X, None, Y, None), EINVAL),
-        ("cfg_ddim_dev step NULL", L.seer_cfg_ddim_step_dev, (X, 1, 1, 4, 2, 1, 8, 7.5, X, None, X, None, Y, None), EINVAL),
-        ("cfg_ddim_dev HW = 0", L.seer_cfg_ddim_step_dev, (X, 1, 1, 4, 2, 1, 0, 7.5, X, I, X, None, Y, None), EINVAL),
+        # seer_cfg_ddim_step(eps, cfg, b, C, F_total, cond_f, HW, scale, coef, index, step, x, noise, seeds, temperature, x_prev, pred_x0), host form
+        ("cfg_ddim F_total == cond_f", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 2, 8, 7.5, X, 0, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim cond_f < 0", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, -1, 8, 7.5, X, 0, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim index < 0", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, X, -1, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim b = 0", L.seer_cfg_ddim_step, (X, 1, 0, 4, 2, 1, 8, 7.5, X, 0, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim eps NULL", L.seer_cfg_ddim_step, (None, 1, 1, 4, 2, 1, 8, 7.5, X, 0, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim coef NULL", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, None, 0, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim x_prev NULL", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, X, 0, None, X, None, None, 0.0, None, None), EINVAL),
+        # the same, device form: index = -1 and step
+        ("cfg_ddim_dev F_total == cond_f", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 2, 8, 7.5, X, -1, I, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim_dev step NULL", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 8, 7.5, X, -1, None, X, None, None, 0.0, Y, None), EINVAL),
+        ("cfg_ddim_dev HW = 0", L.seer_cfg_ddim_step, (X, 1, 1, 4, 2, 1, 0, 7.5, X, -1, I, X, None, None, 0.0, Y, None), EINVAL),
         # seer_ddim_step_begin(x0_emb, x, b, reps, C, f1, F_pred, HW, t_table, step, sample, t_out)
         ("step_begin f1 > 0 without x0_emb", L.seer_ddim_step_begin, (None, X, 1, 2, 4, 1, 2, 8, I, I, Y, I), EINVAL),
         ("step_begin reps = 0", L.seer_ddim_step_begin, (X, X, 1, 0, 4, 1, 2, 8, I, I, Y, I), EINVAL),

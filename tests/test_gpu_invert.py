@@ -79,7 +79,7 @@ def _invert(eps, x, coef, index, cfg, case, pred=True, alias=False):
     n = x.numel()
     xn = _Arena(n, x.device, fill=x if alias else None)
     px = _Arena(n, x.device) if pred else None
-    rc = _lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, C, Ft, cond_f, HW, SCALE, _p(coef), index,
+    rc = _lib.load().seer_cfg_ddim_invert_step(_p(eps), int(cfg), b, C, Ft, cond_f, HW, SCALE, _p(coef), index, None, None,
                                                _p(xn.out if alias else x), _p(xn.out), _p(px.out) if pred else None, _s())
     assert rc == 0, rc
     torch.cuda.synchronize()
@@ -166,8 +166,8 @@ def test_the_ddim_step_takes_the_inverted_latent_back(device, cfg):
         assert row[2] == 0.0
         xn, _ = _invert(e32, x32, coef, index, cfg, case)
         back = _Arena(x.numel(), device)
-        rc = _lib.load().seer_cfg_ddim_step(_p(e32), int(cfg), b, 4, cond_f + 3, cond_f, 50, SCALE, _p(coef), index, _p(xn.contiguous()),
-                                            None, _p(back.out), None, _s())
+        rc = _lib.load().seer_cfg_ddim_step(_p(e32), int(cfg), b, 4, cond_f + 3, cond_f, 50, SCALE, _p(coef), index, None,
+                                            _p(xn.contiguous()), None, None, 0.0, _p(back.out), None, _s())
         assert rc == 0
         torch.cuda.synchronize()
         back.guards_hold("x_prev")

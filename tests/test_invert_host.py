@@ -147,8 +147,8 @@ def test_refusals_and_rng():
 def test_exports():
     from seervideoldm_amd import _lib, ops
     from seervideoldm_amd.ddim import STEP_KINDS
-    assert {"seer_cfg_ddim_invert_step", "seer_cfg_ddim_invert_step_dev"} <= set(_lib.SIGNATURES)
-    assert _lib.ABI_VERSION == 26                        # declarations only: no struct changed
+    assert "seer_cfg_ddim_invert_step" in _lib.SIGNATURES
+    assert _lib.ABI_VERSION == 27                        # declarations only: no struct changed
     for name in ("cfg_ddim_invert_step", "cfg_ddim_invert_step_dev"):
         assert callable(getattr(ops, name)), name
     assert callable(R.cfg_ddim_invert_step) and callable(R.cfg_ddim_step) and callable(R.q_sample)
@@ -267,19 +267,22 @@ def test_edit_clips_invert(monkeypatch):
 
 # ---- 6. the entry points' refusals ------------------------------------------------------------------------------------------------
 def refusal_cases(P, W):
-    """(entry point, arguments without the stream, what is wrong) for every refusal of the two entry points.  P stands for every fp32
+    """(entry point, arguments without the stream, what is wrong) for every refusal of the entry point's two forms.  P stands for every fp32
     buffer and W for the two int32 ones; both are 4-byte aligned and non-NULL (tests/test_gpu_invert.py passes real ones)"""
-    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=50, scale=7.5, coef=P, index=0, x=P, x_next=P, pred_x0=P)
+    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=50, scale=7.5, coef=P, index=0, step=None, limit=None, x=P, x_next=P,
+                pred_x0=P)
     for kw in (dict(eps=None), dict(coef=None), dict(x=None), dict(x_next=None), dict(b=0), dict(b=-1), dict(C=0), dict(HW=0), dict(HW=-4),
                dict(cond_f=-1), dict(cond_f=5), dict(cond_f=6), dict(F_total=0, cond_f=0), dict(index=-1), dict(eps=P + 2),
                dict(coef=P + 1), dict(x=P + 2), dict(x_next=P + 3), dict(pred_x0=P + 2),
-               dict(b=1 << 16, C=1 << 16, F_total=1 << 8, cond_f=0, HW=1)):                  # 2^40 elements: a grid beyond one dimension
+               dict(b=1 << 16, C=1 << 16, F_total=1 << 8, cond_f=0, HW=1),                   # 2^40 elements: a grid beyond one dimension
+               dict(step=W), dict(limit=W)):                                                 # a half-set device form
         yield "seer_cfg_ddim_invert_step", tuple({**good, **kw}.values()), kw
-    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=50, scale=7.5, coef=P, step=W, limit=W, x=P, x_next=P, pred_x0=P)
+    good = dict(eps=P, cfg=1, b=2, C=4, F_total=5, cond_f=2, HW=50, scale=7.5, coef=P, index=-1, step=W, limit=W, x=P, x_next=P,
+                pred_x0=P)
     for kw in (dict(eps=None), dict(coef=None), dict(step=None), dict(limit=None), dict(x=None), dict(x_next=None), dict(b=0), dict(C=0),
                dict(HW=0), dict(cond_f=-1), dict(cond_f=5), dict(eps=P + 2), dict(coef=P + 2), dict(step=W + 2), dict(limit=W + 1),
-               dict(x=P + 2), dict(x_next=P + 2), dict(pred_x0=P + 1)):
-        yield "seer_cfg_ddim_invert_step_dev", tuple({**good, **kw}.values()), kw
+               dict(x=P + 2), dict(x_next=P + 2), dict(pred_x0=P + 1), dict(index=0)):
+        yield "seer_cfg_ddim_invert_step", tuple({**good, **kw}.values()), kw
 
 
 def test_kernel_entry_points_refuse_bad_arguments_before_any_launch():

@@ -248,7 +248,7 @@ def test_generate_queue_refuses_dpmpp_without_its_keyword():
 def test_exports():
     from seervideoldm_amd import _lib, ops
     assert "seer_slot_cfg_dpm_step" in _lib.SIGNATURES and callable(ops.slot_cfg_dpm_step)
-    assert _lib.ABI_VERSION == 26
+    assert _lib.ABI_VERSION == 27
     assert ops.SLOT_DPM_STATE_WORDS == slot_dpm_ref.WORDS == 4 and ops.DPM_ROW_WORDS == slot_dpm_ref.ROW == 6
 
 

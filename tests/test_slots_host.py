@@ -160,17 +160,22 @@ def test_exports():
 
 
 def refusal_cases(P):
-    """(entry point, arguments without the stream, what is wrong) for every refusal of the two slot entry points; P is a 4-byte
-    aligned non-NULL pointer that stands for every buffer (tests/test_gpu_slots.py passes a real one)"""
-    good = dict(x0_emb=P, x=P, slots=2, reps=2, C=4, f1=1, F_pred=3, HW=64, t_table=P, nsched=8, step=P, sample=P, t_out=P)
+    """(entry point, arguments without the stream, what is wrong) for every refusal of the two slot entry points in their plain modes
+    (no sampler per slot, no seeds); P is a 4-byte aligned non-NULL pointer with at least 128 bytes behind it that stands for every
+    buffer (tests/test_gpu_slots.py passes a real one)"""
+    good = dict(x0_emb=P, x=P, x_prov=None, slots=2, reps=2, C=4, f1=1, F_pred=3, HW=64, t_table=P, nsched=8, step=P, state=None,
+                sample=P, t_out=P)
     for kw in (dict(x=None), dict(t_table=None), dict(step=None), dict(sample=None), dict(t_out=None), dict(x0_emb=None),
                dict(slots=0), dict(nsched=0), dict(reps=0), dict(reps=3), dict(C=0), dict(F_pred=0), dict(HW=0), dict(f1=-1),
-               dict(x=P + 2), dict(t_table=P + 1), dict(t_out=P + 3), dict(step=P + 2), dict(sample=P + 1), dict(x0_emb=P + 2)):
+               dict(x=P + 2), dict(t_table=P + 1), dict(t_out=P + 3), dict(step=P + 2), dict(sample=P + 1), dict(x0_emb=P + 2),
+               dict(x_prov=P + 64), dict(state=P)):                                          # one of the pair without the other
         yield "seer_slot_step_begin", tuple({**good, **kw}.values()), kw
-    good = dict(eps=P, slots=2, C=4, F_total=4, cond_f=1, HW=64, scale=P, coef=P, nsched=8, step=P, x=P, x_prev=P, pred_x0=P)
+    good = dict(eps=P, slots=2, C=4, F_total=4, cond_f=1, HW=64, scale=P, coef=P, nsched=8, step=P, x=P, seeds=None, temperature=None,
+                x_prev=P, pred_x0=P)
     for kw in (dict(eps=None), dict(scale=None), dict(coef=None), dict(step=None), dict(x=None), dict(x_prev=None), dict(slots=0),
                dict(nsched=0), dict(cond_f=4), dict(cond_f=5), dict(cond_f=-1), dict(C=0), dict(HW=0), dict(eps=P + 2),
-               dict(scale=P + 1), dict(coef=P + 2), dict(step=P + 3), dict(x=P + 1), dict(x_prev=P + 2), dict(pred_x0=P + 2)):
+               dict(scale=P + 1), dict(coef=P + 2), dict(step=P + 3), dict(x=P + 1), dict(x_prev=P + 2), dict(pred_x0=P + 2),
+               dict(seeds=P), dict(temperature=P)):                                          # one of the pair without the other
         yield "seer_slot_cfg_ddim_step", tuple({**good, **kw}.values()), kw
 
 

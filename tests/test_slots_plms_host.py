@@ -170,7 +170,7 @@ def test_generate_queue_refuses_plms_without_its_keyword():
 
 def test_exports():
     from seervideoldm_amd import _lib, ops
-    assert {"seer_slot_plms_step_begin", "seer_slot_cfg_plms_step"} <= set(_lib.SIGNATURES)
+    assert {"seer_slot_step_begin", "seer_slot_cfg_plms_step"} <= set(_lib.SIGNATURES)
     assert callable(ops.slot_plms_step_begin) and callable(ops.slot_cfg_plms_step)
     assert ops.SLOT_STATE_WORDS == slot_plms_ref.WORDS == 8
 
@@ -186,7 +186,7 @@ def plms_refusal_cases(P):
                dict(slots=0), dict(nsched=0), dict(reps=0), dict(reps=3), dict(C=0), dict(F_pred=0), dict(HW=0), dict(f1=-1),
                dict(x=P + 2), dict(t_table=P + 1), dict(t_out=P + 3), dict(step=P + 2), dict(sample=P + 1), dict(x0_emb=P + 2),
                dict(x_prov=None), dict(state=None), dict(x_prov=Q + 2), dict(state=P + 1), dict(x_prov=P), dict(x=Q)):
-        yield "seer_slot_plms_step_begin", tuple({**good, **kw}.values()), kw
+        yield "seer_slot_step_begin", tuple({**good, **kw}.values()), kw
     good = dict(eps=P, slots=2, C=4, F_total=4, cond_f=1, HW=64, scale=P, coef=P, nsched=8, step=P, state=P, ring=P, x=P, x_prov=Q,
                 x_prev=P, pred_x0=P)
     for kw in (dict(eps=None), dict(scale=None), dict(coef=None), dict(step=None), dict(x=None), dict(x_prev=None), dict(slots=0),

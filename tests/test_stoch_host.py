@@ -197,7 +197,7 @@ def test_exports():
     import inspect
 
     from seervideoldm_amd import SlotSampler, _lib, ops, pipeline
-    new = {"seer_philox_u32", "seer_philox_normal", "seer_cfg_ddim_step_rng", "seer_cfg_ddim_step_rng_dev", "seer_slot_cfg_ddim_step_rng"}
+    new = {"seer_philox_u32", "seer_philox_normal", "seer_cfg_ddim_step", "seer_slot_cfg_ddim_step"}
     assert new <= set(_lib.SIGNATURES)
     for name in ("philox_u32", "philox_normal", "cfg_ddim_step_rng", "cfg_ddim_step_rng_dev", "slot_cfg_ddim_step_rng", "seed_words"):
         assert callable(getattr(ops, name)), name
@@ -209,8 +209,9 @@ def test_exports():
 
 
 def refusal_cases(P):
-    """(entry point, arguments without the stream, what is wrong) for every refusal of the five entry points; P is a 4-byte aligned
-    non-NULL pointer that stands for every buffer (tests/test_gpu_stoch.py passes a real one)"""
+    """(entry point, arguments without the stream, what is wrong) for every refusal of the two generator entry points and of the
+    seeded modes of seer_cfg_ddim_step (host index, then device index) and seer_slot_cfg_ddim_step; P is a 4-byte aligned non-NULL
+    pointer that stands for every buffer (tests/test_gpu_stoch.py passes a real one)"""
     good = dict(seed=1, stream=1, index=0, first_block=0, n_blocks=4, out=P)
     for kw in (dict(out=None), dict(out=P + 2), dict(n_blocks=0), dict(n_blocks=-1), dict(first_block=1 << 32),
                dict(first_block=(1 << 32) - 2, n_blocks=3)):
@@ -218,21 +219,23 @@ def refusal_cases(P):
     good = dict(seed=1, stream=1, index=0, n=5, out=P)
     for kw in (dict(out=None), dict(out=P + 1), dict(n=0), dict(n=-3), dict(n=1 << 31)):
         yield "seer_philox_normal", tuple({**good, **kw}.values()), kw
-    for fn, idx in (("seer_cfg_ddim_step_rng", dict(index=0)), ("seer_cfg_ddim_step_rng_dev", dict(step=P))):
-        good = dict(eps=P, cfg=1, b=2, C=4, F_total=4, cond_f=1, HW=64, scale=7.5, coef=P, **idx, x=P, seeds=P, temperature=1.0, x_prev=P,
-                    pred_x0=P)
-        bad_idx = dict(index=-1) if "index" in idx else dict(step=None)
-        for kw in (dict(eps=None), dict(coef=None), dict(x=None), dict(seeds=None), dict(x_prev=None), bad_idx, dict(b=0), dict(C=0),
+    for idx in (dict(index=0, step=None), dict(index=-1, step=P)):
+        good = dict(eps=P, cfg=1, b=2, C=4, F_total=4, cond_f=1, HW=64, scale=7.5, coef=P, **idx, x=P, noise=None, seeds=P, temperature=1.0,
+                    x_prev=P, pred_x0=P)
+        # seeds=None left the table: with noise NULL too that call is now the deterministic step.  Neither index source, both at once,
+        # and both noise sources at once are refused
+        bad_idx = (dict(index=-1), dict(step=P)) if idx["step"] is None else (dict(step=None), dict(index=0))
+        for kw in (dict(eps=None), dict(coef=None), dict(x=None), dict(x_prev=None), *bad_idx, dict(noise=P), dict(b=0), dict(C=0),
                    dict(HW=0), dict(cond_f=4), dict(cond_f=5), dict(cond_f=-1), dict(seeds=P + 2), dict(x=P + 1),
                    dict(C=1 << 15, F_total=2, HW=1 << 16), dict(C=1 << 14, F_total=9, cond_f=1, HW=1 << 14)):        # 2^31 and 2^31 elements
-            yield fn, tuple({**good, **kw}.values()), kw
+            yield "seer_cfg_ddim_step", tuple({**good, **kw}.values()), kw
     good = dict(eps=P, slots=2, C=4, F_total=4, cond_f=1, HW=64, scale=P, coef=P, nsched=8, step=P, x=P, seeds=P, temperature=P,
                 x_prev=P, pred_x0=P)
     for kw in (dict(eps=None), dict(scale=None), dict(coef=None), dict(step=None), dict(x=None), dict(seeds=None),
                dict(temperature=None), dict(x_prev=None), dict(slots=0), dict(nsched=0), dict(cond_f=4), dict(cond_f=5),
                dict(cond_f=-1), dict(C=0), dict(HW=0), dict(seeds=P + 2), dict(temperature=P + 1), dict(step=P + 3),
                dict(pred_x0=P + 2), dict(C=1 << 15, F_total=2, HW=1 << 16)):
-        yield "seer_slot_cfg_ddim_step_rng", tuple({**good, **kw}.values()), kw
+        yield "seer_slot_cfg_ddim_step", tuple({**good, **kw}.values()), kw
 
 
 def test_kernel_entry_points_refuse_bad_arguments_before_any_launch():

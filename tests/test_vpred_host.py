@@ -410,8 +410,8 @@ def test_unknown_prediction_type_and_inversion_are_refused():
 def test_surface():
     from seervideoldm_amd import _lib, ops, train_ops
     from seervideoldm_amd.trainer import SeerTrainer
-    assert {"seer_v_to_eps", "seer_v_to_eps_dev", "seer_slot_v_to_eps", "seer_velocity_target"} <= set(_lib.SIGNATURES)
-    assert _lib.ABI_VERSION == 26                        # declarations only: no struct changed
+    assert {"seer_v_to_eps", "seer_slot_v_to_eps", "seer_velocity_target"} <= set(_lib.SIGNATURES)
+    assert _lib.ABI_VERSION == 27                        # declarations only: no struct changed
     assert all(callable(getattr(ops, n)) for n in ("v_to_eps", "v_to_eps_dev", "slot_v_to_eps")) and callable(train_ops.velocity_target)
     assert ops.PREDICTION_TYPES == ("epsilon", "v_prediction")
     for fn in (SlotSampler.__init__, SeerTrainer.__init__, pipeline.generate_queue):
@@ -471,19 +471,20 @@ def test_compat_unknown_prediction_is_the_references_error(compat_env):
 
 # ---- the entry points' refusals ---------------------------------------------------------------------------------------------------------
 def refusal_cases(P, W, T8):
-    """(entry point, arguments without the stream, what is wrong) for every refusal of the four entry points.  P stands for every fp32
+    """(entry point, arguments without the stream, what is wrong) for every refusal of the three entry points (seer_v_to_eps in its two forms).  P stands for every fp32
     buffer, W for the int32 ones and T8 for the int64 timesteps; all aligned and non-NULL (tests/test_gpu_vpred.py passes real ones)"""
-    good = dict(v=P, reps=2, b=2, C=4, F_total=5, cond_f=2, HW=96, coef=P, nsched=10, index=3, x=P, out=P)
+    good = dict(v=P, reps=2, b=2, C=4, F_total=5, cond_f=2, HW=96, coef=P, nsched=10, index=3, step=None, x=P, out=P)
     shape = (dict(b=0), dict(b=-1), dict(C=0), dict(HW=0), dict(HW=-4), dict(cond_f=-1), dict(cond_f=5), dict(cond_f=6),
              dict(F_total=0, cond_f=0), dict(nsched=0), dict(nsched=-3))
     huge = dict(b=1 << 16, C=1 << 16, F_total=1 << 8, cond_f=0, HW=1)                        # 2^40 elements: a grid beyond one dimension
     for kw in (dict(v=None), dict(coef=None), dict(x=None), dict(out=None), dict(reps=0), dict(reps=3), dict(reps=-1), *shape,
-               dict(index=-1), dict(index=10), dict(index=11), dict(v=P + 2), dict(coef=P + 1), dict(x=P + 2), dict(out=P + 3), huge):
+               dict(index=-1), dict(index=10), dict(index=11), dict(v=P + 2), dict(coef=P + 1), dict(x=P + 2), dict(out=P + 3), huge,
+               dict(step=W)):
         yield "seer_v_to_eps", tuple({**good, **kw}.values()), kw
-    good = dict(v=P, reps=2, b=2, C=4, F_total=5, cond_f=2, HW=96, coef=P, nsched=10, step=W, x=P, out=P)
+    good = dict(v=P, reps=2, b=2, C=4, F_total=5, cond_f=2, HW=96, coef=P, nsched=10, index=-1, step=W, x=P, out=P)
     for kw in (dict(v=None), dict(coef=None), dict(step=None), dict(x=None), dict(out=None), dict(reps=0), dict(reps=3), *shape,
-               dict(v=P + 2), dict(coef=P + 1), dict(step=W + 2), dict(x=P + 2), dict(out=P + 3), huge):
-        yield "seer_v_to_eps_dev", tuple({**good, **kw}.values()), kw
+               dict(v=P + 2), dict(coef=P + 1), dict(step=W + 2), dict(x=P + 2), dict(out=P + 3), huge, dict(index=3)):
+        yield "seer_v_to_eps", tuple({**good, **kw}.values()), kw
     good = dict(v=P, slots=2, C=4, F_total=5, cond_f=2, HW=96, coef=P, nsched=10, step=W, state=W, x=P, x_prov=P + 4096, out=P)
     shape = tuple(kw for kw in shape if "b" not in kw)
     for kw in (dict(v=None), dict(coef=None), dict(step=None), dict(x=None), dict(out=None), dict(state=None), dict(x_prov=None),
