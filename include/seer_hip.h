@@ -775,6 +775,49 @@ int seer_slot_v_to_eps(const float* v, int32_t slots, int32_t C, int32_t F_total
                        int32_t nsched, const int32_t* step, const int32_t* state /* NULL: no sampler per slot */, const float* x,
                        const float* x_prov /* NULL with state */, float* out, void* stream);
 
+/* ---- guidance rescale: classifier-free guidance with the std of the conditional branch (Lin et al. 2023, "Common Diffusion Noise
+ * Schedules and Sample Steps are Flawed", section 3.4; diffusers rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale)) --------
+ * Guidance at scale s multiplies the std of the model output by a factor that grows with s.  Per CLIP, over the n = C (F_total - cond_f)
+ * HW elements of its predicted frames (frames >= cond_f; the conditioning frames are never read or written and may hold NaN):
+ *   c_i  the conditional row,      g_i = eu_i + scale * (c_i - eu_i), the fp32 value every update kernel above combines (one device
+ *        function for all of them), so the moments are taken of exactly the numbers that get scaled;
+ *   S1c = sum c, S2c = sum c c, S1g = sum g, S2g = sum g g       in double (every fp32 x fp32 product is exact there);
+ *   q_c = max(n S2c - S1c^2, 0),   q_g = n S2g - S1g^2           (n^2 times the variance: exact on integer data, and the n - 1 of an
+ *                                                                  unbiased std cancels in the ratio);
+ *   m   = (float)(phi * sqrt(q_c / q_g) + (1 - phi))             in double, phi = `rescale` widened from float;
+ *   out = m * g                                                   one fp32 product, written IN PLACE to the clip's uc row AND its c row.
+ * That is rescale_noise_cfg with std over all non-batch dims (agreement in float64: 6e-15).  DEVIATION: where q_g <= 0 (a constant g;
+ * n = 1) or the ratio is not finite, m = 1 and out = g; diffusers divides by the zero std and returns inf or NaN.
+ * Both rows are overwritten because the update kernels are unchanged: they compute eu + scale * (ec - eu) with eu == ec, which is ec
+ * again exactly for finite values (ec - eu = +0, scale * 0 = 0, eu + 0 = eu, with or without FMA contraction).  The node acts on the raw
+ * model output -- for a v-model on v, IN FRONT of seer_v_to_eps, whose conversion is affine with the same x_t for both rows and keeps
+ * them equal.
+ * TWO launches over the same grid (P, clips), P = ceil(n / SEER_RESCALE_TILE), and no atomics, counters or waiting inside a launch:
+ *   moments  block (p, clip) reduces elements [p TILE, min((p + 1) TILE, n)) to the four doubles in a fixed order -- per thread in index
+ *            order, __shfl_xor across the wave64, the waves through LDS in wave order -- and stores them to ws[clip][p][4];
+ *   apply    every block sums its clip's P partials in index order, makes m and writes m g to both rows of its tile (an element's two
+ *            inputs are read before either is written); block p = 0 writes mult[clip] = m when mult != NULL.
+ * The tiling depends on n alone -- not on b, the row or the slot -- so a clip's m and rows are the same bits in any batch or slot layout
+ * and in every run.
+ *   out   fp32 [2 b, C, F_total, HW], uc rows then c rows (slot form: b = slots, slot s owns rows s and slots + s);
+ *   ws    double [clips][P][4], seer_cfg_rescale_ws_bytes(clips, ...) bytes, 8-byte aligned; it need not be zeroed;
+ *   mult  fp32 [clips] or NULL: the multipliers, for a caller that wants to look at them.
+ *   seer_cfg_rescale       `scale` and `rescale` from the host, for every clip.  rescale == 0: SEER_OK, nothing launched.
+ *   seer_slot_cfg_rescale  slot s uses scale[s] and rescale[s] (device memory) and its in-flight index step[s][1].  A slot that is idle
+ *                          (index < 0 or >= nsched) or has rescale[s] == 0 has NONE of its words written: neither rows, ws nor mult.
+ *                          No step or state word is written by either kernel.  It does not read a PLMS phase: both evaluations of a
+ *                          PLMS first step are rescaled alike.  rescale[s] is not clamped: the host validates it (SlotSampler.submit).
+ * SEER_EINVAL, nothing launched: a NULL required pointer (mult may be NULL), b <= 0, slots outside 1 .. 4, non-positive extents, cond_f
+ * outside 0 .. F_total - 1, nsched < 1, (solo form) rescale outside [0, 1] or not finite, a pointer that is not 4-byte (ws: 8-byte)
+ * aligned, more than 65535 clips or 2^31 - 1 tiles.  seer_cfg_rescale_ws_bytes returns SEER_EINVAL for clips <= 0 or such extents. */
+#define SEER_RESCALE_TILE 1024   /* elements of a clip per workgroup: 256 threads x 4; a multiple of 256 */
+int64_t seer_cfg_rescale_ws_bytes(int32_t clips, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW);
+int seer_cfg_rescale(float* out, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale, float rescale,
+                     double* ws, float* mult /* [b] or NULL */, void* stream);
+int seer_slot_cfg_rescale(float* out, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, const float* scale,
+                          const float* rescale, int32_t nsched, const int32_t* step, double* ws, float* mult /* [slots] or NULL */,
+                          void* stream);
+
 /* decoded image post-process of ddim_sample (utils/ddim_sampling_utils.py:41): clamp((x+1)/2, 0, 1) in place */
 int seer_clamp01(float* x, int64_t n, void* stream);
 

@@ -179,6 +179,9 @@ SIGNATURES = {
     "seer_cfg_dpm_step": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
     "seer_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_slot_v_to_eps": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_cfg_rescale_ws_bytes": ([_i32, _i32, _i32, _i32, _i32], C.c_int64),
+    "seer_cfg_rescale": ([_vp, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _vp, _vp], C.c_int),
+    "seer_slot_cfg_rescale": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp], C.c_int),
     "seer_clamp01": ([_vp, _i64, _vp], C.c_int),
     "seer_gaussian_sample": ([_vp, _i32, _i32, _i32, _vp, _vp, _vp], C.c_int),
     # training step

@@ -23,6 +23,9 @@ yaml's `ddim_steps` is then the PLMS step count (S steps cost S + 1 UNet evaluat
 `SEER_COMPAT_PREDICTION=v_prediction` (read by `install()`, or `install(prediction="v_prediction")`) makes that sampler, whichever it
 is, treat the UNet's output as the velocity v (a model fine-tuned with `prediction_type: v_prediction`, train.py:373-374); unset or
 `epsilon`, it is eps as before.
+`SEER_COMPAT_GUIDANCE_RESCALE=0.7` (read by `install()`, or `install(guidance_rescale=0.7)`) makes that sampler rescale its guided
+output to the conditional branch's std, blended by that factor (Lin et al. 2023; a number in [0, 1], how v-models are sampled);
+unset or 0, nothing is rescaled.
 `SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
 `CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
 then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
@@ -66,6 +69,8 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
                 mod.DDIMSampler = DPMSolverSampler
             if spec.name == "ldm.models.diffusion.ddim_video" and _prediction == "v_prediction":
                 mod.DDIMSampler = _v_sampler(mod.DDIMSampler)
+            if spec.name == "ldm.models.diffusion.ddim_video" and _rescale:
+                mod.DDIMSampler = _rescale_sampler(mod.DDIMSampler, _rescale)
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -96,23 +101,45 @@ def _v_sampler(cls):
             cls.__init__(self, *args, **kwargs)
         _v_samplers[cls] = type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__, "__module__": cls.__module__})
     return _v_samplers[cls]
+
+
+_rescale = 0.
+_rescale_samplers = {}      # (sampler class, phi) -> its subclass whose guidance_rescale defaults to phi
+
+
+def _rescale_sampler(cls, phi: float):
+    """`cls` with guidance_rescale=phi as its constructor's default, as _v_sampler does for the prediction type"""
+    if (cls, phi) not in _rescale_samplers:
+        def __init__(self, *args, **kwargs):
+            kwargs.setdefault("guidance_rescale", phi)
+            cls.__init__(self, *args, **kwargs)
+        _rescale_samplers[cls, phi] = type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__,
+                                                                  "__module__": cls.__module__})
+    return _rescale_samplers[cls, phi]
+
+
 _clip_saved = None          # (transformers module, its own CLIPTextModel) while the native text encoder stands in
 
 
 def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None,
-            prediction: Optional[str] = None) -> None:
+            prediction: Optional[str] = None, guidance_rescale: Optional[float] = None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
     `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler, "dpmpp" its DPMSolverSampler; anything else keeps
     DDIMSampler.
     `prediction` (default: the environment's SEER_COMPAT_PREDICTION) = "v_prediction" makes that class one whose constructor defaults
     to prediction_type="v_prediction"; "epsilon" or nothing keeps it as it is; anything else is train.py:376's ValueError.
+    `guidance_rescale` (default: the environment's SEER_COMPAT_GUIDANCE_RESCALE, 0 when unset) in (0, 1] makes that class one whose
+    constructor defaults to guidance_rescale of that value; 0 keeps it as it is; anything outside [0, 1] is a ValueError.
     `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
     CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
-    global _sampler, _prediction, _clip_saved
+    global _sampler, _prediction, _rescale, _clip_saved
     _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
     _prediction = (os.environ.get("SEER_COMPAT_PREDICTION", "") if prediction is None else prediction).strip().lower()
     if _prediction not in ("", "epsilon", "v_prediction"):
         raise ValueError(f"Unknown prediction type {_prediction}")
+    from seervideoldm_amd.ops import check_guidance_rescale
+    _rescale = check_guidance_rescale((os.environ.get("SEER_COMPAT_GUIDANCE_RESCALE", "").strip() or 0.)
+                                      if guidance_rescale is None else guidance_rescale)
     if (os.environ.get("SEER_COMPAT_CLIP", "") if clip is None else clip).strip().lower() == "native" and _clip_saved is None:
         import transformers
         from seervideoldm_amd import CLIPTextEncoder

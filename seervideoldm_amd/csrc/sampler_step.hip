@@ -1,8 +1,8 @@
 // The kernels at both ends of a sampler step on gfx950, fp32, one thread per latent element: "assemble the UNet input and latch the
 // counter", "CFG-combine eps and apply the DDIM, inversion, PLMS or DPM-Solver++ update", "re-noise the given latents", and between the two
-// ends "turn a v-model's output into eps".  Every form of a step -- host index, device counter, seeded, over slots -- runs ONE device
-// body per idea (cfg_eps_at, step_update, invert_update, plms_update, dpm_update, eps_from_v, known_blend_at), so an element gets the
-// same bits from each of them.
+// ends "turn a v-model's output into eps" and "rescale the guided output to the conditional row's std" (the one reduction here).
+// Every form of a step -- host index, device counter, seeded, over slots -- runs ONE device body per idea (cfg_eps_at, step_update,
+// invert_update, plms_update, dpm_update, eps_from_v, the rescale pair, known_blend_at), so an element gets the same bits from each.
 #include "seer_common.h"
 #include "seer_philox.h"
 #include <cstdint>
@@ -448,6 +448,119 @@ __global__ void slot_v_to_eps_kernel(const float* v, int slots, int C, int Ft, i
     v_to_eps_at(v, lat + s * per, coef + ((int64_t)s * nsched + index) * 4, C, Ft, cond_f, HW, r, i - r * per, out);
 }
 
+// ---- guidance rescale (Lin et al. 2023, section 3.4; diffusers rescale_noise_cfg): the guided output g of a clip, scaled so that its std
+// over the clip's predicted frames matches the conditional row's, blended with the unscaled g by phi -- out = m g with
+//   m = phi sqrt(q_c / q_g) + (1 - phi),   q = n S2 - S1^2 (n^2 times the variance: the n - 1 of an unbiased std cancels in the ratio),
+// written to BOTH rows of the clip's [uc | c] pair: the update kernel behind it then combines eu == ec, which gives ec again exactly
+// (ec - eu = +0, scale * 0 = 0, eu + 0 = eu, contracted or not), so no update kernel knows of it.  It is the first thing here that needs
+// a whole clip, and it is two launches over the same grid (P tiles of SEER_RESCALE_TILE elements, clips): "moments" reduces a tile to
+// four doubles (sum c, sum c^2, sum g, sum g^2) in a fixed order -- per thread in index order, __shfl_xor across the wave, the waves
+// through LDS in wave order -- and STORES them to ws[clip][p][4]; "apply" sums a clip's P partials in index order, makes m and writes
+// m g over the tile.  No atomics, no counter, no waiting inside a launch: a clip's m has the same bits in every run, and, because the
+// tiling follows from n alone, for every batch size, row and slot.  g is cfg_eps_at's value in both passes: the moments are taken of
+// exactly the numbers that get scaled.
+// The form is read from the pointers: scale_v == nullptr is the solo form (`scale`, `phi` for every clip); else slot s uses scale_v[s]
+// and phi_v[s], and a slot that is idle (step[s][1] outside 0 .. nsched - 1) or has phi_v[s] == 0 has no word written by either kernel.
+enum { RESCALE_THREADS = 256, RESCALE_PER_THREAD = SEER_RESCALE_TILE / RESCALE_THREADS };
+static_assert(SEER_RESCALE_TILE % RESCALE_THREADS == 0 && RESCALE_PER_THREAD >= 1, "SEER_RESCALE_TILE is a multiple of 256");
+
+struct RescaleClip {
+    bool active;
+    float scale, phi;
+};
+
+__device__ __forceinline__ RescaleClip rescale_clip(int clip, float scale, float phi, const float* __restrict__ scale_v,
+                                                    const float* __restrict__ phi_v, int nsched, const int* __restrict__ step) {
+    if (!scale_v) return RescaleClip{true, scale, phi};
+    const int index = step[2 * clip + 1];
+    const float ph = phi_v[clip];
+    return RescaleClip{index >= 0 && index < nsched && ph != 0.f, scale_v[clip], ph};
+}
+
+// the offset in eps [2 rows, C, Ft, HW] of element e (counted over the predicted frames) of the uc row of `clip`; its c row is
+// rows * C * Ft * HW further on (cfg_eps_at's own addressing)
+__device__ __forceinline__ int64_t rescale_offset(int clip, int C, int Ft, int cond_f, int HW, int64_t e) {
+    const int Fp = Ft - cond_f;
+    const int hw = (int)(e % HW);
+    const int f = (int)((e / HW) % Fp);
+    const int c = (int)(e / ((int64_t)HW * Fp));
+    return (((int64_t)clip * C + c) * Ft + (f + cond_f)) * HW + hw;
+}
+
+__global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_moments_kernel(
+    const float* __restrict__ eps, int rows, int C, int Ft, int cond_f, int HW, float scale, float phi,
+    const float* __restrict__ scale_v, const float* __restrict__ phi_v, int nsched, const int* __restrict__ step,
+    double* __restrict__ ws) {
+    const int clip = blockIdx.y;
+    const RescaleClip rc = rescale_clip(clip, scale, phi, scale_v, phi_v, nsched, step);
+    if (!rc.active) return;
+    const int64_t n = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t pair = (int64_t)rows * C * Ft * HW;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < RESCALE_PER_THREAD; ++k) {
+        const int64_t e = (int64_t)blockIdx.x * SEER_RESCALE_TILE + k * RESCALE_THREADS + threadIdx.x;
+        if (e >= n) break;
+        const double c = (double)eps[rescale_offset(clip, C, Ft, cond_f, HW, e) + pair];
+        const double g = (double)cfg_eps_at(eps, 1, rows, C, Ft, cond_f, HW, rc.scale, (int64_t)clip * n + e);
+        s[0] += c, s[1] += c * c, s[2] += g, s[3] += g * g;
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int j = 0; j < 4; ++j) s[j] += __shfl_xor(s[j], off);
+    __shared__ double part[RESCALE_THREADS / 64][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < 4; ++j) part[wave][j] = s[j];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double t = part[0][threadIdx.x];
+        for (int w = 1; w < RESCALE_THREADS / 64; ++w) t += part[w][threadIdx.x];
+        ws[((int64_t)clip * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = t;
+    }
+}
+
+// the multiplier of a clip from its four sums; q_g <= 0 (a constant clip, n = 1) or a ratio that is not finite: 1, where diffusers
+// divides by a zero std
+__device__ __forceinline__ float rescale_multiplier(const double* s, int64_t n, float phi) {
+    const double nn = (double)n;
+    const double qc = fmax(nn * s[1] - s[0] * s[0], 0.0);
+    const double qg = nn * s[3] - s[2] * s[2];
+    if (!(qg > 0.0)) return 1.f;
+    const double r = qc / qg;
+    if (!isfinite(r)) return 1.f;
+    return (float)((double)phi * sqrt(r) + (1.0 - (double)phi));
+}
+
+__global__ __launch_bounds__(RESCALE_THREADS) void cfg_rescale_apply_kernel(
+    float* eps, int rows, int C, int Ft, int cond_f, int HW, float scale, float phi, const float* __restrict__ scale_v,
+    const float* __restrict__ phi_v, int nsched, const int* __restrict__ step, const double* __restrict__ ws,
+    float* __restrict__ mult) {
+    const int clip = blockIdx.y;
+    const RescaleClip rc = rescale_clip(clip, scale, phi, scale_v, phi_v, nsched, step);
+    if (!rc.active) return;
+    const int64_t n = (int64_t)C * (Ft - cond_f) * HW;
+    const int64_t pair = (int64_t)rows * C * Ft * HW;
+    __shared__ float m_shared;
+    if (threadIdx.x == 0) {
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        const double* w = ws + (int64_t)clip * gridDim.x * 4;
+        for (unsigned p = 0; p < gridDim.x; ++p)
+            for (int j = 0; j < 4; ++j) s[j] += w[4 * (int64_t)p + j];
+        const float m = rescale_multiplier(s, n, rc.phi);
+        m_shared = m;
+        if (blockIdx.x == 0 && mult) mult[clip] = m;
+    }
+    __syncthreads();
+    const float m = m_shared;
+    for (int k = 0; k < RESCALE_PER_THREAD; ++k) {
+        const int64_t e = (int64_t)blockIdx.x * SEER_RESCALE_TILE + k * RESCALE_THREADS + threadIdx.x;
+        if (e >= n) break;
+        const int64_t off = rescale_offset(clip, C, Ft, cond_f, HW, e);
+        const float v = m * cfg_eps_at(eps, 1, rows, C, Ft, cond_f, HW, rc.scale, (int64_t)clip * n + e);
+        eps[off] = v;
+        eps[off + pair] = v;
+    }
+}
+
 // ---- GIVEN latents (masked sampling, stochastic_encode; CompVis ldm/models/diffusion/ddim.py:144-147, 207-221): q(e) is the given
 // latent x0 noised to the level of coefficient row `index`, its noise n either read from a tensor or normal e of Philox stream 2 of
 // the clip's seed at that index.  One expression for the three kernels below, so the seeded form gets the bits of the noise-tensor
@@ -690,6 +803,55 @@ extern "C" int seer_slot_v_to_eps(const float* v, int32_t slots, int32_t C, int3
     return launch_per_element(slot_v_to_eps_kernel, 2 * elements(slots, C, (int64_t)F_total - cond_f, HW),
                               {v, coef, step, state, x, x_prov, out}, stream, v, slots, C, F_total, cond_f, HW, coef, nsched, step, state,
                               x, x_prov, out);
+}
+
+// guidance rescale: two launches over (tiles of a clip, clips); the solo and the slot export differ in where scale and phi come from
+namespace {
+
+inline int64_t rescale_tiles(int32_t C, int32_t F_total, int32_t cond_f, int32_t HW) {
+    return (elements(1, C, (int64_t)F_total - cond_f, HW) + SEER_RESCALE_TILE - 1) / SEER_RESCALE_TILE;
+}
+
+int launch_rescale(float* out, int32_t clips, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale, float phi,
+                   const float* scale_v, const float* phi_v, int32_t nsched, const int32_t* step, double* ws, float* mult,
+                   void* stream) {
+    for (const void* p : Pointers{out, scale_v, phi_v, step, mult})
+        if (reinterpret_cast<uintptr_t>(p) & 3) return SEER_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 7) return SEER_EINVAL;
+    const int64_t tiles = rescale_tiles(C, F_total, cond_f, HW);
+    if (tiles > 0x7fffffff || clips > 65535) return SEER_EINVAL;
+    const dim3 grid((unsigned)tiles, (unsigned)clips), block(RESCALE_THREADS);
+    hipLaunchKernelGGL(cfg_rescale_moments_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), out, clips, C, F_total,
+                       cond_f, HW, scale, phi, scale_v, phi_v, nsched, step, ws);
+    SEER_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cfg_rescale_apply_kernel, grid, block, 0, reinterpret_cast<hipStream_t>(stream), out, clips, C, F_total,
+                       cond_f, HW, scale, phi, scale_v, phi_v, nsched, step, ws, mult);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t seer_cfg_rescale_ws_bytes(int32_t clips, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW) {
+    if (clips <= 0 || !update_shape_ok(C, F_total, cond_f, HW)) return SEER_EINVAL;
+    return (int64_t)clips * rescale_tiles(C, F_total, cond_f, HW) * 4 * (int64_t)sizeof(double);
+}
+
+extern "C" int seer_cfg_rescale(float* out, int32_t b, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW, float scale,
+                                float rescale, double* ws, float* mult, void* stream) {
+    if (!out || !ws || b <= 0 || !update_shape_ok(C, F_total, cond_f, HW) || !(rescale >= 0.f && rescale <= 1.f))
+        return SEER_EINVAL;
+    if (rescale == 0.f) return SEER_OK;
+    return launch_rescale(out, b, C, F_total, cond_f, HW, scale, rescale, nullptr, nullptr, 1, nullptr, ws, mult, stream);
+}
+
+// slots 1..4 as in the other slot forms; phi is the host's to validate (submit), nothing is clamped here
+extern "C" int seer_slot_cfg_rescale(float* out, int32_t slots, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                                     const float* scale, const float* rescale, int32_t nsched, const int32_t* step, double* ws,
+                                     float* mult, void* stream) {
+    if (!out || !scale || !rescale || !step || !ws || slots < 1 || slots > 4 || nsched < 1 || !update_shape_ok(C, F_total, cond_f, HW))
+        return SEER_EINVAL;
+    return launch_rescale(out, slots, C, F_total, cond_f, HW, 0.f, 0.f, scale, rescale, nsched, step, ws, mult, stream);
 }
 
 // given latents: exactly one of noise and seeds; a clip's element index is a Philox counter word, as in the seeded steps

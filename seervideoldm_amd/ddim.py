@@ -30,6 +30,13 @@ output is then v = sqrt(a) eps - sqrt(1 - a) x0, and ONE more elementwise kernel
 seer_v_to_eps) turns it into eps = sqrt(a) v + sqrt(1 - a) x_t in front of the step's last kernel, with the coefficient row that
 kernel reads.  Everything behind it -- CFG, eta > 0, seeds, mask / x0, decode, stochastic_encode -- acts on eps or on latents and is
 unchanged.  `encode` is refused for such a model (see there).  With the default "epsilon" nothing new is launched or allocated.
+
+`DDIMSampler(device, guidance_rescale=0.7)` -- or `guidance_rescale=` on sample, decode, encode, p_sample_ddim and p_invert_ddim, which
+overrides the constructor's value for that call -- is guidance rescale (Lin et al. 2023, section 3.4; diffusers' rescale_noise_cfg), the
+way v-models are sampled: the guided model output is scaled so that its std over a clip matches the conditional branch's and blended
+with the unscaled one by that factor.  One node (two launches, seer_cfg_rescale) between the model and the conversion above overwrites
+both rows of the [uc | c] pair with the result, and the update kernels behind it are unchanged (DESIGN.md "Guidance rescale").  A number
+in [0, 1]; at 0 (the default), or where CFG is off, nothing is launched and the graph keys are what they were.  A sharded model is refused.
 """
 from __future__ import annotations
 
@@ -66,6 +73,8 @@ class DDIMSampler(object):
         self.ops = kwargs.get("ops") or ops
         # what the UNet's output is (train.py:371-376): "epsilon", or "v_prediction" -- converted to eps in front of every update
         self.prediction_type = ops.check_prediction_type(kwargs.get("prediction_type", "epsilon"))
+        # guidance rescale (Lin et al. 2023): the default blend factor of every call, 0 = off; a call's own keyword overrides it
+        self.guidance_rescale = ops.check_guidance_rescale(kwargs.get("guidance_rescale", 0.))
         self.consume_rng_when_deterministic = True
         # p_sample_ddim under graph replay hands out its static latent buffers instead of copies of them: the next step
         # overwrites what the previous one returned.  ddim_sampling sets it for its own loop (and copies what it keeps).
@@ -123,7 +132,8 @@ class DDIMSampler(object):
                                   img_callback=img_callback, cond_frames=cond_frames, temperature=temperature,
                                   noise_dropout=noise_dropout, x_T=x_T, log_every_t=log_every_t,
                                   unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds, mask=mask, x0=x0)
+                                  unconditional_conditioning=unconditional_conditioning, seeds=seeds, mask=mask, x0=x0,
+                                  guidance_rescale=kwargs.get("guidance_rescale"))
 
     def _sample_size(self, S, batch_size, shape, conditioning, eta, verbose, is_3d):
         """how every sample() starts (ddim_video.py:84-98): the conditioning warning, the schedule of S steps, the latent's 5-D size"""
@@ -150,7 +160,7 @@ class DDIMSampler(object):
     def ddim_sampling(self, unet, cond, shape, is_3d, x0_emb=None, cond_frames=0, x_T=None, callback=None,
                       img_callback=None, log_every_t=100, temperature=1., noise_dropout=0.,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, seeds=None, mask=None, x0=None,
-                      t_start=None, **kwargs):
+                      t_start=None, guidance_rescale=None, **kwargs):
         """`seeds`: None, or one uint64 per batch row (sample's `seed`): the start code (when x_T is None) and the noise of every step
         then come from the rows' Philox streams, nothing from torch's generator.  `mask` (broadcastable to [b, 1, F_pred, h, w], values
         in [0, 1]) with `x0` [b, C, F_pred, h, w]: in front of every step the latent becomes q * mask + (1 - mask) * latent, q = x0
@@ -173,7 +183,7 @@ class DDIMSampler(object):
         step = lambda img, index: self.p_sample_ddim(
             unet, img, cond, self._t_table[index].expand(b), index=index, is_3d=is_3d, x0_emb=x0_emb, cond_frames=cond_frames,
             temperature=temperature, noise_dropout=noise_dropout, unconditional_guidance_scale=unconditional_guidance_scale,
-            unconditional_conditioning=unconditional_conditioning, seeds=seeds, known=known)
+            unconditional_conditioning=unconditional_conditioning, seeds=seeds, known=known, guidance_rescale=guidance_rescale)
         return self._run_chain(img, self.ddim_timesteps.shape[0] if t_start is None else int(t_start), step, callback, img_callback,
                                log_every_t)
 
@@ -245,7 +255,8 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, unet, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               use_original_steps=False, *, x0_emb=None, cond_frames=0, seed=None, temperature=1., mask=None, x0=None):
+               use_original_steps=False, *, x0_emb=None, cond_frames=0, seed=None, temperature=1., mask=None, x0=None,
+               guidance_rescale=None):
         """CompVis ddim.py:223-241 with the UNet first, as in sample: indices t_start - 1 ... 0 of the current schedule through
         p_sample_ddim, from x_latent taken as the latent at level t_start.  seed, mask and x0 as in sample."""
         if use_original_steps:
@@ -256,11 +267,12 @@ class DDIMSampler(object):
         return self.ddim_sampling(unet, cond, tuple(x_latent.shape), True, x0_emb=x0_emb, cond_frames=cond_frames, x_T=x_latent,
                                   temperature=temperature, unconditional_guidance_scale=unconditional_guidance_scale,
                                   unconditional_conditioning=unconditional_conditioning,
-                                  seeds=_row_seeds(seed, x_latent.shape[0]), mask=mask, x0=x0, t_start=t_start)[0]
+                                  seeds=_row_seeds(seed, x_latent.shape[0]), mask=mask, x0=x0, t_start=t_start,
+                                  guidance_rescale=guidance_rescale)[0]
 
     @torch.no_grad()
     def encode(self, unet, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, callback=None, *, x0_emb=None, cond_frames=0):
+               unconditional_conditioning=None, callback=None, *, x0_emb=None, cond_frames=0, guidance_rescale=None):
         """DDIM inversion, CompVis ddim.py encode() on the current schedule with the UNet first, as in sample: the deterministic
         counterpart of stochastic_encode.  x0 [b, C, F_pred, h, w] is taken as the latent at the level of row 0's a_prev; the indices
         0 ... t_enc - 1 run UPWARD through p_invert_ddim, each evaluating the model at its own (the target level's) timestep, and
@@ -288,7 +300,8 @@ class DDIMSampler(object):
             for index in range(t_enc):
                 img, pred_x0 = self.p_invert_ddim(unet, img, c, self._t_table[index].expand(b), index, x0_emb=x0_emb,
                                                   cond_frames=cond_frames, unconditional_guidance_scale=unconditional_guidance_scale,
-                                                  unconditional_conditioning=unconditional_conditioning, limit=t_enc)
+                                                  unconditional_conditioning=unconditional_conditioning, limit=t_enc,
+                                                  guidance_rescale=guidance_rescale)
                 if every is not None and (index + 1) % every == 0:
                     intermediates["x_inter"].append(img.clone())
                     intermediates["pred_x0"].append(pred_x0.clone())
@@ -300,7 +313,7 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def p_invert_ddim(self, unet, x, c, t, index, x0_emb=None, cond_frames=0, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, limit=None):
+                      unconditional_conditioning=None, limit=None, guidance_rescale=None):
         """One step of encode: x at the level of row `index`'s a_prev, the model evaluated at t (encode passes the row's own timestep)
         -> (x_next at the level of a_t, pred_x0).  Nothing is drawn.  `limit`: the number of rows the chain this step belongs to may
         use (encode's t_enc; the whole schedule when None) -- what the captured step's counter stops at.  Refused for a v-model, as
@@ -314,21 +327,43 @@ class DDIMSampler(object):
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         # the captured step is gated as p_sample_ddim gates its own: batched CFG or none, and t the schedule table's own entry
         plain = uc is None or scale == 1.
+        phi = self._rescale_factor(unet, guidance_rescale, plain)
         if ((plain or uc.shape[2] == c.shape[2]) and torch.is_tensor(t) and t.dtype == torch.long
                 and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
             done = self._invert_graph_step(unet, x, c, None if plain else uc, int(index), x0_emb, 0 if plain else cond_frames, scale,
-                                           limit)
+                                           limit, phi=phi)
             if done is not None:
                 return done
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
-        return self.ops.cfg_ddim_invert_step(eps.float().contiguous(), x, self.ddim_coef, int(index), cfg=cfg, scale=scale,
-                                             cond_f=cond_f)
+        return self.ops.cfg_ddim_invert_step(self._rescaled(eps, scale, cond_f, phi), x, self.ddim_coef, int(index), cfg=cfg,
+                                             scale=scale, cond_f=cond_f)
 
     def _refuse_v_inversion(self):
         if self.prediction_type != "epsilon":
             raise NotImplementedError("DDIM inversion (encode / p_invert_ddim) of a v-prediction model: the step evaluates the model at "
                                       "the target level's timestep on a latent of the level below, so it is ambiguous which level's "
                                       "coefficients convert v to eps")
+
+    def _rescale_factor(self, unet, guidance_rescale, plain):
+        """the blend factor phi of guidance rescale for one step: the call's own `guidance_rescale`, else the constructor's; 0 where CFG
+        is off (`plain`: there is nothing to rescale).  phi > 0 on a sharded model is refused: a clip's elements, or its two rows, are on
+        different ranks there, and the sums are not exchanged."""
+        phi = self.guidance_rescale if guidance_rescale is None else ops.check_guidance_rescale(guidance_rescale)
+        if plain or phi == 0.:
+            return 0.
+        _refuse_sharded(unet, "rescale")
+        return phi
+
+    def _rescaled(self, out, scale, cond_f, phi):
+        """the model output `out` [2b, C, cond_f + F, h, w] as fp32, with guidance rescale applied when phi > 0 (_rescale_factor: CFG
+        is on then): both rows of every clip become m * (the guided output), seer_cfg_rescale, in front of _as_eps -- for a v-model it
+        is v that is rescaled, as in diffusers.  The rows are written on a tensor of this step's own, never on the model's."""
+        res = out.float().contiguous()
+        if phi == 0.:
+            return res
+        if res.data_ptr() == out.data_ptr():
+            res = res.clone()
+        return self.ops.cfg_rescale(res, scale=scale, rescale=phi, cond_f=cond_f)
 
     def _as_eps(self, out, x, index, cond_f):
         """the model output `out` [2b or b, C, cond_f + F, h, w] of an evaluation at x and at schedule entry `index`'s timestep, as fp32
@@ -342,7 +377,7 @@ class DDIMSampler(object):
     def p_sample_ddim(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                       use_original_steps=False, temperature=1., noise_dropout=0., score_corrector=None,
                       corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None,
-                      null_cond_prob=None, seeds=None, known=None):
+                      null_cond_prob=None, seeds=None, known=None, guidance_rescale=None):
         """ddim_video.py:183-238.  `seeds` (int32 [b, 2] on x's device, ops.seed_words; not in the reference): the step's noise is
         drawn inside its last kernel from the rows' seeds and `index`, and torch's generator is left alone.  `known` (_known_pair's
         mask and given latents; not in the reference either): the mask blend of CompVis ddim.py:144-147 in front of the step, on a
@@ -360,16 +395,17 @@ class DDIMSampler(object):
         # one ddim_sample drives: batched CFG or none, eta = 0 or a seed, and t = the schedule's own timestep of `index` (recognised by
         # its address: a view of the device timestep table).  Whether the model's steps may be captured at all is _step_graph's question.
         plain = uc is None or scale == 1.
+        phi = self._rescale_factor(unet, guidance_rescale, plain)
         if ((sigma == 0. or seeds is not None) and (plain or uc.shape[2] == c.shape[2]) and torch.is_tensor(t) and t.dtype == torch.long
                 and t.data_ptr() == self._t_table.data_ptr() + 8 * int(index)):
             done = self._graph_step(unet, x, c, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale,
-                                    seeds=seeds, temperature=temperature, known=known)
+                                    seeds=seeds, temperature=temperature, known=known, phi=phi)
             if done is not None:
                 return done
         if known is not None:
             x = self.ops.known_blend(x.clone(), known[0], known[1], self.ddim_coef, index, seeds=seeds)
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
-        eps = self._as_eps(eps, x, index, cond_f)
+        eps = self._as_eps(self._rescaled(eps, scale, cond_f, phi), x, index, cond_f)
         if seeds is not None:
             return self.ops.cfg_ddim_step_rng(eps, x, self.ddim_coef, index, seeds, cfg=cfg, scale=scale,
                                               cond_f=cond_f, temperature=temperature)
@@ -405,7 +441,7 @@ class DDIMSampler(object):
         return eps, cfg, cond_f
 
     # ---- the captured step -----------------------------------------------------------------------------------------
-    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1., known=None):
+    def _graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, seeds=None, temperature=1., known=None, phi=0.):
         """One p_sample_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_step):
         no torch kernel between two UNet evaluations except the reference's per-step RNG draw, no host-written scalars -- the
         schedule index lives in device memory and the captured step counts it down itself.  Returns None when this step cannot
@@ -413,7 +449,7 @@ class DDIMSampler(object):
         is the same entry point given seeds and the step draws nothing, at any eta.  With `known` (seeded only) seer_known_blend is the
         step's first node, over static copies of the mask and the given latents."""
         kind = "step" if seeds is None else "step-rng" if known is None else "step-mask"
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, kind, None if seeds is None else float(temperature))
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, kind, None if seeds is None else float(temperature), phi=phi)
         if G is None:
             return None
         if seeds is not None:
@@ -424,11 +460,11 @@ class DDIMSampler(object):
             G["step"][:1].fill_(int(index))         # start of a chain (or a caller that jumps): the only host-written index
         return self._replay_step(G, x, index, draw=seeds is None)
 
-    def _invert_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, limit):
+    def _invert_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, limit, phi=0.):
         """One p_invert_ddim as a single hipGraph replay (seer_ddim_step_begin -> the UNet's kernels -> seer_cfg_ddim_invert_step).
         The captured step counts its index UPWARD and stops writing at the limit word of its static buffers; at the start of a chain
         the host writes those two words, step[0] and limit[0], and nothing after.  None when the step cannot be captured."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "invert")
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "invert", phi=phi)
         if G is None:
             return None
         if G["expect"] != index or G["limit_host"] != limit:
@@ -455,12 +491,14 @@ class DDIMSampler(object):
             self._cfg_cat = torch.cat([uc, c]).contiguous()
         return self._cfg_cat
 
-    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, kind, temperature=None):
+    def _step_graph(self, unet, x, c, uc, x0_emb, cond_frames, scale, kind, temperature=None, phi=0.):
         """the captured step of this kind / shape / CFG / scale (captured on first use) with x and its read-by-address inputs
         refreshed; None when the step cannot be captured.  `kind` is the key's first word and an entry of STEP_KINDS.  A seeded kind
         comes with its temperature, the key's last field: like the guidance scale it is an argument of the last kernel and frozen
         into the capture; seeds, mask and given latents live in static buffers and are no part of the key.  A v-model's step has one
-        more node and "v_prediction" as the key's very last word; the default's keys are what they were."""
+        more node and "v_prediction" as the key's last word of its own; the default's keys are what they were.  `phi` (_rescale_factor:
+        0 unless CFG is on) > 0 is guidance rescale, one more node in front of that one and ("rescale", phi) as the key's trailing words:
+        phi is a kernel argument frozen into the capture, like the guidance scale."""
         eng = None if self._capture_refused else capture_engine(unet, self.ops, x.device)
         if eng is None:
             return None
@@ -477,10 +515,12 @@ class DDIMSampler(object):
         # (the guidance scale is only part of a CFG step: a plain step at another scale is the same graph)
         key = (kind, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv,
                *(() if temperature is None else (float(temperature),)),
-               *(() if self.prediction_type == "epsilon" else (self.prediction_type,)))
+               *(() if self.prediction_type == "epsilon" else (self.prediction_type,)),
+               *(("rescale", float(phi)) if cfg and phi > 0. else ()))
         G = eng.graph_get(key)
         if G is None:
-            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L)
+            G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L,
+                                   phi=float(phi) if cfg else 0.)
             if G is None:
                 return None
         n = self.ddim_coef.shape[0]
@@ -495,8 +535,9 @@ class DDIMSampler(object):
             G["x"].copy_(x)
         return G
 
-    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, temperature, ctx, L):
-        """the step of kind key[0] over fresh static buffers, captured and put under `key`; None when the capture is refused"""
+    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, temperature, ctx, L, phi=0.):
+        """the step of kind key[0] over fresh static buffers, captured and put under `key`; None when the capture is refused.  phi > 0:
+        the rescale node sits behind the model and in front of the v-conversion, its workspace one more static buffer"""
         dev = x.device
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
@@ -509,6 +550,8 @@ class DDIMSampler(object):
                  coef=torch.zeros((nsched, 4), device=dev, dtype=torch.float32),
                  ttab=torch.zeros((nsched,), device=dev, dtype=torch.long), expect=None, **buffers(x),
                  kept={})                            # step_graph.refresh's record of what the static buffers were last filled from
+        if phi > 0.:
+            G["rescale_ws"] = ops.cfg_rescale_workspace(b, Cc, f1 + Fp, f1, h * w, dev)
         G["coef"][:, 0] = 1.0                        # a_t = 1 in the unused rows: the warm-up below must stay finite
         G["x"].copy_(x)
         if x0_emb is not None:
@@ -519,7 +562,9 @@ class DDIMSampler(object):
                 launch(G)
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
             eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
-            if self.prediction_type != "epsilon":       # in place, on the engine's output buffer: nothing is allocated for it
+            if phi > 0.:                                # in place, on the engine's output buffer, both rows of every clip
+                ops.cfg_rescale(eps, scale=scale, rescale=phi, cond_f=f1, ws=G["rescale_ws"])
+            if self.prediction_type != "epsilon":       # in place as well: nothing is allocated for it
                 ops.v_to_eps_dev(eps, G["x"], G["coef"], G["step"], cond_f=f1, out=eps)
             update(G, eps, temperature, cfg=cfg, scale=scale, cond_f=f1)
         if capture_step(eng, key, G, body) is None:
@@ -576,7 +621,9 @@ def _refuse_sharded(unet, what: str) -> None:
     """what one clip sharded over several ranks (parallel.attach) cannot do"""
     if getattr(unet, "_shard", None) is not None:
         raise ValueError({"seed": "seed: a frame-sharded model draws its noise on rank 0 (detach it, parallel.attach, to sample from a seed)",
-                          "mask": "mask: a frame-sharded model cannot blend given latents (detach it, parallel.attach)"}[what])
+                          "mask": "mask: a frame-sharded model cannot blend given latents (detach it, parallel.attach)",
+                          "rescale": "guidance_rescale: a sharded model holds a clip's elements, or its two CFG rows, on different ranks, "
+                                     "and the sums are not exchanged (detach it, parallel.attach, or sample with guidance_rescale=0)"}[what])
 
 
 def _row_seeds(seed, batch_size: int):

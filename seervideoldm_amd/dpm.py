@@ -26,7 +26,8 @@ the history is the step's own pred_x0 buffer, and the kernel picks its order fro
 no host-written scalar after its first step.
 
 prediction_type="v_prediction" (DDIMSampler's keyword) converts the model's v with the DDIM coefficient rows of this sampler's own
-timesteps, the log-SNR grid included, in front of either form of the step.
+timesteps, the log-SNR grid included, in front of either form of the step.  `guidance_rescale` (DDIMSampler's keyword; per call on
+sample, decode and p_sample_dpm) rescales the guided model output in front of that, in either form of the step as well.
 
 Only the deterministic solver is built: no mask / x0, no seed, no eta > 0 (the SDE variant), no noise_dropout, no order 3, no
 singlestep (2S) form.  The per-step torch.randn draw of the reference's samplers is kept (consume_rng_when_deterministic), as in
@@ -123,11 +124,13 @@ class DPMSolverSampler(DDIMSampler):
         return self.dpm_sampling(unet, conditioning, size, x0_emb=x0_emb, callback=callback, img_callback=img_callback,
                                  cond_frames=cond_frames, x_T=x_T, log_every_t=log_every_t,
                                  unconditional_guidance_scale=unconditional_guidance_scale,
-                                 unconditional_conditioning=unconditional_conditioning)
+                                 unconditional_conditioning=unconditional_conditioning,
+                                 guidance_rescale=kwargs.get("guidance_rescale"))
 
     @torch.no_grad()
     def dpm_sampling(self, unet, cond, shape, x0_emb=None, cond_frames=0, x_T=None, callback=None, img_callback=None,
-                     log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, t_start=None, **kwargs):
+                     log_every_t=100, unconditional_guidance_scale=1., unconditional_conditioning=None, t_start=None,
+                     guidance_rescale=None, **kwargs):
         """the chain over the indices n - 1 ... 0 of the current schedule (t_start - 1 ... 0 with `t_start`: x_T is then the latent at
         that level), every step one captured replay where the step can be captured, launch by launch (p_sample_dpm) where not"""
         b = shape[0]
@@ -135,6 +138,7 @@ class DPMSolverSampler(DDIMSampler):
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         plain = uc is None or scale == 1.
         batched = plain or uc.shape[2] == cond.shape[2]
+        phi = self._rescale_factor(unet, guidance_rescale, plain)
         d_prev, chained = None, False
 
         def step(img, index):
@@ -142,11 +146,12 @@ class DPMSolverSampler(DDIMSampler):
             out = None
             if batched:
                 out = self._dpm_graph_step(unet, img, cond, None if plain else uc, index, x0_emb, 0 if plain else cond_frames, scale,
-                                           restart=not chained)
+                                           restart=not chained, phi=phi)
             chained = out is not None
             if out is None:
                 out = self.p_sample_dpm(unet, img, cond, self._t_table[index].expand(b), index, x0_emb=x0_emb, cond_frames=cond_frames,
-                                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, d_prev=d_prev)
+                                        unconditional_guidance_scale=scale, unconditional_conditioning=uc, d_prev=d_prev,
+                                        guidance_rescale=phi)
             d_prev = out[1]
             return out
         return self._run_chain(img, self.ddim_timesteps.shape[0] if t_start is None else int(t_start), step, callback, img_callback,
@@ -155,7 +160,8 @@ class DPMSolverSampler(DDIMSampler):
     @torch.no_grad()
     def p_sample_dpm(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                      use_original_steps=False, quantize_denoised=False, temperature=1., noise_dropout=0., score_corrector=None,
-                     corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None, d_prev=None):
+                     corrector_kwargs=None, unconditional_guidance_scale=1., unconditional_conditioning=None, d_prev=None,
+                     guidance_rescale=None):
         """One step, launch by launch (seer_cfg_dpm_step) -> (x_prev, pred_x0).  `d_prev`: the pred_x0 the step at index + 1
         returned, None for the first step of a chain; the order follows from it (step_order)."""
         if use_original_steps or noise_dropout > 0. or repeat_noise or quantize_denoised or score_corrector is not None:
@@ -163,11 +169,13 @@ class DPMSolverSampler(DDIMSampler):
         x = x.to(torch.float32).contiguous()
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         order = self.step_order(index, d_prev is not None)
+        phi = self._rescale_factor(unet, guidance_rescale, uc is None or scale == 1.)
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
         if self.consume_rng_when_deterministic:
             torch.randn(x.shape, device=x.device)       # the reference's samplers draw in every update, also at sigma = 0
-        return self.ops.cfg_dpm_step(self._as_eps(eps, x, index, cond_f), x, self.dpm_coef, int(index), order, cfg=cfg, scale=scale,
-                                     cond_f=cond_f, d_prev=d_prev.to(torch.float32).contiguous() if order == 2 else None)
+        eps = self._as_eps(self._rescaled(eps, scale, cond_f, phi), x, index, cond_f)
+        return self.ops.cfg_dpm_step(eps, x, self.dpm_coef, int(index), order, cfg=cfg, scale=scale, cond_f=cond_f,
+                                     d_prev=d_prev.to(torch.float32).contiguous() if order == 2 else None)
 
     def p_sample_ddim(self, *args, **kwargs):
         raise NotImplementedError("DPMSolverSampler steps with p_sample_dpm")
@@ -177,7 +185,8 @@ class DPMSolverSampler(DDIMSampler):
 
     @torch.no_grad()
     def decode(self, unet, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None,
-               use_original_steps=False, *, x0_emb=None, cond_frames=0, seed=None, temperature=1., mask=None, x0=None):
+               use_original_steps=False, *, x0_emb=None, cond_frames=0, seed=None, temperature=1., mask=None, x0=None,
+               guidance_rescale=None):
         """SDEdit's downward half (DDIMSampler.decode) with this solver: indices t_start - 1 ... 0 of the current schedule from x_latent
         taken as the latent at level t_start, first order on its first step.  Nothing is drawn, so `seed` (what edit_clips hands
         every decode) and `temperature` have nothing to act on."""
@@ -190,13 +199,14 @@ class DPMSolverSampler(DDIMSampler):
             raise ValueError(f"t_start = {t_start}: 1 .. {n}, the entries of the current schedule")
         return self.dpm_sampling(unet, cond, tuple(x_latent.shape), x0_emb=x0_emb, cond_frames=cond_frames, x_T=x_latent,
                                  unconditional_guidance_scale=unconditional_guidance_scale,
-                                 unconditional_conditioning=unconditional_conditioning, t_start=t_start)[0]
+                                 unconditional_conditioning=unconditional_conditioning, t_start=t_start,
+                                 guidance_rescale=guidance_rescale)[0]
 
-    def _dpm_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, restart):
+    def _dpm_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, restart, phi=0.):
         """One step as a single replay.  `restart` (the first step of a chain), a counter that is not where this step needs it, or a
         new schedule: the host writes the index and the four state words -- history invalid, the order, the final-step rule -- and
         the step runs first order; these are the only host writes of a chain.  Returns None when the step cannot be captured."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "dpm")
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "dpm", phi=phi)
         if G is None:
             return None
         n = self.dpm_coef.shape[0]

@@ -1457,6 +1457,71 @@ def slot_v_to_eps(v: torch.Tensor, x: torch.Tensor, coef: torch.Tensor, step: to
     return out
 
 
+# ---- guidance rescale (include/seer_hip.h, "guidance rescale"): the guided output scaled to the conditional row's std, per clip ----------
+RESCALE_TILE = 1024         # SEER_RESCALE_TILE: elements of a clip per workgroup of the two rescale launches
+
+
+def check_guidance_rescale(phi) -> float:
+    """the blend factor of guidance rescale: a number in [0, 1] (0: off); anything else is a ValueError"""
+    try:
+        value = float(phi)
+    except (TypeError, ValueError):
+        value = float("nan")
+    if not 0. <= value <= 1.:
+        raise ValueError(f"guidance_rescale = {phi!r}: a number in [0, 1] (0 is off, 0.7 the usual value)")
+    return value
+
+
+def cfg_rescale_workspace(clips: int, C: int, F_total: int, cond_f: int, HW: int, device) -> torch.Tensor:
+    """the float64 workspace of cfg_rescale / slot_cfg_rescale for `clips` clips of that shape (seer_cfg_rescale_ws_bytes)"""
+    nbytes = int(_lib.load().seer_cfg_rescale_ws_bytes(int(clips), int(C), int(F_total), int(cond_f), int(HW)))
+    if nbytes < 0:
+        raise ValueError(f"seer_cfg_rescale_ws_bytes({clips}, {C}, {F_total}, {cond_f}, {HW}): {nbytes}")
+    return torch.empty((nbytes // 8,), device=device, dtype=torch.float64)
+
+
+def _req_rescale(out: torch.Tensor, cond_f: int, ws: Optional[torch.Tensor], mult: Optional[torch.Tensor]):
+    """out [2 clips, C, F_total, h, w], the [uc | c] pair in place -> (clips, C, F_total, h * w, ws); a missing workspace is made"""
+    _req(out, torch.float32, "out")
+    assert out.is_contiguous() and out.dim() == 5 and out.shape[0] % 2 == 0 and out.shape[0] > 0 and 0 <= int(cond_f) < out.shape[2]
+    clips, Cc, Ft, HW = out.shape[0] // 2, out.shape[1], out.shape[2], out.shape[3] * out.shape[4]
+    if ws is None:
+        ws = cfg_rescale_workspace(clips, Cc, Ft, cond_f, HW, out.device)
+    _req(ws, torch.float64, "ws")
+    need = int(_lib.load().seer_cfg_rescale_ws_bytes(clips, Cc, Ft, int(cond_f), HW)) // 8
+    assert ws.is_contiguous() and ws.numel() >= need, f"ws: {ws.numel()} doubles, the call stores {need}"
+    if mult is not None:
+        _req(mult, torch.float32, "mult")
+        assert mult.is_contiguous() and mult.numel() == clips
+    return clips, Cc, Ft, HW, ws
+
+
+def cfg_rescale(out: torch.Tensor, *, scale: float, rescale: float, cond_f: int, ws: Optional[torch.Tensor] = None,
+                mult: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """guidance rescale of a model output, in place: both rows of every clip of out [2b (uc then c), C, F_total, h, w] become m * g over
+    the frames >= cond_f, g the CFG-combined value at `scale` and m = rescale * std(c row) / std(g) + 1 - rescale per clip (1 where
+    std(g) is 0); the update kernel behind it then finds eu == ec.  `mult` [b] receives the m.  rescale == 0 launches nothing
+    (seer_cfg_rescale)"""
+    b, Cc, Ft, HW, ws = _req_rescale(out, cond_f, ws, mult)
+    check(_lib.load().seer_cfg_rescale(_p(out), b, Cc, Ft, int(cond_f), HW, float(scale), check_guidance_rescale(rescale), _p(ws),
+                                       _p(mult), _stream()), "seer_cfg_rescale")
+    return out
+
+
+def slot_cfg_rescale(out: torch.Tensor, scale: torch.Tensor, rescale: torch.Tensor, coef: torch.Tensor, step: torch.Tensor, *,
+                     cond_f: int, ws: Optional[torch.Tensor] = None, mult: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cfg_rescale over slots (out [2 slots, ...]): slot s uses scale[s] and rescale[s], fp32 [slots] in device memory; a slot whose
+    index step[s, 1] is outside the table coef [slots, nsched, ..] or whose rescale[s] is 0 has no word written -- rows, ws, mult
+    (seer_slot_cfg_rescale)"""
+    slots, Cc, Ft, HW, ws = _req_rescale(out, cond_f, ws, mult)
+    _req(step, torch.int32, "step"); _req(rescale, torch.float32, "rescale")
+    _req_slot_tables(slots, coef, step, scale)
+    assert rescale.is_contiguous() and rescale.numel() == slots
+    check(_lib.load().seer_slot_cfg_rescale(_p(out), slots, Cc, Ft, int(cond_f), HW, _p(scale), _p(rescale), coef.shape[1], _p(step),
+                                            _p(ws), _p(mult), _stream()), "seer_slot_cfg_rescale")
+    return out
+
+
 def clamp01_(x: torch.Tensor) -> torch.Tensor:
     _req(x, torch.float32, "x")
     assert x.is_contiguous()

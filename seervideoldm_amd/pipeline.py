@@ -19,6 +19,7 @@ from typing import Iterable, Iterator, List, Optional, Tuple
 
 import torch
 
+from . import ops
 from .ddim import ddim_sample, frames_to_latents, latents_to_clip
 
 
@@ -26,9 +27,12 @@ from .ddim import ddim_sample, frames_to_latents, latents_to_clip
 def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, text_emb: torch.Tensor,
                    empty_emb: torch.Tensor, *, num_frames: int, cond_frames: int, ddim_steps: int = 30,
                    scale: float = 7.5, num_samples: int = 1, noise_generator: Optional[torch.Generator] = None,
-                   latent_generator: Optional[torch.Generator] = None) -> List[torch.Tensor]:
+                   latent_generator: Optional[torch.Generator] = None,
+                   guidance_rescale: Optional[float] = None) -> List[torch.Tensor]:
     """x0_image: [b, 3, 1, H, W] (one image, repeated over the conditioning frames like inference_img.py:166) or
-    [b, 3, cond_frames, H, W].  Returns `num_samples` clips [b, 3, num_frames - cond_frames, H, W] in [0, 1]."""
+    [b, 3, cond_frames, H, W].  Returns `num_samples` clips [b, 3, num_frames - cond_frames, H, W] in [0, 1].
+    `guidance_rescale` (None: the sampler's own) stands in for the sampler's default while these clips are sampled: ddim_sample keeps
+    the reference's signature and has no keyword to carry it."""
     dev = x0_image.device
     f1, f2 = cond_frames, num_frames - cond_frames
     if x0_image.shape[2] == 1:
@@ -42,10 +46,17 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
     uc = empty_emb.unsqueeze(1).expand(-1, c.shape[1], -1, -1).contiguous()
 
     clips = []
-    for _ in range(num_samples):
-        noise = torch.randn((b, c_l, f2, h_l, w_l), generator=noise_generator).to(dev)     # CPU draw, then moved (:179,187)
-        clips.append(ddim_sample(sampler, sunet, vae, shape=(b, c_l, f2, h_l, w_l), c=c, start_code=noise, x0_emb=x0_emb,
-                                 ddim_steps=ddim_steps, scale=scale, uc=uc))
+    own = getattr(sampler, "guidance_rescale", 0.)
+    if guidance_rescale is not None:
+        sampler.guidance_rescale = ops.check_guidance_rescale(guidance_rescale)
+    try:
+        for _ in range(num_samples):
+            noise = torch.randn((b, c_l, f2, h_l, w_l), generator=noise_generator).to(dev)     # CPU draw, then moved (:179,187)
+            clips.append(ddim_sample(sampler, sunet, vae, shape=(b, c_l, f2, h_l, w_l), c=c, start_code=noise, x0_emb=x0_emb,
+                                     ddim_steps=ddim_steps, scale=scale, uc=uc))
+    finally:
+        if guidance_rescale is not None:
+            sampler.guidance_rescale = own
     return clips
 
 
@@ -53,7 +64,8 @@ def generate_clips(sunet, fstext_model, vae, sampler, x0_image: torch.Tensor, te
 def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots: int, num_frames: int, cond_frames: int,
                    latent_generator: Optional[torch.Generator] = None, max_steps: int = 64,
                    plms: bool = False, stochastic: bool = False, editing: bool = False,
-                   dpm: bool = False, prediction_type: str = "epsilon") -> Iterator[Tuple[object, torch.Tensor]]:
+                   dpm: bool = False, prediction_type: str = "epsilon",
+                   rescale: bool = False) -> Iterator[Tuple[object, torch.Tensor]]:
     """generate_clips over a queue of requests through a SlotSampler (slots.py): `slots` clips share one captured step and a
     finished clip's slot is refilled at once.  A request is dict(x0_image [1, 3, 1 or cond_frames, H, W], text_emb [1, 77, D],
     empty_emb [1, 77, D], ddim_steps, scale, noise [1, 4, num_frames - cond_frames, H/8, W/8] (the start code), tag, and
@@ -65,7 +77,9 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     seed) and t_start; in a queue started without it those keys are a ValueError as well.  `dpm=True`
     builds it with dpm=True: a request may then name sampler = "dpmpp" and carry order, lower_order_final and discretize
     (SlotSampler.submit); a request naming "dpmpp" without it is a ValueError.  `prediction_type="v_prediction"`
-    builds it for a model fine-tuned on the velocity target: it belongs to the queue, not to a request.  The VAE encode
+    builds it for a model fine-tuned on the velocity target: it belongs to the queue, not to a request.  `rescale=True` builds it with
+    rescale=True: a request may then carry guidance_rescale (SlotSampler.submit); in a queue started without it a non-zero value is a
+    ValueError.  The VAE encode
     (drawing from `latent_generator`, in admission order) and FSText run when a request is admitted -- it is taken from the iterable
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
@@ -92,10 +106,13 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
                 sampler.append(SlotSampler(sunet, slots, shape=(c_l, f2, h_l, w_l), cond_frames=f1, context_shape=tuple(c.shape[2:]),
                                            max_steps=max_steps, device=x0_emb.device, plms=plms, stochastic=stochastic,
                                            **(dict(editing=True) if editing else {}), **(dict(dpm=True) if dpm else {}),
-                                           **(dict(prediction_type=prediction_type) if prediction_type != "epsilon" else {})))
+                                           **(dict(prediction_type=prediction_type) if prediction_type != "epsilon" else {}),
+                                           **(dict(rescale=True) if rescale else {})))
             seeded = {k: r[k] for k in ("seed", "eta", "temperature") if k in r}
             edit = {k: r[k] for k in ("mask", "known", "t_start") if r.get(k) is not None}
-            solver = {k: r[k] for k in ("order", "lower_order_final", "discretize") if k in r}
+            solver = {k: r[k] for k in ("order", "lower_order_final", "discretize", "guidance_rescale") if k in r}
+            if solver.get("guidance_rescale") and not rescale:
+                raise ValueError("guidance_rescale: a request carries it only in a queue started with rescale=True")
             if edit and not editing:
                 raise ValueError(f"{sorted(edit)}: a request carries these only in a queue started with editing=True")
             if "known" in edit:
@@ -129,7 +146,8 @@ def edit_t_enc(strength: float, entries: int) -> int:
 def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb: torch.Tensor, empty_emb: torch.Tensor, *,
                cond_frames: int, ddim_steps: int = 30, scale: float = 7.5, strength: Optional[float] = None,
                keep_mask: Optional[torch.Tensor] = None, seed, latent_generator: Optional[torch.Generator] = None,
-               invert: bool = False, source_emb: Optional[torch.Tensor] = None, source_scale: float = 1.0) -> torch.Tensor:
+               invert: bool = False, source_emb: Optional[torch.Tensor] = None, source_scale: float = 1.0,
+               guidance_rescale: Optional[float] = None) -> torch.Tensor:
     """Edit an existing clip.  `video` [b, 3, F, H, W] in [-1, 1] is VAE-encoded in one call (as evaluate_batch does; the posterior
     draw takes `latent_generator`); its first `cond_frames` latents condition the clip, the rest are the GIVEN latents.  Exactly one of
       strength   in (0, 1] (SDEdit): the given latents are noised to level t_enc = edit_t_enc(strength, schedule entries) by
@@ -142,7 +160,9 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
     guidance `source_scale` (its unconditional branch is `empty_emb` when that scale is not 1), and sampler.decode brings them back
     under `text_emb` at `scale`: the clip itself under the source prompt, a structure-preserving edit under another.  Nothing is
     drawn on this path, so `seed` may be None.  A sampler built with prediction_type="v_prediction" refuses it (NotImplementedError,
-    DDIMSampler.encode), before anything is encoded."""
+    DDIMSampler.encode), before anything is encoded.  `guidance_rescale` (None: the sampler's own) goes to every sample, encode and
+    decode call made here."""
+    gr = {} if guidance_rescale is None else dict(guidance_rescale=ops.check_guidance_rescale(guidance_rescale))
     if invert:
         if getattr(sampler, "prediction_type", "epsilon") != "epsilon":
             sampler._refuse_v_inversion()
@@ -167,18 +187,18 @@ def edit_clips(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb:
     if keep_mask is not None:
         samples, _ = sampler.sample(unet=sunet, S=ddim_steps, conditioning=c, batch_size=b, shape=given.shape[1:], x0_emb=x0_emb,
                                     verbose=False, unconditional_guidance_scale=scale, unconditional_conditioning=uc, eta=0.0,
-                                    is_3d=True, seed=seed, mask=keep_mask, x0=given)
+                                    is_3d=True, seed=seed, mask=keep_mask, x0=given, **gr)
     elif invert:
         c_src = c if source_emb is None or source_emb is text_emb else fstext_model(context=source_emb)
         uc_src = None if source_scale == 1.0 else empty_emb.unsqueeze(1).expand(-1, c_src.shape[1], -1, -1).contiguous()
         noised, _ = sampler.encode(sunet, given, c_src, t_enc, unconditional_guidance_scale=source_scale,
-                                   unconditional_conditioning=uc_src, x0_emb=x0_emb)
+                                   unconditional_conditioning=uc_src, x0_emb=x0_emb, **gr)
         samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,
-                                 x0_emb=x0_emb)
+                                 x0_emb=x0_emb, **gr)
     else:
         noised = sampler.stochastic_encode(given, t_enc, seed=seed)
         samples = sampler.decode(sunet, noised, c, t_enc, unconditional_guidance_scale=scale, unconditional_conditioning=uc,
-                                 x0_emb=x0_emb, seed=seed)
+                                 x0_emb=x0_emb, seed=seed, **gr)
     return latents_to_clip(vae, samples)
 
 
@@ -197,16 +217,18 @@ def concat_all_gather(t: torch.Tensor, process_group=None) -> torch.Tensor:
 @torch.no_grad()
 def evaluate_batch(sunet, fstext_model, vae, sampler, video: torch.Tensor, text_emb: torch.Tensor, empty_emb: torch.Tensor, *,
                    cond_frames: int, ddim_steps: int = 30, scale: float = 7.5, process_group=None, gather: bool = True,
-                   noise_generator: Optional[torch.Generator] = None, latent_generator: Optional[torch.Generator] = None):
+                   noise_generator: Optional[torch.Generator] = None, latent_generator: Optional[torch.Generator] = None,
+                   guidance_rescale: Optional[float] = None):
     """The body of eval.py's validation loop (eval.py:186-231) for THIS rank's batch: the first `cond_frames` frames of
     `video` [b, 3, F, H, W] in [-1, 1] condition the rest; returns (pred, gt) = ([conditioning frames | sampled frames],
     ground truth), both [N*b, 3, F, H, W] in [0, 1] gathered over the ranks of `process_group` (None = every rank, as
     accelerator.gather does) in rank order.  N GPUs evaluate N batches with no communication until this final gather (the
-    samples are the independent units of the path); gather=False returns this rank's batch only."""
+    samples are the independent units of the path); gather=False returns this rank's batch only.  `guidance_rescale` (None: the
+    sampler's own) is generate_clips' keyword."""
     x0 = video[:, :, :cond_frames]
     clip = generate_clips(sunet, fstext_model, vae, sampler, x0, text_emb, empty_emb, num_frames=video.shape[2],
                           cond_frames=cond_frames, ddim_steps=ddim_steps, scale=scale, num_samples=1,
-                          noise_generator=noise_generator, latent_generator=latent_generator)[0]
+                          noise_generator=noise_generator, latent_generator=latent_generator, guidance_rescale=guidance_rescale)[0]
     pred = torch.cat([(x0.float() + 1.0) / 2.0, clip], dim=2)
     gt = (video.float() + 1.0) / 2.0
     if not gather:

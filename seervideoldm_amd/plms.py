@@ -20,6 +20,9 @@ activations in the engine's small graph cache for one step per sample.
 The reference draws noise_like(x.shape) in every get_x_prev_and_pred_x0 call, also at sigma = 0 -- twice on the first step, once
 on every later one (plms.py:212); those draws are kept (consume_rng_when_deterministic) so a seeded run leaves the device RNG
 stream where the reference leaves it.
+
+`guidance_rescale` (DDIMSampler's keyword; per call on sample and p_sample_plms) rescales the guided output of EVERY evaluation, both
+of the first step included, in front of the combination: the history then holds rescaled eps.
 """
 from __future__ import annotations
 
@@ -49,17 +52,19 @@ class PLMSSampler(DDIMSampler):
         return self.plms_sampling(unet, conditioning, size, x0_emb=x0_emb, is_3d=is_3d, callback=callback,
                                   img_callback=img_callback, cond_frames=cond_frames, temperature=temperature, x_T=x_T,
                                   log_every_t=log_every_t, unconditional_guidance_scale=unconditional_guidance_scale,
-                                  unconditional_conditioning=unconditional_conditioning)
+                                  unconditional_conditioning=unconditional_conditioning,
+                                  guidance_rescale=kwargs.get("guidance_rescale"))
 
     @torch.no_grad()
     def plms_sampling(self, unet, cond, shape, is_3d=True, x0_emb=None, cond_frames=0, x_T=None, callback=None,
                       img_callback=None, log_every_t=100, temperature=1., unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, **kwargs):
+                      unconditional_conditioning=None, guidance_rescale=None, **kwargs):
         """plms.py:114-170 over the Seer model call"""
         b = shape[0]
         img, x0_emb = self._chain_start(unet, shape, x_T, x0_emb)
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         plain = uc is None or scale == 1.
+        phi = self._rescale_factor(unet, guidance_rescale, plain)
         # a chain whose later steps are captured (batched CFG or none, and a model whose steps may be captured at all) runs the two
         # evaluations of its first step launch by launch, not as a UNet graph of their own
         graph = ((plain or uc.shape[2] == cond.shape[2]) and not self._capture_refused
@@ -72,7 +77,7 @@ class PLMSSampler(DDIMSampler):
             first, out = not old_eps, None
             if graph and not first:
                 out = self._plms_graph_step(unet, img, cond, None if plain else uc, index, x0_emb, 0 if plain else cond_frames,
-                                            scale, old_eps, restart=not chained)
+                                            scale, old_eps, restart=not chained, phi=phi)
             chained = out is not None
             if out is None:
                 if first and graph:
@@ -82,7 +87,7 @@ class PLMSSampler(DDIMSampler):
                     out = self.p_sample_plms(unet, img, cond, self._t_table[index].expand(b), index, x0_emb=x0_emb,
                                              cond_frames=cond_frames, temperature=temperature, unconditional_guidance_scale=scale,
                                              unconditional_conditioning=uc, old_eps=old_eps,
-                                             t_next=self._t_table[max(index - 1, 0)].expand(b))
+                                             t_next=self._t_table[max(index - 1, 0)].expand(b), guidance_rescale=phi)
                 finally:
                     if first and graph:
                         unet.use_graph = True
@@ -96,7 +101,7 @@ class PLMSSampler(DDIMSampler):
     def p_sample_plms(self, unet, x, c, t, index, is_3d=True, x0_emb=None, cond_frames=0, repeat_noise=False,
                       use_original_steps=False, quantize_denoised=False, temperature=1., noise_dropout=0.,
                       score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                      unconditional_conditioning=None, old_eps=None, t_next=None):
+                      unconditional_conditioning=None, old_eps=None, t_next=None, guidance_rescale=None):
         """plms.py:172-236 -> (x_prev, pred_x0, e_t); e_t is this step's (first) CFG-combined eps, the one old_eps keeps.
         Launch by launch (seer_cfg_plms_step; for a v-model seer_v_to_eps in front of each)."""
         if use_original_steps or noise_dropout > 0. or repeat_noise or quantize_denoised or score_corrector is not None:
@@ -105,24 +110,25 @@ class PLMSSampler(DDIMSampler):
         uc, scale = unconditional_conditioning, unconditional_guidance_scale
         old_eps = [] if old_eps is None else old_eps
         history = [e.to(torch.float32).contiguous() for e in reversed(old_eps[-3:])]       # newest first
+        phi = self._rescale_factor(unet, guidance_rescale, uc is None or scale == 1.)
         eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
         kw = dict(cfg=cfg, scale=scale, cond_f=cond_f)
+        as_eps = lambda out, at, row: self._as_eps(self._rescaled(out, scale, cond_f, phi), at, row, cond_f)
         if not history:
             # pseudo improved Euler: a provisional DDIM step to t_next, a second evaluation there, the mean of the two eps
             if t_next is None:
                 raise ValueError("the first PLMS step (old_eps empty) needs t_next")
             self._consume_rng(x)
-            x_prov, _, e_t = self.ops.cfg_plms_step(self._as_eps(eps, x, index, cond_f), x, self.ddim_coef, index, 0,
-                                                    want_pred_x0=False, **kw)
+            x_prov, _, e_t = self.ops.cfg_plms_step(as_eps(eps, x, index), x, self.ddim_coef, index, 0, want_pred_x0=False, **kw)
             eps2, _, _ = self._model_output(unet, x_prov, c, t_next, x0_emb, cond_frames, uc, scale)
             self._consume_rng(x)
             # (a v-model's second evaluation was made at x_prov and at t_next = the timestep of entry max(index - 1, 0): that row)
-            x_prev, pred_x0, _ = self.ops.cfg_plms_step(self._as_eps(eps2, x_prov, max(int(index) - 1, 0), cond_f), x, self.ddim_coef,
-                                                        index, 1, history=[e_t], **kw)
+            x_prev, pred_x0, _ = self.ops.cfg_plms_step(as_eps(eps2, x_prov, max(int(index) - 1, 0)), x, self.ddim_coef, index, 1,
+                                                        history=[e_t], **kw)
         else:
             self._consume_rng(x)
-            x_prev, pred_x0, e_t = self.ops.cfg_plms_step(self._as_eps(eps, x, index, cond_f), x, self.ddim_coef, index,
-                                                          len(history) + 1, history=history, **kw)
+            x_prev, pred_x0, e_t = self.ops.cfg_plms_step(as_eps(eps, x, index), x, self.ddim_coef, index, len(history) + 1,
+                                                          history=history, **kw)
         return x_prev, pred_x0, e_t
 
     def _consume_rng(self, x):
@@ -135,11 +141,11 @@ class PLMSSampler(DDIMSampler):
     def ddim_sampling(self, *args, **kwargs):
         raise NotImplementedError("PLMSSampler samples with plms_sampling")
 
-    def _plms_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, old_eps, restart):
+    def _plms_graph_step(self, unet, x, c, uc, index, x0_emb, cond_frames, scale, old_eps, restart, phi=0.):
         """one later PLMS step as a single replay; `restart` (or a chain the graph did not run last) seeds the ring from old_eps and
         writes the step index and the ring state of that index: the only host writes of a chain.  Returns None when the step
         cannot be captured."""
-        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "plms")
+        G = self._step_graph(unet, x, c, uc, x0_emb, cond_frames, scale, "plms", phi=phi)
         if G is None:
             return None
         if restart or G["expect"] != index or G["ring_host"] is None:

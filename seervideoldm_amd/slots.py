@@ -51,6 +51,12 @@ is the velocity v, and the step gains one launch between the model and the updat
 with the slot's own coefficient row -- for a PLMS clip's second evaluation the row below and the provisional latent it was made at.
 It holds in every mode above, under a key of its own, and the promise reads against the solo sampler built with the same keyword.
 
+With `rescale=True` a request may carry guidance_rescale = phi in [0, 1] (submit): the step gains one node, seer_slot_cfg_rescale (two
+launches), between the model and the v-conversion, which scales a slot's guided output to the std of its conditional row and writes it
+to both of the slot's rows (DESIGN.md "Guidance rescale").  Each slot has its phi in device memory, like its scale; a slot with phi = 0
+is not touched by the node, so rescaled and plain clips share a queue and a plain clip has the bits it has in a queue built without the
+keyword.  It goes with every mode above, under a key of its own; the promise reads against the solo sampler's sample(guidance_rescale=phi).
+
 Out of scope: PLMS with noise or with a mask, DPM-Solver++ with noise, with a mask or from a start level, PLMS and DPM-Solver++ in one
 queue, slots of different clip shapes, frame-sharded models, a per-slot K/V refresh, resizing without a new
 capture.
@@ -84,11 +90,13 @@ class SlotSampler:
     `lower_order_final`, `discretize`): the step's last kernel then carries a sampler per slot, DDIM or DPM-Solver++, over two more
     static buffers, under a key of its own; it excludes plms, stochastic and editing (the solo DPMSolverSampler has no seeded or masked
     form for a slot to be bit-equal to).  `prediction_type` "epsilon" (the default: nothing changes) or "v_prediction": what the
-    UNet's output is (train.py:371-376; anything else is its ValueError), in every mode."""
+    UNet's output is (train.py:371-376; anything else is its ValueError), in every mode.  `rescale=True` lets a request carry
+    guidance_rescale (submit): the step then has the rescale node behind the model, over a per-slot factor and a workspace, under a key
+    of its own; it goes with every other keyword."""
 
     def __init__(self, unet, slots: int, shape, cond_frames: int, context_shape, max_steps: int = 64, device=None, ops=hip_ops,
                  model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False,
-                 dpm: bool = False, prediction_type: str = "epsilon"):
+                 dpm: bool = False, prediction_type: str = "epsilon", rescale: bool = False):
         self.prediction_type = hip_ops.check_prediction_type(prediction_type)
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
@@ -162,6 +170,10 @@ class SlotSampler:
         if self.stochastic:
             self._temp = torch.ones((n,), device=dev, dtype=f32)
             self._update = ("slot_cfg_ddim_step_rng", (self._seeds, self._temp))
+        self.rescale = bool(rescale)
+        if self.rescale:
+            self._phi = torch.zeros((n,), device=dev, dtype=f32)                      # 0: the rescale node leaves the slot alone
+            self._rescale_ws = self.ops.cfg_rescale_workspace(n, C, f1 + Fp, f1, h * w, dev)
         self._left = [0] * n                          # steps a slot still has to run; 0 = free
         self._sched = DDIMSampler(dev)
         self._tables: Dict[Tuple[int, float], Tuple[torch.Tensor, torch.Tensor]] = {}
@@ -206,7 +218,7 @@ class SlotSampler:
     @torch.no_grad()
     def submit(self, x_T, x0_emb, c, uc, S: int, scale: float, eta: float = 0., method: str = "ddim", seed: Optional[int] = None,
                temperature: float = 1., mask=None, x0=None, t_start: Optional[int] = None, order: int = 2,
-               lower_order_final: bool = True, discretize: str = "uniform") -> int:
+               lower_order_final: bool = True, discretize: str = "uniform", guidance_rescale: float = 0.) -> int:
         """Admit one clip into a free slot and return the slot.  x_T [1 or none, C, F_pred, h, w] is the start code, x0_emb
         [.., C, f1, h, w] the conditioning latents (None when f1 == 0), c / uc [.., f1 + F_pred, L, D] the text context and the
         empty-prompt context, S the number of DDIM steps (DDIMSampler.make_schedule(S): the stride rule can give S + 1 entries),
@@ -228,10 +240,16 @@ class SlotSampler:
         have fewer than S entries) -- DPMSolverSampler's constructor keywords, with its defaults; the clip's tables are that sampler's
         make_schedule(S) and it occupies its slot for one step per entry.  The three keywords belong to "dpmpp": with another method
         anything but their defaults is a ValueError, as is "dpmpp" on a sampler built without dpm=True.
+        A sampler built with rescale=True also takes guidance_rescale, a number in [0, 1]: the clip's guided model output is rescaled to
+        the std of its conditional row and blended by that factor in every evaluation (0: the clip is a plain one).  Without
+        rescale=True a non-zero value is a ValueError, as is a value outside [0, 1] anywhere.
         Raises RuntimeError when no slot is free, ValueError for a schedule longer than max_steps, a shape that is not the
         constructor's, eta != 0, a frame-sharded model, an unknown method, and "plms" or "dpmpp" on a sampler built without it."""
         C, Fp, h, w = self.shape
         F, (L, D) = self.f1 + Fp, self.context_shape
+        phi = hip_ops.check_guidance_rescale(guidance_rescale)
+        if phi != 0. and not self.rescale:
+            raise ValueError("guidance_rescale needs a sampler built with rescale=True")
         if not self.editing and (mask is not None or x0 is not None or t_start is not None):
             raise ValueError("mask / x0 / t_start need a sampler built with editing=True")
         if (mask is None) != (x0 is None):
@@ -292,6 +310,8 @@ class SlotSampler:
         self._coef[s, :n].copy_(coef)
         self._ttab[s, :n].copy_(ttab)
         self._scale[s:s + 1].fill_(float(scale))
+        if self.rescale:
+            self._phi[s:s + 1].fill_(phi)
         if x_T is None:                              # the start code of a seeded clip: stream 0 of its seed
             self.ops.philox_normal(int(seed), hip_ops.PHILOX_STREAM_START, 0, self._x[s].numel(), out=self._x[s])
         else:
@@ -343,8 +363,9 @@ class SlotSampler:
 
     def run(self, requests: Iterable[dict]) -> Iterator[Tuple[object, torch.Tensor]]:
         """Generator over an iterable of dict(x_T=, x0_emb=, c=, uc=, S=, scale=, tag=[, method=][, eta=, seed=, temperature=]
-        [, mask=, x0=, t_start=][, order=, lower_order_final=, discretize=]): fills free slots in request order (a request is taken
-        from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in finishing order."""
+        [, mask=, x0=, t_start=][, order=, lower_order_final=, discretize=][, guidance_rescale=]): fills free slots in request order
+        (a request is taken from the iterable only when a slot is free for it), steps, and yields (tag, latent) as clips finish, in
+        finishing order."""
         it, tags, more = iter(requests), {}, True
         while True:
             while more and self.free_slots():
@@ -365,6 +386,8 @@ class SlotSampler:
         for name, args in self._front:
             getattr(self.ops, name)(*args)
         eps = model()
+        if self.rescale:                             # both rows of a slot with phi > 0 become its rescaled guided output, in place
+            self.ops.slot_cfg_rescale(eps, self._scale, self._phi, self._coef, self._step, cond_f=self.f1, ws=self._rescale_ws)
         if self.prediction_type != "epsilon":        # v -> eps, in place on the model's output, per slot
             phases = dict(state=self._state, x_prov=self._xprov) if self.plms else {}
             self.ops.slot_v_to_eps(eps, self._x, self._coef, self._step, cond_f=self.f1, out=eps, **phases)
@@ -388,7 +411,7 @@ class SlotSampler:
         G = None
         if not self._capture_refused and capture_engine(unet, self.ops, self.device) is not None:
             key = (self._kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv,
-                   *(() if self.prediction_type == "epsilon" else (self.prediction_type,)))
+                   *(() if self.prediction_type == "epsilon" else (self.prediction_type,)), *(("rescale",) if self.rescale else ()))
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)
