@@ -942,6 +942,34 @@ int seer_zero_insert2x_bf16(const void* d, int32_t n_img, int32_t H, int32_t W, 
  * dpred fp32 [B, C, F_total, HW] = d loss / d pred (zero on the conditioning frames).  workspace: 1024 floats. */
 int seer_mse_loss_grad(const float* pred, const float* target, int32_t B, int32_t C, int32_t F_total, int32_t cond_f,
                        int32_t HW, float* loss, float* dpred, float* workspace, void* stream);
+/* The same loss with Min-SNR-gamma weighting (Hang et al., "Efficient Diffusion Training via Min-SNR Weighting Strategy", ICCV 2023;
+ * `--snr_gamma` of the diffusers training scripts): sample b carries the weight w_b of its timestep, inside the loss and inside dpred.
+ *   pred, dpred     fp32 [B, C, F_total, HW];   target fp32 [B, C, F_total - cond_f, HW]
+ *   timesteps       int64 [B], alphas_cumprod fp32 [T], BOTH IN DEVICE MEMORY (a captured step stays valid when the timesteps change);
+ *                   a timestep outside [0, T) is clamped into the table, as in seer_velocity_target.  The table's values are the
+ *                   caller's and are not checked: they lie in [0, 1].
+ *   a = alphas_cumprod[t_b] and snr_gamma widened to double; each operation below one rounded double operation; w_b rounded once to fp32:
+ *     v_prediction == 0 (eps-model):  w_b = fmin(1.0, snr_gamma * (1.0 - a) / a)     = min(SNR, gamma) / SNR;        a = 0: 1,  a = 1: 0
+ *     v_prediction == 1 (v-model):    w_b = fmin(a, snr_gamma * (1.0 - a))           = min(SNR, gamma) / (SNR + 1);  a = 0: 0,  a = 1: 0
+ *   weights[b]      = w_b                                                            (the bits of that float64 expression cast to fp32)
+ *   sample_loss[b]  = mean over the n_s = C (F_total - cond_f) HW predicted elements of sample b of (pred - target)^2, UNweighted
+ *   loss            = (1 / B) sum_b w_b sample_loss_b
+ *   dpred[i]        = 2.0f * d * inv_n * w_b, the products in this order, d = pred - target and inv_n = (float)(1.0 / (B n_s)): the
+ *                     expression of seer_mse_loss_grad times w_b (the same bits where w_b == 1); +0.0f on the conditioning frames.
+ * Reproducible, no atomics.  Launch one, grid (nblk, B), nblk <= SEER_SNR_MSE_BLOCKS: a block strides over its sample, adds
+ * (double)(d * d) (the fp32 product, widened), tree-reduces in LDS in a fixed order and stores one double at workspace[b * nblk + blk].
+ * Launch two adds a sample's partials in index order (sum_b), writes sample_loss[b] = (float)(sum_b * (1.0 / n_s)), adds
+ * (double)w_b * (sum_b / n_s) over b = 0 .. B-1 in order and writes loss = (float)(total / B).
+ *   workspace       B * SEER_SNR_MSE_BLOCKS doubles, 8-byte aligned; it need not be zeroed.
+ * 16-byte accesses when HW % 4 == 0 and pred, target and dpred are 16-byte aligned, a scalar path otherwise.
+ * SEER_EINVAL, nothing launched: a NULL pointer; T, B, C, F_total or HW not positive; cond_f outside 0 .. F_total - 1; B above 65535 (the
+ * launch grid) or more than 2^46 elements; snr_gamma not finite or not positive; v_prediction outside {0, 1}; a float pointer not
+ * 4-byte aligned, timesteps or workspace not 8-byte aligned; dpred overlapping pred or target, or any two of the five outputs
+ * (loss, sample_loss, weights, dpred, workspace) overlapping. */
+#define SEER_SNR_MSE_BLOCKS 64
+int seer_snr_mse_loss_grad(const float* pred, const float* target, const int64_t* timesteps, const float* alphas_cumprod, int32_t T,
+                           float snr_gamma, int32_t v_prediction, int32_t B, int32_t C, int32_t F_total, int32_t cond_f, int32_t HW,
+                           float* loss, float* sample_loss, float* weights, float* dpred, double* workspace, void* stream);
 /* `--text_loss` of train.py:346-347 (the FSTextTransformer initialisation stage): loss = mean_{b,l,c} (mean_f y - target)^2
  * with y bf16 [b, F, LC] (FSTextTransformer output), target fp32 [b, LC] (the CLIP sequence); its gradient is ADDED to dy
  * (bf16 [b, F, LC], the gradient arriving from the UNet).  workspace: 1024 floats. */

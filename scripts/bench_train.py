@@ -1,6 +1,7 @@
 """Time one fine-tuning step (BASELINE config 5: b=1, F=12, cond_frames=2, 32x32 latent, full-size SeerUNet + 8-layer
 FSTextTransformer, random-init weights, synthetic latents) on one MI355X: forward+loss+backward and the optimizer, with HIP
-events on the current stream.  Usage: python scripts/bench_train.py [steps] [frames] [latent] [batch] [--eager]"""
+events on the current stream.  Usage: python scripts/bench_train.py [steps] [frames] [latent] [batch] [--eager] [--snr-gamma G]
+--snr-gamma G: SeerTrainer(snr_gamma=G), Min-SNR-gamma loss weighting (seer_snr_mse_loss_grad in the place of seer_mse_loss_grad)."""
 import json
 import sys
 import time
@@ -23,11 +24,12 @@ def build(device, cfg=None, fs_layers=8):
     return unet, fst
 
 
-def time_train(device, steps=5, warmup=2, Fr=12, cond=2, lat=32, b=1, use_graph=True, unet=None, fst=None, process_group=None):
+def time_train(device, steps=5, warmup=2, Fr=12, cond=2, lat=32, b=1, use_graph=True, unet=None, fst=None, process_group=None,
+               snr_gamma=None):
     if unet is None or fst is None:
         unet, fst = build(device)
     fst.set_numframe(Fr)
-    tr = SeerTrainer(unet, fst, lr=1e-5, max_grad_norm=0.3, process_group=process_group)
+    tr = SeerTrainer(unet, fst, lr=1e-5, max_grad_norm=0.3, process_group=process_group, snr_gamma=snr_gamma)
     g = torch.Generator().manual_seed(0)
     x = torch.randn((b, 4, Fr, lat, lat), generator=g).to(device)
     noise = torch.randn((b, 4, Fr - cond, lat, lat), generator=g).to(device)
@@ -55,16 +57,22 @@ def time_train(device, steps=5, warmup=2, Fr=12, cond=2, lat=32, b=1, use_graph=
             "hipgraph": bool(use_graph and not getattr(tr, "_graph_broken", False)), "fwd_bwd_ms": sum(fb) / len(fb), "optimizer_ms": sum(opt) / len(opt), "host_enqueue_ms": sum(host[warmup:]) / len(host[warmup:]),
             "ms_per_step": (sum(fb) + sum(opt)) / len(fb), "steps": steps, "trainable_params": int(n_u + n_f),
             "loss_first": losses[0], "loss_last": losses[-1],
-            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30}
+            "peak_mem_gb": torch.cuda.max_memory_allocated() / 2 ** 30, **({} if snr_gamma is None else {"snr_gamma": snr_gamma})}
 
 
 if __name__ == "__main__":
-    pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+    argv, snr_gamma = sys.argv[1:], None
+    for i, a in enumerate(argv):
+        if a == "--snr-gamma" or a.startswith("--snr-gamma="):
+            snr_gamma = float(a.split("=", 1)[1]) if "=" in a else float(argv[i + 1])
+            argv = argv[:i] + argv[i + (1 if "=" in a else 2):]
+            break
+    pos = [a for a in argv if not a.startswith("--")]
     steps = int(pos[0]) if len(pos) > 0 else 5
     Fr = int(pos[1]) if len(pos) > 1 else 12
     lat = int(pos[2]) if len(pos) > 2 else 32
     b = int(pos[3]) if len(pos) > 3 else 1
     t0 = time.time()
-    r = time_train(torch.device("cuda:0"), steps=steps, Fr=Fr, lat=lat, b=b, use_graph="--eager" not in sys.argv)
+    r = time_train(torch.device("cuda:0"), steps=steps, Fr=Fr, lat=lat, b=b, use_graph="--eager" not in argv, snr_gamma=snr_gamma)
     r["wall_s"] = time.time() - t0
     print(json.dumps(r))

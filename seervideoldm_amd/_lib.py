@@ -207,6 +207,8 @@ SIGNATURES = {
     "seer_sumpool2x_bf16": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "seer_zero_insert2x_bf16": ([_vp, _i32, _i32, _i32, _i32, _vp, _vp], C.c_int),
     "seer_mse_loss_grad": ([_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp], C.c_int),
+    "seer_snr_mse_loss_grad": ([_vp, _vp, _vp, _vp, _i32, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+                               C.c_int),
     "seer_text_loss_grad": ([_vp, _vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp], C.c_int),
     "seer_conv_out_bwd": ([_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp], C.c_int),
     "seer_axpby_f32": ([_vp, _vp, _f32, _f32, _i64, _vp], C.c_int),

@@ -714,6 +714,112 @@ __global__ void sum_partials_kernel(const float* __restrict__ partial, int n, fl
     }
 }
 
+// Min-SNR-gamma weighted MSE (seer_snr_mse_loss_grad): sample b of the batch carries the weight w_b = min(SNR, gamma) / SNR for an
+// eps-model, min(SNR, gamma) / (SNR + 1) for a v-model, SNR = a / (1 - a) at a = alphas_cumprod[timesteps[b]].  Both are written
+// without SNR itself -- fmin(1, gamma (1 - a) / a) and fmin(a, gamma (1 - a)) --, so neither end of the table (a = 0: SNR = 0,
+// a = 1: SNR = inf) is a special case.  Evaluated in double from the fp32 a and gamma, every step one correctly rounded operation
+// and no add behind a multiply (nothing to contract), rounded once to fp32: the bits of the same numpy float64 expression.
+__device__ __forceinline__ float snr_weight(const int64_t* __restrict__ ts, const float* __restrict__ acp, int T, int b, float gamma,
+                                            int v_prediction) {
+    int64_t t = ts[b];
+    t = t < 0 ? 0 : (t >= T ? T - 1 : t);                            // the clamp of velocity_target_kernel
+    const double a = (double)acp[t], g = (double)gamma;
+    const double w = v_prediction ? fmin(a, g * (1.0 - a)) : fmin(1.0, g * (1.0 - a) / a);
+    return (float)w;
+}
+
+// launch one, grid (nblk, B): block (blk, b) strides over the C * F_total * HW elements of sample b, V = 4 consecutive positions of one
+// (c, f) row per thread and trip (16-byte accesses; HW % 4 == 0, bases 16-byte aligned) or V = 1.  dpred = 2 d inv_n w_b, the products
+// in the order of mse_kernel, +0 on the conditioning frames; the squares are rounded fp32 products added as doubles, tree-reduced in
+// LDS in a fixed order: one double per block at partial[b * nblk + blk].  No atomics.
+template <int V>
+__global__ void __launch_bounds__(256) snr_mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                      const int64_t* __restrict__ ts, const float* __restrict__ acp, int T,
+                                                      float gamma, int v_prediction, int C, int F_total, int cond_f, int HW,
+                                                      float inv_n, float* __restrict__ dpred, double* __restrict__ partial) {
+    const int b = blockIdx.y;
+    const float w = snr_weight(ts, acp, T, b, gamma, v_prediction);
+    const int64_t per = (int64_t)C * F_total * HW;                    // elements of one sample of pred
+    const int64_t per_v = per / V;
+    const int f2 = F_total - cond_f;
+    const float* p = pred + (int64_t)b * per;
+    float* g = dpred + (int64_t)b * per;
+    const float* tg = target + (int64_t)b * C * f2 * HW;
+    double s = 0.0;
+    for (int64_t iv = (int64_t)blockIdx.x * 256 + threadIdx.x; iv < per_v; iv += (int64_t)gridDim.x * 256) {
+        const int64_t i = iv * V;
+        const int hw = (int)(i % HW);
+        const int64_t r = i / HW;
+        const int f = (int)(r % F_total);
+        const int64_t c = r / F_total;
+        if constexpr (V == 4) {
+            f32x4 o = {0.f, 0.f, 0.f, 0.f};
+            if (f >= cond_f) {
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
+                const f32x4 tv = *reinterpret_cast<const f32x4*>(tg + (c * f2 + (f - cond_f)) * HW + hw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = pv[k] - tv[k];
+                    const float q = d * d;
+                    s += (double)q;
+                    o[k] = 2.0f * d * inv_n * w;
+                }
+            }
+            *reinterpret_cast<f32x4*>(g + i) = o;
+        } else {
+            float o = 0.f;
+            if (f >= cond_f) {
+                const float d = p[i] - tg[(c * f2 + (f - cond_f)) * HW + hw];
+                const float q = d * d;
+                s += (double)q;
+                o = 2.0f * d * inv_n * w;
+            }
+            g[i] = o;
+        }
+    }
+    __shared__ double red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[(int64_t)b * gridDim.x + blockIdx.x] = red[0];
+}
+
+// launch two, one block: per chunk of 256 samples, thread i adds the nblk partials of its sample in index order, writes sample_loss[b]
+// and weights[b] and puts w_b * (sum_b / n_s) into LDS; thread 0 adds the chunk's terms in order to its running total.  Each
+// quotient, product and sum is one rounded double operation (no contraction): the loss is a function of the inputs only.
+__global__ void __launch_bounds__(256) snr_mse_final_kernel(const double* __restrict__ partial, int nblk, int B, double n_s,
+                                                            const int64_t* __restrict__ ts, const float* __restrict__ acp, int T,
+                                                            float gamma, int v_prediction, float* __restrict__ loss,
+                                                            float* __restrict__ sample_loss, float* __restrict__ weights) {
+#pragma clang fp contract(off)
+    __shared__ double term[256];
+    const double inv_ns = 1.0 / n_s;
+    double total = 0.0;                              // thread 0's
+    for (int b0 = 0; b0 < B; b0 += 256) {            // block-uniform trips
+        const int b = b0 + (int)threadIdx.x;
+        if (b < B) {
+            const double* row = partial + (int64_t)b * nblk;
+            double s = 0.0;
+            for (int k = 0; k < nblk; ++k) s += row[k];
+            const float w = snr_weight(ts, acp, T, b, gamma, v_prediction);
+            sample_loss[b] = (float)(s * inv_ns);
+            weights[b] = w;
+            const double q = s / n_s;
+            term[threadIdx.x] = (double)w * q;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = B - b0 < 256 ? B - b0 : 256;
+            for (int i = 0; i < n; ++i) total += term[i];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = (float)(total / (double)B);
+}
+
 // conv_out backward (input gradient only; conv_out is frozen): dx[b,f,y,x,ci] = sum_{co,ky,kx} dpred[b,co,f,y+1-ky,x+1-kx]
 // * w[co,ci,ky,kx].  Wt fp32 [Cout][3][3][C0] (the direct conv_out layout).  One block per (image row), weights in LDS.
 template <int COUT>
@@ -1275,7 +1381,52 @@ extern "C" int seer_mse_loss_grad(const float* pred, const float* target, int32_
     return SEER_OK;
 }
 
-namespace { std::once_flag g_conv_out_bwd_lds_once; }      // dynamic-LDS opt-in of conv_out_bwd_kernel (no function-local statics)
+extern "C" int seer_snr_mse_loss_grad(const float* pred, const float* target, const int64_t* timesteps, const float* alphas_cumprod,
+                                      int32_t T, float snr_gamma, int32_t v_prediction, int32_t B, int32_t C, int32_t F_total,
+                                      int32_t cond_f, int32_t HW, float* loss, float* sample_loss, float* weights, float* dpred,
+                                      double* workspace, void* stream) {
+    if (!pred || !target || !timesteps || !alphas_cumprod || !loss || !sample_loss || !weights || !dpred || !workspace) return SEER_EINVAL;
+    if (T <= 0 || B <= 0 || B > 65535 || C <= 0 || F_total <= 0 || HW <= 0 || cond_f < 0 || cond_f >= F_total) return SEER_EINVAL;   // B: grid y
+    if (!(snr_gamma > 0.f) || !(snr_gamma < __builtin_huge_valf())) return SEER_EINVAL;              // NaN fails both comparisons
+    if (v_prediction != 0 && v_prediction != 1) return SEER_EINVAL;
+    const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    const uintptr_t floats = addr(pred) | addr(target) | addr(alphas_cumprod) | addr(loss) | addr(sample_loss) | addr(weights) | addr(dpred);
+    if ((floats & 3) || ((addr(timesteps) | addr(workspace)) & 7)) return SEER_EINVAL;
+    const double per_d = (double)C * F_total * HW;
+    if (per_d * B > 0x1p46) return SEER_EINVAL;                       // every byte range below stays far inside 64 bits
+    const int64_t per = (int64_t)C * F_total * HW, n_s = (int64_t)C * (F_total - cond_f) * HW;
+    // no output may overlap another output, and dpred neither pred nor target (a block reads elements that another one writes)
+    struct Range { uintptr_t lo, hi; };
+    const Range outs[5] = {{addr(dpred), addr(dpred) + (uintptr_t)B * per * 4}, {addr(loss), addr(loss) + 4},
+                           {addr(sample_loss), addr(sample_loss) + (uintptr_t)B * 4}, {addr(weights), addr(weights) + (uintptr_t)B * 4},
+                           {addr(workspace), addr(workspace) + (uintptr_t)B * SEER_SNR_MSE_BLOCKS * 8}};
+    const Range ins[2] = {{addr(pred), addr(pred) + (uintptr_t)B * per * 4}, {addr(target), addr(target) + (uintptr_t)B * n_s * 4}};
+    const auto overlap = [](const Range& x, const Range& y) { return x.lo < y.hi && y.lo < x.hi; };
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (overlap(outs[i], outs[j])) return SEER_EINVAL;
+    if (overlap(outs[0], ins[0]) || overlap(outs[0], ins[1])) return SEER_EINVAL;
+    const bool vec = HW % 4 == 0 && ((addr(pred) | addr(target) | addr(dpred)) & 15) == 0;   // rows start a multiple of HW floats behind a base
+    const int64_t per_v = vec ? per / 4 : per;
+    int64_t nblk = (per_v + 255) / 256;
+    if (nblk > SEER_SNR_MSE_BLOCKS) nblk = SEER_SNR_MSE_BLOCKS;
+    const float inv_n = (float)(1.0 / ((double)B * (double)n_s));       // the inv_n of seer_mse_loss_grad
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)nblk, (unsigned)B);
+    if (vec)
+        hipLaunchKernelGGL(snr_mse_kernel<4>, grid, dim3(256), 0, st, pred, target, timesteps, alphas_cumprod, T, snr_gamma, v_prediction,
+                           C, F_total, cond_f, HW, inv_n, dpred, workspace);
+    else
+        hipLaunchKernelGGL(snr_mse_kernel<1>, grid, dim3(256), 0, st, pred, target, timesteps, alphas_cumprod, T, snr_gamma, v_prediction,
+                           C, F_total, cond_f, HW, inv_n, dpred, workspace);
+    SEER_LAUNCH_CHECK();
+    hipLaunchKernelGGL(snr_mse_final_kernel, dim3(1), dim3(256), 0, st, workspace, (int)nblk, B, (double)n_s, timesteps, alphas_cumprod, T,
+                       snr_gamma, v_prediction, loss, sample_loss, weights);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+namespace { std::once_flag g_conv_out_bwd_lds_once; }     // dynamic-LDS opt-in of conv_out_bwd_kernel (no function-local statics)
 
 extern "C" int seer_conv_out_bwd(const float* dpred, int32_t B, int32_t C0, int32_t F, int32_t H, int32_t W_, const float* Wt,
                                  int32_t Cout, void* dx, void* stream) {

@@ -296,6 +296,40 @@ def mse_loss_grad(pred: torch.Tensor, target: torch.Tensor, cond_f: int) -> Tupl
     return loss, dpred
 
 
+SNR_MSE_BLOCKS = 64         # SEER_SNR_MSE_BLOCKS of include/seer_hip.h: the partial sums a sample may leave in the workspace
+
+
+def snr_mse_loss_grad(pred: torch.Tensor, target: torch.Tensor, timesteps: torch.Tensor, alphas_cumprod: torch.Tensor, cond_f: int,
+                      snr_gamma: float, v_prediction: bool = False, *, sample_loss: Optional[torch.Tensor] = None,
+                      weights: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """mse_loss_grad with Min-SNR-gamma weighting (seer_snr_mse_loss_grad): sample b weighs min(SNR, gamma) / SNR -- for a v-model
+    (`v_prediction`) min(SNR, gamma) / (SNR + 1) -- at alphas_cumprod[timesteps[b]], inside the loss and inside dpred.  pred, target as
+    in mse_loss_grad; timesteps int64 [B] and alphas_cumprod fp32 [T] on pred's device (the kernel reads them there; a timestep outside
+    [0, T) is clamped into the table).  -> (loss [1], dpred like pred, sample_loss [B]: the unweighted per-sample means, weights [B]);
+    `sample_loss` / `weights`: caller-owned fp32 [B] buffers to receive them."""
+    _req(pred, torch.float32, "pred"); _req(target, torch.float32, "target"); _req(alphas_cumprod, torch.float32, "alphas_cumprod")
+    _req(timesteps, torch.int64, "timesteps")
+    assert pred.is_contiguous() and target.is_contiguous() and pred.dim() == 5
+    assert alphas_cumprod.dim() == 1 and alphas_cumprod.is_contiguous() and timesteps.is_contiguous()
+    B, Cc, Ft, H, W = pred.shape
+    assert target.shape == (B, Cc, Ft - cond_f, H, W) and timesteps.shape == (B,) and alphas_cumprod.numel() > 0
+    assert timesteps.device == pred.device and alphas_cumprod.device == pred.device, "timesteps and the table live on pred's device"
+    loss = torch.empty((1,), device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred)
+    outs = []
+    for t, name in ((sample_loss, "sample_loss"), (weights, "weights")):
+        if t is None:
+            t = torch.empty((B,), device=pred.device, dtype=torch.float32)
+        _req(t, torch.float32, name)
+        assert t.is_contiguous() and t.shape == (B,) and t.device == pred.device
+        outs.append(t)
+    ws = torch.empty((B * SNR_MSE_BLOCKS,), device=pred.device, dtype=torch.float64)
+    check(_lib.load().seer_snr_mse_loss_grad(_p(pred), _p(target), _p(timesteps), _p(alphas_cumprod), alphas_cumprod.numel(),
+                                             float(snr_gamma), int(bool(v_prediction)), B, Cc, Ft, int(cond_f), H * W, _p(loss),
+                                             _p(outs[0]), _p(outs[1]), _p(dpred), _p(ws), _stream()), "seer_snr_mse_loss_grad")
+    return loss, dpred, outs[0], outs[1]
+
+
 def text_loss_grad(y: torch.Tensor, target: torch.Tensor, b: int, Fr: int, dy: torch.Tensor) -> torch.Tensor:
     """y, dy bf16 [b*F*l, C] (rows (b, f, l)); target fp32 [b, l, C].  Adds the text-loss gradient to dy, returns the loss [1]."""
     _req(y, bf16, "y"); _req(dy, bf16, "dy"); _req(target, torch.float32, "target")

@@ -20,6 +20,7 @@ file's wiring on CPU against autograd of the oracle).
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Dict, List, Optional, Tuple
 
@@ -164,7 +165,8 @@ class SeerTrainer:
     def __init__(self, unet: SeerUNet, fstext: FSTextTransformer, *, lr: float = 1e-4, betas=(0.9, 0.999),
                  weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, gradient_accumulation_steps: int = 1,
                  text_loss: bool = False, use_8bit_adam: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None,
-                 prediction_type: str = "epsilon"):
+                 prediction_type: str = "epsilon", snr_gamma: Optional[float] = None,
+                 alphas_cumprod: Optional[torch.Tensor] = None):
         self.ops, self.tops = ops, tops
         # train.py:371-376 (the scheduler's prediction_type): the loss target is the noise, or -- "v_prediction" -- the velocity
         # sqrt(a) noise - sqrt(1 - a) latents (seer_velocity_target); forward_backward itself does not know which
@@ -182,6 +184,24 @@ class SeerTrainer:
         self.unet, self.fstext = unet, fstext
         self.eng = _Engine(unet, ops=ops, fold_ln=False)
         self.device = self.eng.device
+        # Min-SNR-gamma loss weighting (`--snr_gamma` of the diffusers training scripts; Hang et al., ICCV 2023): sample b of a batch
+        # weighs min(SNR, gamma) / SNR, for a v-model min(SNR, gamma) / (SNR + 1), at its own timestep.  There is no autograd here, so
+        # the weight enters where dpred is born: seer_snr_mse_loss_grad takes the place of seer_mse_loss_grad in the step and reads the
+        # timesteps and this table from device memory (a captured step replays with new timesteps).  None: the flat mean, as before.
+        self.snr_gamma: Optional[float] = None
+        self.last_sample_loss = self.last_loss_weights = None     # fp32 [b] of the last step: unweighted per-sample losses, weights
+        if snr_gamma is not None:
+            gamma = float(snr_gamma)
+            if not (math.isfinite(gamma) and gamma > 0.0):
+                raise ValueError(f"snr_gamma must be a finite positive number (the diffusers scripts use 5.0), got {snr_gamma!r}")
+            if not hasattr(tops, "snr_mse_loss_grad"):
+                raise ValueError("snr_gamma needs a training backend with snr_mse_loss_grad (train_ops.snr_mse_loss_grad)")
+            table = ddpm_alphas_cumprod() if alphas_cumprod is None else alphas_cumprod
+            if table.dim() != 1 or table.numel() == 0:
+                raise ValueError(f"alphas_cumprod: a table [T], got {tuple(table.shape)}")
+            self.snr_gamma = gamma
+            self._snr_acp = table.detach().to(self.device, f32).clone().contiguous()      # the trainer's own copy, never rewritten
+            self._snr_acp_seen = None                               # (table object, its version) that last passed _check_snr_table
         self.step_count = 0
         sd_u = {k: v for k, v in unet.state_dict().items()}
         sd_f = {k: v for k, v in fstext.state_dict().items()}
@@ -789,9 +809,9 @@ class SeerTrainer:
                 import warnings
                 warnings.warn(f"hipGraph capture of the training step failed ({type(e).__name__}: {e}); running eagerly")
                 return self.forward_backward(model_input, target, timesteps, text_cond_emb, cond_frames, False, on_unet_grads)
-            g = (ga, gb, bufs, loss, self.last_pred, st)
+            g = (ga, gb, bufs, loss, self.last_pred, st, (self.last_sample_loss, self.last_loss_weights))
             self._graphs = {key: g}
-        ga, gb, bufs, loss, pred, _ = g
+        ga, gb, bufs, loss, pred, _, snr_outs = g
         for dst, src in zip(bufs, (model_input, target, t, text_cond_emb)):
             dst.copy_(src)
         ga.replay()
@@ -799,6 +819,7 @@ class SeerTrainer:
             on_unet_grads()
         gb.replay()
         self.last_pred = pred
+        self.last_sample_loss, self.last_loss_weights = snr_outs       # the graph's static outputs (None without snr_gamma)
         return loss
 
     def _phase_a(self, model_input, target, timesteps, text_cond_emb, cond_frames):
@@ -812,7 +833,12 @@ class SeerTrainer:
         t = timesteps if torch.is_tensor(timesteps) else torch.tensor([timesteps] * b)
         t = t.to(model_input.device, torch.int64).expand(b).contiguous()
         pred, tape = self._unet_fwd(model_input.float().contiguous(), t, y, text_cond_emb.shape[1], cond_frames)
-        loss, dpred = self.tops.mse_loss_grad(pred, target.float().contiguous(), cond_frames)
+        if self.snr_gamma is None:
+            loss, dpred = self.tops.mse_loss_grad(pred, target.float().contiguous(), cond_frames)
+        else:           # the weights are inside dpred: nothing behind this line knows of them
+            loss, dpred, self.last_sample_loss, self.last_loss_weights = self.tops.snr_mse_loss_grad(
+                pred, target.float().contiguous(), t, self._snr_acp, cond_frames, self.snr_gamma,
+                self.prediction_type == "v_prediction")
         dctx = self._unet_bwd(tape, dpred)
         if self.text_loss:      # loss += mse(text_seq.mean(1), text_cond_emb): its gradient joins the UNet's d context
             lt = self.tops.text_loss_grad(y, text_cond_emb.float().contiguous(), b, Fr, dctx)
@@ -897,6 +923,7 @@ class SeerTrainer:
         """train.py:355-387 after the VAE encode: DDPM add_noise, concat the conditioning latents, forward, loss, backward,
         clip, AdamW (the optimizer runs every `gradient_accumulation_steps` calls).  alphas_cumprod: the scheduler's table
         (fp32 [T]).  The loss target is the noise, or with prediction_type="v_prediction" the velocity (train.py:371-374)."""
+        self._check_snr_table(alphas_cumprod)
         acp = alphas_cumprod.to(latents.device, f32)
         a = acp[timesteps].reshape(-1, 1, 1, 1, 1)
         noisy = a.sqrt() * latents + (1 - a).sqrt() * noise               # DDPMScheduler.add_noise (input preparation)
@@ -907,6 +934,22 @@ class SeerTrainer:
         if self.accumulate():
             self.optimizer_step(lr)
         return loss
+
+    def _check_snr_table(self, alphas_cumprod) -> None:
+        """with snr_gamma the loss weights come from the table the trainer holds: a step that noises with another one is an error.
+        Compared once per tensor object (and again when it was written to since), so a training loop pays no per-step read-back."""
+        if self.snr_gamma is None:
+            return
+        seen = self._snr_acp_seen
+        if seen is not None and seen[0] is alphas_cumprod and seen[1] == alphas_cumprod._version:
+            return
+        held = self._snr_acp
+        if alphas_cumprod.dim() != 1 or alphas_cumprod.numel() != held.numel():
+            raise ValueError(f"alphas_cumprod has {tuple(alphas_cumprod.shape)} entries, the table the Min-SNR weights are taken from "
+                             f"(SeerTrainer(alphas_cumprod=...)) has {held.numel()}")
+        if not torch.equal(alphas_cumprod.detach().to(held.device, f32), held):
+            raise ValueError("alphas_cumprod differs from the table the Min-SNR weights are taken from (SeerTrainer(alphas_cumprod=...))")
+        self._snr_acp_seen = (alphas_cumprod, alphas_cumprod._version)
 
     def _loss_target(self, latents, noise, timesteps, acp):
         """train.py:371-376: the noise, or the velocity of (latents, noise) at the timesteps -- one launch, seer_velocity_target"""
@@ -948,6 +991,7 @@ class SeerTrainer:
         if self.fstext.num_frames != Fr:
             raise ValueError(f"step_from_batch: the FSTextTransformer is set to {self.fstext.num_frames} frames, the video has "
                              f"{Fr}: call fstext.set_numframe({Fr}) first (train.py:187)")
+        self._check_snr_table(alphas_cumprod)
         dev, f2 = self.device, Fr - f1
         if attention_mask is not None:
             attention_mask = attention_mask.to(dev)
