@@ -1004,6 +1004,26 @@ int seer_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, flo
 int seer_adamw8_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v, const float* qmap_m,
                      const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
                      int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream);
+/* seer_adamw_step / seer_adamw8_step that also move an exponential moving average of the parameters (the CompVis tree's
+ * ldm/modules/ema.py LitEma, diffusers' `--use_ema`) in the same launch, from the register that holds the new parameter p':
+ *   ema' = ema - one_minus_decay * (ema - p')
+ * LitEma.forward's `shadow.sub_(one_minus_decay * (shadow - param))`: three fp32 operations, each rounded on its own (a difference, a
+ * product, a difference; never contracted into a fused multiply-add), so ema' has the bits of those three torch operations.  p, the
+ * moments (codes, scales) and p_bf16 receive exactly what the plain entry point writes.  ema: fp32 [n] in BOTH optimizer modes: at
+ * decay 0.9999 a step moves the average by 1e-4 of its distance to p', far below what an 8- or 16-bit state can hold.
+ * The expression is taken literally: one_minus_decay = 1 does not always yield p' exactly (ema - (ema - p') rounds twice);
+ * one_minus_decay = 0 leaves ema's bits untouched unless ema - p' is non-finite (0 * inf = NaN); a non-finite p' makes ema non-finite,
+ * as in LitEma: there is no guard.
+ * SEER_EINVAL, nothing launched: everything the plain entry point refuses; ema == NULL; one_minus_decay outside [0, 1] (a NaN
+ * included); ema not 4-byte (seer_adamw_ema_step) or not 16-byte (seer_adamw8_ema_step) aligned; ema's n floats overlapping p, g, the
+ * moments (m, v; cm, cv, absmax_m, absmax_v), p_bf16 or grad_sumsq. */
+int seer_adamw_ema_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream,
+                        float* ema, float one_minus_decay);
+int seer_adamw8_ema_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v, const float* qmap_m,
+                         const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream, float* ema,
+                         float one_minus_decay);
 
 /* The glue of train.py:349-365 between the VAE encoder and the UNet, in ONE launch: posterior sample, latent scale, DDPM add_noise
  * and the `(b f) c h w -> b c f h w` rearranges (train.py:353-354,365).

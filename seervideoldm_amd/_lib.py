@@ -216,6 +216,9 @@ SIGNATURES = {
     "seer_adamw_step": ([_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp], C.c_int),
     "seer_adamw8_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp],
                          C.c_int),
+    "seer_adamw_ema_step": ([_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp, _vp, _f32], C.c_int),
+    "seer_adamw8_ema_step": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _f32, _i32, _vp, _f32, _vp, _vp,
+                              _vp, _f32], C.c_int),
     "seer_train_inputs": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp], C.c_int),
     "seer_velocity_target": ([_vp, _vp, _vp, _vp, _i32, _i32, _i64, _vp, _vp], C.c_int),
 }

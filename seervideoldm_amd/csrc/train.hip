@@ -872,10 +872,27 @@ __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ g,
 // torch.optim.AdamW (train.py:226-232) on flat fp32 buffers; the gradient is first scaled by
 // min(1, max_norm / (sqrt(*sumsq) + 1e-6)) when sumsq != NULL (torch.nn.utils.clip_grad_norm_, train.py:384).
 // Also refreshes the bf16 working copy of the parameters.
+//
+// EMA (seer_adamw_ema_step, seer_adamw8_ema_step): the same update bodies, and an exponential moving average of the parameters
+// (LitEma of the CompVis tree, ldm/modules/ema.py:42) moved from the register that holds the new parameter: 8 bytes of traffic per
+// element instead of the three passes of torch operations.  ema is fp32 in BOTH optimizer modes: at decay 0.9999 a step moves the
+// average by 1e-4 of its distance to p, far below what an 8- or 16-bit state can hold.  The EMA = false instantiations read
+// neither ema nor omd: they are the kernels without the switch.
+//
+// ema_update: shadow.sub_(one_minus_decay * (shadow - param)) as the three separately rounded fp32 operations torch performs.  The
+// pragma keeps the product and the second difference from contracting into one v_fma_f32 (__fsub_rn / __fmul_rn do not).
+__device__ __forceinline__ float ema_update(float e, float p, float omd) {
+#pragma clang fp contract(off)
+    const float d = e - p;
+    const float s = omd * d;
+    return e - s;
+}
+
+template <bool EMA>
 __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, float lr, float b1, float b2, float eps,
                                                     float wd, float bc1, float bc2_sqrt, const float* __restrict__ sumsq,
-                                                    float max_norm, bf16* __restrict__ p_bf16) {
+                                                    float max_norm, bf16* __restrict__ p_bf16, float* __restrict__ ema, float omd) {
     float coef = 1.0f;
     if (sumsq) coef = fminf(1.0f, max_norm / (sqrtf(*sumsq) + 1e-6f));
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -889,6 +906,7 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
         m[i] = mi;
         v[i] = vi;
         if (p_bf16) p_bf16[i] = (bf16)pi;
+        if (EMA) ema[i] = ema_update(ema[i], pi, omd);
     }
 }
 
@@ -916,12 +934,13 @@ __device__ __forceinline__ float adam8_wave_max(float x) {
     return x;
 }
 
+template <bool EMA>
 __global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, const float* __restrict__ g, uint8_t* __restrict__ cm,
                                                      uint8_t* __restrict__ cv, float* __restrict__ absmax_m,
                                                      float* __restrict__ absmax_v, const float* __restrict__ qmap_m,
                                                      const float* __restrict__ qmap_v, int64_t nblk, float lr, float b1, float b2,
                                                      float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ sumsq,
-                                                     float max_norm, bf16* __restrict__ p_bf16) {
+                                                     float max_norm, bf16* __restrict__ p_bf16, float* __restrict__ ema, float omd) {
     __shared__ float qm[256], qv[256];
     qm[threadIdx.x] = qmap_m[threadIdx.x];
     qv[threadIdx.x] = qmap_v[threadIdx.x];
@@ -975,6 +994,12 @@ __global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, cons
 #pragma unroll
             for (int e = 0; e < 4; ++e) o[e] = (bf16)pv[e];
             reinterpret_cast<bf16x4*>(p_bf16)[q4] = o;
+        }
+        if (EMA) {
+            f32x4 ev = reinterpret_cast<const f32x4*>(ema)[q4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) ev[e] = ema_update(ev[e], pv[e], omd);
+            reinterpret_cast<f32x4*>(ema)[q4] = ev;
         }
     }
 }
@@ -1459,17 +1484,80 @@ extern "C" int seer_sumsq_f32(const float* g, int64_t n, float* out, float* work
     return SEER_OK;
 }
 
-extern "C" int seer_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                               float eps, float weight_decay, int32_t step, const float* grad_sumsq, float max_norm,
-                               void* p_bf16, void* stream) {
+// [a, a + an) and [b, b + bn) share a byte (an empty or NULL range shares none)
+static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    if (!a || !b || !an || !bn) return false;
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bn && y < x + an;
+}
+
+// what the two _ema entry points refuse of (ema, one_minus_decay) beyond NULL and the overlaps: !(0 <= omd <= 1) also catches a NaN
+static bool ema_args_bad(const float* ema, float omd, uintptr_t align_mask) {
+    return !ema || !(omd >= 0.0f && omd <= 1.0f) || (reinterpret_cast<uintptr_t>(ema) & align_mask);
+}
+
+static int adamw_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                        float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream,
+                        float* ema, float omd) {
     if (!p || !g || !m || !v || n <= 0 || step <= 0) return SEER_EINVAL;
+    if (ema) {
+        const size_t nb = (size_t)n * sizeof(float);
+        if (ranges_overlap(ema, nb, p, nb) || ranges_overlap(ema, nb, g, nb) || ranges_overlap(ema, nb, m, nb) ||
+            ranges_overlap(ema, nb, v, nb) || ranges_overlap(ema, nb, p_bf16, (size_t)n * sizeof(bf16)) ||
+            ranges_overlap(ema, nb, grad_sumsq, sizeof(float)))
+            return SEER_EINVAL;
+    }
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     int64_t blocks = (n + 256 * 8 - 1) / (256 * 8);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n,
-                       lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_sumsq, max_norm,
-                       reinterpret_cast<bf16*>(p_bf16));
+    auto kernel = ema ? adamw_kernel<true> : adamw_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, lr, beta1,
+                       beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_sumsq, max_norm, reinterpret_cast<bf16*>(p_bf16),
+                       ema, omd);
+    SEER_LAUNCH_CHECK();
+    return SEER_OK;
+}
+
+extern "C" int seer_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                               float eps, float weight_decay, int32_t step, const float* grad_sumsq, float max_norm,
+                               void* p_bf16, void* stream) {
+    return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_sumsq, max_norm, p_bf16, stream, nullptr, 0.f);
+}
+
+extern "C" int seer_adamw_ema_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                   float eps, float weight_decay, int32_t step, const float* grad_sumsq, float max_norm,
+                                   void* p_bf16, void* stream, float* ema, float one_minus_decay) {
+    if (ema_args_bad(ema, one_minus_decay, 3)) return SEER_EINVAL;
+    return adamw_launch(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_sumsq, max_norm, p_bf16, stream, ema,
+                        one_minus_decay);
+}
+
+static int adamw8_launch(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v, const float* qmap_m,
+                         const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                         int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16, void* stream, float* ema, float omd) {
+    if (!p || !g || !cm || !cv || !absmax_m || !absmax_v || !qmap_m || !qmap_v || n <= 0 || n % 256 || step < 1) return SEER_EINVAL;
+    const uintptr_t wide = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g);
+    const uintptr_t narrow = reinterpret_cast<uintptr_t>(cm) | reinterpret_cast<uintptr_t>(cv) | reinterpret_cast<uintptr_t>(absmax_m) |
+                             reinterpret_cast<uintptr_t>(absmax_v) | reinterpret_cast<uintptr_t>(qmap_m) |
+                             reinterpret_cast<uintptr_t>(qmap_v) | reinterpret_cast<uintptr_t>(grad_sumsq);
+    if ((wide & 15) || (narrow & 3) || (reinterpret_cast<uintptr_t>(p_bf16) & 7)) return SEER_EINVAL;
+    const int64_t nblk = n / 256;
+    if (ema) {
+        const size_t nb = (size_t)n * sizeof(float), sb = (size_t)nblk * sizeof(float);
+        if (ranges_overlap(ema, nb, p, nb) || ranges_overlap(ema, nb, g, nb) || ranges_overlap(ema, nb, cm, (size_t)n) ||
+            ranges_overlap(ema, nb, cv, (size_t)n) || ranges_overlap(ema, nb, absmax_m, sb) || ranges_overlap(ema, nb, absmax_v, sb) ||
+            ranges_overlap(ema, nb, p_bf16, (size_t)n * sizeof(bf16)) || ranges_overlap(ema, nb, grad_sumsq, sizeof(float)))
+            return SEER_EINVAL;
+    }
+    const double bc1 = 1.0 - pow((double)beta1, (double)step);
+    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    int64_t blocks = (nblk + 3) / 4;               // four waves, one 256-element block each per trip
+    if (blocks > 2048) blocks = 2048;
+    auto kernel = ema ? adamw8_kernel<true> : adamw8_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, cm, cv, absmax_m,
+                       absmax_v, qmap_m, qmap_v, nblk, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), grad_sumsq,
+                       max_norm, reinterpret_cast<bf16*>(p_bf16), ema, omd);
     SEER_LAUNCH_CHECK();
     return SEER_OK;
 }
@@ -1478,22 +1566,17 @@ extern "C" int seer_adamw8_step(float* p, const float* g, uint8_t* cm, uint8_t* 
                                 const float* qmap_m, const float* qmap_v, int64_t n, float lr, float beta1, float beta2, float eps,
                                 float weight_decay, int32_t step, const float* grad_sumsq, float max_norm, void* p_bf16,
                                 void* stream) {
-    if (!p || !g || !cm || !cv || !absmax_m || !absmax_v || !qmap_m || !qmap_v || n <= 0 || n % 256 || step < 1) return SEER_EINVAL;
-    const uintptr_t wide = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g);
-    const uintptr_t narrow = reinterpret_cast<uintptr_t>(cm) | reinterpret_cast<uintptr_t>(cv) | reinterpret_cast<uintptr_t>(absmax_m) |
-                             reinterpret_cast<uintptr_t>(absmax_v) | reinterpret_cast<uintptr_t>(qmap_m) |
-                             reinterpret_cast<uintptr_t>(qmap_v) | reinterpret_cast<uintptr_t>(grad_sumsq);
-    if ((wide & 15) || (narrow & 3) || (reinterpret_cast<uintptr_t>(p_bf16) & 7)) return SEER_EINVAL;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const int64_t nblk = n / 256;
-    int64_t blocks = (nblk + 3) / 4;               // four waves, one 256-element block each per trip
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adamw8_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, g, cm, cv,
-                       absmax_m, absmax_v, qmap_m, qmap_v, nblk, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
-                       grad_sumsq, max_norm, reinterpret_cast<bf16*>(p_bf16));
-    SEER_LAUNCH_CHECK();
-    return SEER_OK;
+    return adamw8_launch(p, g, cm, cv, absmax_m, absmax_v, qmap_m, qmap_v, n, lr, beta1, beta2, eps, weight_decay, step, grad_sumsq,
+                         max_norm, p_bf16, stream, nullptr, 0.f);
+}
+
+extern "C" int seer_adamw8_ema_step(float* p, const float* g, uint8_t* cm, uint8_t* cv, float* absmax_m, float* absmax_v,
+                                    const float* qmap_m, const float* qmap_v, int64_t n, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, int32_t step, const float* grad_sumsq, float max_norm,
+                                    void* p_bf16, void* stream, float* ema, float one_minus_decay) {
+    if (ema_args_bad(ema, one_minus_decay, 15)) return SEER_EINVAL;
+    return adamw8_launch(p, g, cm, cv, absmax_m, absmax_v, qmap_m, qmap_v, n, lr, beta1, beta2, eps, weight_decay, step, grad_sumsq,
+                         max_norm, p_bf16, stream, ema, one_minus_decay);
 }
 
 extern "C" int seer_axpby_f32(float* y, const float* x, float alpha, float beta, int64_t n, void* stream) {

@@ -383,6 +383,29 @@ def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tenso
                                       _stream()), "seer_adamw_step")
 
 
+def _req_ema(ema: torch.Tensor, p: torch.Tensor, one_minus_decay: float) -> float:
+    _req(ema, torch.float32, "ema")
+    assert ema.is_contiguous() and ema.numel() == p.numel(), "ema: a contiguous fp32 buffer of p's size"
+    return float(one_minus_decay)
+
+
+def adamw_ema_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, ema: torch.Tensor, *,
+                   one_minus_decay: float, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, step: int,
+                   grad_sumsq: Optional[torch.Tensor] = None, max_norm: float = 1.0, p_bf16: Optional[torch.Tensor] = None) -> None:
+    """adamw_step that also moves the exponential moving average `ema` (fp32 [n]) of the parameters in the same launch
+    (seer_adamw_ema_step): ema -= one_minus_decay * (ema - p_new), LitEma's three separately rounded fp32 operations."""
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _req(t, torch.float32, n)
+        assert t.is_contiguous() and t.numel() == p.numel()
+    omd = _req_ema(ema, p, one_minus_decay)
+    if p_bf16 is not None:
+        _req(p_bf16, bf16, "p_bf16")
+        assert p_bf16.is_contiguous() and p_bf16.numel() == p.numel()
+    check(_lib.load().seer_adamw_ema_step(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                                          float(eps), float(weight_decay), int(step), _p(grad_sumsq), float(max_norm), _p(p_bf16),
+                                          _stream(), _p(ema), omd), "seer_adamw_ema_step")
+
+
 ADAM8_BLOCK = 256           # elements per quantisation block of the 8-bit optimizer state
 ADAM8_ZERO_CODES = (127, 0)  # the codes of 0.0 in the signed / unsigned book: a fresh state
 _adam8_qmaps: dict = {}
@@ -439,6 +462,31 @@ def adamw8_step(p: torch.Tensor, g: torch.Tensor, cm: torch.Tensor, cv: torch.Te
     check(_lib.load().seer_adamw8_step(_p(p), _p(g), _p(cm), _p(cv), _p(absmax_m), _p(absmax_v), _p(qm), _p(qv), n, float(lr),
                                        float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
                                        _p(grad_sumsq), float(max_norm), _p(p_bf16), _stream()), "seer_adamw8_step")
+
+
+def adamw8_ema_step(p: torch.Tensor, g: torch.Tensor, cm: torch.Tensor, cv: torch.Tensor, absmax_m: torch.Tensor,
+                    absmax_v: torch.Tensor, ema: torch.Tensor, *, one_minus_decay: float, lr: float, betas=(0.9, 0.999),
+                    eps: float = 1e-8, weight_decay: float = 1e-2, step: int, grad_sumsq: Optional[torch.Tensor] = None,
+                    max_norm: float = 1.0, p_bf16: Optional[torch.Tensor] = None) -> None:
+    """adamw8_step that also moves the exponential moving average `ema` of the parameters (seer_adamw8_ema_step); `ema` stays
+    fp32 [n] in 8-bit mode (a step at decay 0.9999 is far below what an 8-bit state resolves)."""
+    n = p.numel()
+    for t, name in ((p, "p"), (g, "g"), (absmax_m, "absmax_m"), (absmax_v, "absmax_v")):
+        _req(t, torch.float32, name)
+    for t, name in ((cm, "cm"), (cv, "cv")):
+        _req(t, torch.uint8, name)
+    assert all(t.is_contiguous() for t in (p, g, cm, cv, absmax_m, absmax_v))
+    assert n % ADAM8_BLOCK == 0 and g.numel() == cm.numel() == cv.numel() == n, "flat buffers of a multiple of 256 elements"
+    assert absmax_m.numel() == absmax_v.numel() == n // ADAM8_BLOCK
+    omd = _req_ema(ema, p, one_minus_decay)
+    if p_bf16 is not None:
+        _req(p_bf16, bf16, "p_bf16")
+        assert p_bf16.is_contiguous() and p_bf16.numel() == n
+    qm, qv = adam8_qmaps(p.device)
+    check(_lib.load().seer_adamw8_ema_step(_p(p), _p(g), _p(cm), _p(cv), _p(absmax_m), _p(absmax_v), _p(qm), _p(qv), n, float(lr),
+                                           float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                           _p(grad_sumsq), float(max_norm), _p(p_bf16), _stream(), _p(ema), omd),
+          "seer_adamw8_ema_step")
 
 
 def train_inputs(moments: torch.Tensor, eps_post: Optional[torch.Tensor], noise: torch.Tensor, timesteps: torch.Tensor,

@@ -20,6 +20,7 @@ file's wiring on CPU against autograd of the oracle).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, List, Optional, Tuple
@@ -65,17 +66,38 @@ def ddpm_alphas_cumprod(num_train_timesteps: int = 1000, beta_start: float = 0.0
     return torch.cumprod(1.0 - betas, dim=0)
 
 
+def ema_one_minus_decay(decay: float, num_updates: int, warmup: bool = True) -> float:
+    """`one_minus_decay` of update number `num_updates` (1 for the first: the count AFTER incrementing) as LitEma.forward computes it
+    with fp32 tensors (ldm/modules/ema.py:26-32), returned as a Python float that is exactly that fp32 value:
+        warmup:      fl32(1) - min(fl32(decay), fl32(1 + n) / fl32(10 + n))          (`use_num_upates=True`, the default there)
+        otherwise:   fl32(1) - fl32(decay)
+    Also diffusers' EMAModel with use_ema_warmup=False (its inv_gamma / power warm-up and update_after_step are not provided)."""
+    d = float(decay)
+    if not (math.isfinite(d) and 0.0 <= d <= 1.0):
+        raise ValueError(f"ema_decay must be a finite number in [0, 1], got {decay!r}")
+    d = torch.tensor(d, dtype=f32)
+    if warmup:
+        n = int(num_updates)
+        if n < 0:
+            raise ValueError(f"num_updates must not be negative, got {num_updates!r}")
+        d = torch.minimum(d, torch.tensor(1 + n, dtype=f32) / torch.tensor(10 + n, dtype=f32))
+    return float(torch.tensor(1.0, dtype=f32) - d)
+
+
 FP32_FORMAT = "adam-fp32"              # optimizer.bin of save_state: fp32 m, v (files of this kind carry no "format" entry)
 ADAM8_FORMAT = "adam8-block256"        # 8-bit codes + one fp32 scale per 256-element block (use_8bit_adam)
+EMA_FORMAT = "seer-ema-fp32-v1"        # ema.bin of save_state: the two flat packed fp32 averages (use_ema)
 
 
 class _Params:
     """flat fp32 master / gradient / Adam buffers with named views (packed layouts).  Every tensor starts on a multiple of `align`
     elements and n is one; the padding has a zero gradient and stays zero.  adam8: the moments are 8-bit codes cm / cv with one fp32
     scale per 256-element block (absmax_m / absmax_v; seer_adamw8_step) instead of the fp32 buffers m / v, which are None then;
-    with align = 256 no block spans two tensors, so a tensor's optimizer state depends on its own values only."""
+    with align = 256 no block spans two tensors, so a tensor's optimizer state depends on its own values only.  ema: None, or the
+    exponential moving average of p (fp32 in both modes), a clone of p at construction, padding included: p's padding stays zero, so
+    the average's does."""
 
-    def __init__(self, tensors: "Dict[str, torch.Tensor]", device, align: int = 8, adam8: bool = False):
+    def __init__(self, tensors: "Dict[str, torch.Tensor]", device, align: int = 8, adam8: bool = False, ema: bool = False):
         assert align % 8 == 0 and (not adam8 or align % 256 == 0)
         self.names = list(tensors)
         self.shapes = {k: tuple(v.shape) for k, v in tensors.items()}
@@ -99,6 +121,7 @@ class _Params:
             self.m = torch.zeros_like(self.p)
             self.v = torch.zeros_like(self.p)
         self.pb = self.p.to(bf16)
+        self.ema = self.p.clone() if ema else None
 
     def state(self) -> "Dict[str, torch.Tensor]":
         """the optimizer state tensors by name"""
@@ -166,7 +189,8 @@ class SeerTrainer:
                  weight_decay: float = 1e-2, eps: float = 1e-8, max_grad_norm: float = 1.0, gradient_accumulation_steps: int = 1,
                  text_loss: bool = False, use_8bit_adam: bool = False, ops=hip_ops, tops=hip_train_ops, process_group=None,
                  prediction_type: str = "epsilon", snr_gamma: Optional[float] = None,
-                 alphas_cumprod: Optional[torch.Tensor] = None):
+                 alphas_cumprod: Optional[torch.Tensor] = None, use_ema: bool = False, ema_decay: float = 0.9999,
+                 ema_warmup: bool = True):
         self.ops, self.tops = ops, tops
         # train.py:371-376 (the scheduler's prediction_type): the loss target is the noise, or -- "v_prediction" -- the velocity
         # sqrt(a) noise - sqrt(1 - a) latents (seer_velocity_target); forward_backward itself does not know which
@@ -202,10 +226,24 @@ class SeerTrainer:
             self.snr_gamma = gamma
             self._snr_acp = table.detach().to(self.device, f32).clone().contiguous()      # the trainer's own copy, never rewritten
             self._snr_acp_seen = None                               # (table object, its version) that last passed _check_snr_table
+        # An exponential moving average of the trained weights (`--use_ema` of the diffusers scripts; LitEma / ema_scope of the CompVis
+        # tree): P.ema, moved once per optimizer step INSIDE the AdamW launch (seer_adamw_ema_step / seer_adamw8_ema_step) from the
+        # register that holds the new parameter, with LitEma's arithmetic bit for bit.  False: exactly the launches there were.
+        self.use_ema = bool(use_ema)
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        if not (math.isfinite(self.ema_decay) and 0.0 <= self.ema_decay <= 1.0):
+            raise ValueError(f"ema_decay must be a finite number in [0, 1], got {ema_decay!r}")
+        self.ema_num_updates = 0
+        self._in_ema_scope = False
+        if self.use_ema:
+            need = "adamw8_ema_step" if self.use_8bit_adam else "adamw_ema_step"
+            if not hasattr(tops, need):
+                raise ValueError(f"use_ema needs a training backend with {need} (train_ops.{need})")
         self.step_count = 0
         sd_u = {k: v for k, v in unet.state_dict().items()}
         sd_f = {k: v for k, v in fstext.state_dict().items()}
         pk = dict(align=256, adam8=True) if self.use_8bit_adam else {}
+        pk["ema"] = self.use_ema
         self.pu = _Params(_pack_temporal_fp32(sd_u), self.device, **pk)
         self.pf = _Params(_pack_fstext_fp32(sd_f, fstext.num_layers), self.device, **pk)
         for P in (self.pu, self.pf):                            # mean of the micro-batch gradients when accumulating
@@ -779,6 +817,8 @@ class SeerTrainer:
         The step has two phases: (A) FSTextTransformer forward, UNet forward, loss, UNet backward -- after it the UNet's
         gradient segment is final -- and (B) the FSTextTransformer backward.  `on_unet_grads()` is called between them: data
         parallel training starts the all-reduce of the UNet segment there, so it travels under phase B."""
+        if self._in_ema_scope:
+            raise RuntimeError("forward_backward inside ema_scope(): the working weights hold the average there")
         if not model_input.is_cuda and self.ops is hip_ops:
             raise hip_ops._lib.SeerHipError("SeerTrainer needs ROCm tensors: the HIP kernels are the only compute path")
         if use_graph and not self._graph_broken:
@@ -871,6 +911,8 @@ class SeerTrainer:
             self._early_hu = dist.all_reduce(self.pu.g, group=self.pg, async_op=True)
 
     def optimizer_step(self, lr: Optional[float] = None) -> None:
+        if self._in_ema_scope:
+            raise RuntimeError("optimizer_step inside ema_scope(): the master parameters hold the average there")
         lr = self.lr if lr is None else lr
         gu = self.pu.acc if self.accum > 1 else self.pu.g
         gf = self.pf.acc if self.accum > 1 else self.pf.g
@@ -884,6 +926,9 @@ class SeerTrainer:
             hf = dist.all_reduce(gf, group=self.pg, async_op=True)
         self.step_count += 1
         kw = dict(lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, step=self.step_count)
+        if self.use_ema:      # once per optimizer step, not per micro-batch; every rank computes the same bits from the averaged gradient
+            self.ema_num_updates += 1
+            kw["one_minus_decay"] = ema_one_minus_decay(self.ema_decay, self.ema_num_updates, self.ema_warmup)
         if hu is not None:
             hu.wait()
             self.tops.axpby(gu, gu, 1.0 / ws, 0.0)
@@ -896,10 +941,68 @@ class SeerTrainer:
         self.grad_norm_sq = ss
 
     def _adamw(self, P: _Params, g: torch.Tensor, **kw) -> None:
-        if P.adam8:
+        if P.ema is not None:
+            if P.adam8:
+                self.tops.adamw8_ema_step(P.p, g, P.cm, P.cv, P.absmax_m, P.absmax_v, P.ema, p_bf16=P.pb, **kw)
+            else:
+                self.tops.adamw_ema_step(P.p, g, P.m, P.v, P.ema, p_bf16=P.pb, **kw)
+        elif P.adam8:
             self.tops.adamw8_step(P.p, g, P.cm, P.cv, P.absmax_m, P.absmax_v, p_bf16=P.pb, **kw)
         else:
             self.tops.adamw_step(P.p, g, P.m, P.v, p_bf16=P.pb, **kw)
+
+    # ================================================================================================ the average
+    def _need_ema(self, what: str) -> None:
+        if not self.use_ema:
+            raise RuntimeError(f"{what} needs SeerTrainer(use_ema=True)")
+
+    def ema_state_bytes(self) -> int:
+        """bytes of the average held for both segments (4 per element; 0 without use_ema).  Not part of optimizer_state_bytes()."""
+        return sum(P.ema.numel() * P.ema.element_size() for P in (self.pu, self.pf) if P.ema is not None)
+
+    def ema_state_dict(self) -> "Dict[str, Dict[str, torch.Tensor]]":
+        """the averaged weights as `trainable_state_dict()` gives the raw ones: fp32, under the reference's names"""
+        self._need_ema("ema_state_dict")
+        if self._in_ema_scope:      # (exchanged: the average sits in the master buffers)
+            return self.trainable_state_dict_of(self.pu.p, self.pf.p)
+        return self.trainable_state_dict_of(self.pu.ema, self.pf.ema)
+
+    @torch.no_grad()
+    def reset_ema(self) -> None:
+        """ema <- p and the update count back to 0 (the warm-up starts over)"""
+        self._need_ema("reset_ema")
+        if self._in_ema_scope:
+            raise RuntimeError("reset_ema inside ema_scope()")
+        for P in (self.pu, self.pf):
+            P.ema.copy_(P.p)
+        self.ema_num_updates = 0
+
+    @torch.no_grad()
+    def _exchange_ema(self) -> None:
+        """P.p <-> P.ema IN PLACE (the working weights and the captured graphs are views of / read those addresses), then the bf16
+        working copy and the modules follow the master buffers"""
+        for P in (self.pu, self.pf):
+            tmp = P.p.clone()
+            P.p.copy_(P.ema)
+            P.ema.copy_(tmp)
+            P.pb.copy_(P.p)
+        self.sync_modules()
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """`with trainer.ema_scope():` -- inside, the SAME SeerUNet / FSTextTransformer objects sample with the averaged weights (the
+        CompVis tree's `ema_scope`); on exit the raw parameters and the average have their former bits.  optimizer_step,
+        forward_backward and a nested ema_scope raise RuntimeError inside."""
+        self._need_ema("ema_scope")
+        if self._in_ema_scope:
+            raise RuntimeError("ema_scope inside ema_scope()")
+        self._exchange_ema()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            self._exchange_ema()
 
     def optimizer_state_bytes(self) -> int:
         """bytes of optimizer state held for both segments (fp32: 8 per element; 8-bit: 2 per element + 8 per 256-element block)"""
@@ -1060,17 +1163,32 @@ class SeerTrainer:
         """the files of `accelerator.save_state(save_path)` that inference reads back (inference_img.py:98-104):
         `pytorch_model.bin` (SeerUNet) and `pytorch_model_1.bin` (FSTextTransformer), plus the Adam state of this trainer
         (`optimizer.bin`: flat packed buffers) and the step counters of train.py:398."""
-        import os
-        os.makedirs(save_path, exist_ok=True)
-        self.sync_modules()
-        cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}
-        torch.save(cpu(self.unet.state_dict()), os.path.join(save_path, "pytorch_model.bin"))
-        torch.save(cpu(self.fstext.state_dict()), os.path.join(save_path, "pytorch_model_1.bin"))
+        if self._in_ema_scope:
+            raise RuntimeError("save_state inside ema_scope(): save_ema_weights() writes the averaged model")
+        self._save_modules(save_path)
         st = {"step_count": self.step_count, "micro": self._micro, "epoch": epoch, "global_step": global_step,
               "unet": {k: t.cpu() for k, t in self.pu.state().items()}, "fstext": {k: t.cpu() for k, t in self.pf.state().items()}}
         if self.use_8bit_adam:          # (a file without "format" is the fp32 one: m and v)
             st["format"] = ADAM8_FORMAT
         torch.save(st, os.path.join(save_path, "optimizer.bin"))
+        if self.use_ema:
+            torch.save({"format": EMA_FORMAT, "decay": self.ema_decay, "warmup": self.ema_warmup, "num_updates": self.ema_num_updates,
+                        "unet": self.pu.ema.cpu(), "fstext": self.pf.ema.cpu()}, os.path.join(save_path, "ema.bin"))
+        return save_path
+
+    def _save_modules(self, save_path: str) -> None:
+        """`pytorch_model.bin` (SeerUNet) and `pytorch_model_1.bin` (FSTextTransformer) from the master buffers as they stand"""
+        os.makedirs(save_path, exist_ok=True)
+        self.sync_modules()
+        cpu = lambda sd: {k: v.detach().cpu() for k, v in sd.items()}
+        torch.save(cpu(self.unet.state_dict()), os.path.join(save_path, "pytorch_model.bin"))
+        torch.save(cpu(self.fstext.state_dict()), os.path.join(save_path, "pytorch_model_1.bin"))
+
+    def save_ema_weights(self, save_path: str) -> str:
+        """the two module files of `save_state` for the AVERAGED model, into a directory of its own: inference_img.py:98-104 (and
+        io.load_seer_checkpoint) read it as any checkpoint.  No optimizer state, no ema.bin."""
+        with self.ema_scope():
+            self._save_modules(save_path)
         return save_path
 
     def load_optimizer_state(self, save_path: str) -> None:
@@ -1084,6 +1202,25 @@ class SeerTrainer:
         for P, key in ((self.pu, "unet"), (self.pf, "fstext")):
             for k, t in P.state().items():
                 t.copy_(st[key][k])
+        if self.use_ema:                    # (a trainer without the average ignores ema.bin)
+            self._load_ema(os.path.join(save_path, "ema.bin"))
+
+    def _load_ema(self, path: str) -> None:
+        if not os.path.exists(path):
+            import warnings
+            warnings.warn(f"{path} is missing: the average restarts from the loaded parameters (reset_ema)")
+            self.reset_ema()
+            return
+        st = torch.load(path, map_location="cpu")
+        if st.get("format") != EMA_FORMAT:
+            raise ValueError(f"ema.bin holds format {st.get('format')!r}, this trainer reads {EMA_FORMAT!r}")
+        for P, key in ((self.pu, "unet"), (self.pf, "fstext")):
+            t = st[key]
+            if t.dim() != 1 or t.numel() != P.n:
+                raise ValueError(f"ema.bin: the {key} average has {tuple(t.shape)} elements, this trainer's packed buffer has {P.n}")
+        for P, key in ((self.pu, "unet"), (self.pf, "fstext")):
+            P.ema.copy_(st[key].to(f32))
+        self.ema_num_updates = int(st["num_updates"])
 
     def trainable_state_dict(self) -> "Dict[str, Dict[str, torch.Tensor]]":
         """{'unet': {...}, 'fstext': {...}} fp32 tensors under the REFERENCE's parameter names (unpacked)."""
