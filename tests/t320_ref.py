@@ -21,6 +21,9 @@ from tests.test_gpu_f16_matrix import _exact_pre, _ints
 
 bf16, f32, f64 = torch.bfloat16, torch.float32, torch.float64
 BM, BN, BK, FX_SHIFT = 256, 320, 64, 20
+# where the mutations sit, for a kernel of another geometry (tests/gemm_epi_ref.py passes its own): the block tile, the rows of a wave
+# tile, the columns of the wave whose K step is dropped, and the 16 x 16 fragment (row offset in that wave, columns) of the slice mutations
+GEOM = dict(BM=BM, BN=BN, WTM=64, wave_cols=(160, 320), frag=(16, 160 + 48))
 T320, KERNEL_T320 = 22, 4            # SEER_TILE_T256x320, SEER_GEMM_KERNEL_T320 (include/seer_hip.h)
 MUTATIONS = ["drop_kstep_one_wave", "residual_row_clamped", "slice_last_twice", "slice0_skipped", "rowvec_batch_per_wave_tile",
              "rot_no_modulo", "colscale_whole_fragment", "value_gate_exchanged_16", "pad_after_border_valid", "phases_swapped",
@@ -60,18 +63,31 @@ def slice_bounds(K, S, s):
 
 # ------------------------------------------------------------------------------------------- the epilogue
 def _rot_blocks(v, rot, no_modulo):
-    """fused320_ref.rotary on the 320-column blocks below rot_cols (head_dim divides 320)"""
-    assert rot["cols"] % 320 == 0 and 320 % rot["head_dim"] == 0
+    """fused320_ref.rotary on the 320-column blocks below rot_cols where head_dim divides 320; any other width (cols a multiple of
+    head_dim) through the same formula on the heads themselves"""
     v = v.clone()
-    for c0 in range(0, rot["cols"], 320):
-        v[:, c0:c0 + 320] = rotary(v[:, c0:c0 + 320], rot["table"], rot["tokens"], rot["off"], rot["head_dim"], rot["rot_dim"],
-                                   no_modulo=no_modulo)
+    if rot["cols"] % 320 == 0 and 320 % rot["head_dim"] == 0:
+        for c0 in range(0, rot["cols"], 320):
+            v[:, c0:c0 + 320] = rotary(v[:, c0:c0 + 320], rot["table"], rot["tokens"], rot["off"], rot["head_dim"], rot["rot_dim"],
+                                       no_modulo=no_modulo)
+        return v
+    M, hd, rd, cols = v.shape[0], rot["head_dim"], rot["rot_dim"], rot["cols"]
+    assert cols % hd == 0 and cols <= v.shape[1]
+    rows = torch.arange(M, device=v.device)
+    cs = rot["table"][(rows if no_modulo else rows % rot["tokens"]) + rot["off"]].to(f64)
+    c, s = cs[:, None, :, 0], cs[:, None, :, 1]
+    h = v[:, :cols].reshape(M, cols // hd, hd).clone()
+    x0, x1 = h[:, :, 0:rd:2].clone(), h[:, :, 1:rd:2].clone()
+    h[:, :, 0:rd:2], h[:, :, 1:rd:2] = x0 * c - x1 * s, x1 * c + x0 * s
+    v[:, :cols] = h.reshape(M, cols)
     return v
 
 
-def epilogue(acc, p, mut=None, exact=False):
-    """acc [M, N] float64 -> the value the kernel rounds, or None where `mut` does not apply"""
+def epilogue(acc, p, mut=None, exact=False, geom=GEOM):
+    """acc [M, N] float64 -> the value the kernel rounds, or None where `mut` does not apply.  p["silu"] / p["qgelu"] (the tile kernel
+    and the reduce pass; not this kernel): v / (1 + exp(-v)) or v * sigmoid(1.702 v) behind bias and row vector"""
     M, N = acc.shape
+    BM, WTM = geom["BM"], geom["WTM"]
     dev = acc.device
     rows = torch.arange(M, device=dev)
     v = acc
@@ -97,12 +113,23 @@ def epilogue(acc, p, mut=None, exact=False):
         rpb = p["rows_per_batch"]
         b = rows // rpb
         if mut == "rowvec_batch_per_wave_tile":
-            b = (rows // 64 * 64) // rpb
+            b = (rows // WTM * WTM) // rpb
             if bool((b == rows // rpb).all()):
                 return None
         v = v + p["rowvec"][b]
     elif mut == "rowvec_batch_per_wave_tile":
         return None
+    assert not (p.get("silu") and p.get("qgelu")), "one activation per launch"
+    if (p.get("silu") or p.get("qgelu")) and p.get("act_exact"):
+        # x / (1 + expf(-c x)), c = 1 or 1.702, on the class where fp32 leaves no choice: 0 -> 0; x >= 20 -> x (expf < 2^-25: the
+        # denominator is 1); x <= -104 -> -0 (expf overflows to +inf) -- NOT the identity, so a launch without its activation differs
+        assert bool(((v == 0) | (v >= 20) | (v <= -104)).all()), "exact SiLU / quick-GELU: 0, at least 20, or at most -104"
+        assert bool((v == 0).any()) and bool((v >= 20).any()) and bool((v <= -104).any())
+        v = torch.where(v <= -104, torch.zeros_like(v), v)
+    elif p.get("silu"):
+        v = v * torch.sigmoid(v)
+    elif p.get("qgelu"):
+        v = v * torch.sigmoid(1.702 * v)
     rot = p.get("rot")
     if mut == "rot_no_modulo" and (rot is None or M <= rot["tokens"]):
         return None
@@ -126,7 +153,8 @@ def epilogue(acc, p, mut=None, exact=False):
     return v
 
 
-def _store(pre, p, mut):
+def _store(pre, p, mut, geom=GEOM):
+    BM, BN = geom["BM"], geom["BN"]
     if mut == "truncating_stores":
         return trunc16(pre)
     out = r16(pre)
@@ -140,7 +168,7 @@ def _store(pre, p, mut):
 
 
 # ------------------------------------------------------------------------------------------- GEMM
-def gemm(p, mut=None, exact=False):
+def gemm(p, mut=None, exact=False, geom=GEOM):
     """p: a [M, K1], a2 [M, K - K1] or None, w [N, K] (GEGLU: NATURAL order, value rows | gate rows), bias, geglu, rowvec +
     rows_per_batch, rot (dict table, tokens, off, head_dim, rot_dim, cols), col_scale (factor, cols), res, S (K slices, for the
     slice mutations), a2_buf / a2_off / lda (the buffer a2 is a view of, for a2_read_with_lda).
@@ -163,24 +191,25 @@ def gemm(p, mut=None, exact=False):
         _exact_pre(K, float(A.abs().max()), float(w.abs().max()), *[float(p[k].abs().max()) for k in ("bias", "rowvec", "res") if p.get(k) is not None])
         assert_exact_sums(A, w, *[p[k].expand(M, N) for k in ("bias", "res") if p.get(k) is not None], what="t320 gemm")
     acc = A @ w.t()
-    r0 = 64 if M > 64 else 0                                               # wave (1, 1) of tile 0 (wave (0, 1) of a one-wave-row tile)
-    rs = slice(r0, min(r0 + 64, M))
+    WTM, (c0, c1), (fr0, fc0) = geom["WTM"], geom["wave_cols"], geom["frag"]
+    r0 = WTM if M > WTM else 0                                             # wave (1, 1) of tile 0 (wave (0, 1) of a one-wave-row tile)
+    rs = slice(r0, min(r0 + WTM, M))
     if mut == "drop_kstep_one_wave":
         acc = acc.clone()
-        acc[rs, 160:320] -= A[rs, K - BK:] @ w[160:320, K - BK:].t()
+        acc[rs, c0:c1] -= A[rs, K - BK:] @ w[c0:c1, K - BK:].t()
     S = p.get("S", 1)
     if mut in ("slice_last_twice", "slice0_skipped"):
         if S < 2:
             return None
         k0, k1 = slice_bounds(K, S, S - 1 if mut == "slice_last_twice" else 0)
-        fr, fc = slice(r0 + 16, min(r0 + 32, M)), slice(160 + 48, 160 + 64)    # quad (i 1, j 3) of that wave: a 16 x 16 fragment
+        fr, fc = slice(r0 + fr0, min(r0 + fr0 + 16, M)), slice(fc0, fc0 + 16)    # quad (i 1, j 3) of that wave: a 16 x 16 fragment
         part = A[fr, k0:k1] @ w[fc, k0:k1].t()
         acc = acc.clone()
         acc[fr, fc] += part if mut == "slice_last_twice" else -part
-    pre = epilogue(acc, p, mut, exact)
+    pre = epilogue(acc, p, mut, exact, geom)
     if pre is None:
         return None
-    out = _store(pre, p, mut)
+    out = _store(pre, p, mut, geom)
     return None if out is None else dict(pre=pre, out=out)
 
 
@@ -212,7 +241,7 @@ def conv_gather(x, w, stride, pad_after, border_valid=False):
     return out
 
 
-def conv(p, mut=None, exact=False):
+def conv(p, mut=None, exact=False, geom=GEOM):
     """p: x [n, Ci, H, W], w [Co, Ci, 3, 3], stride, pad_after, up (True: nearest-2x in front, the four phase convs of ops.conv_up2x),
     and the epilogue keys of gemm().  Returns dict(pre, out) over channels-last rows [n Ho Wo, Co]"""
     x, w = p["x"], p["w"]
@@ -238,10 +267,10 @@ def conv(p, mut=None, exact=False):
     acc = _rows_cl(full)
     if mut == "pad_after_border_valid":
         acc = conv_gather(x, w, stride, pad_after, border_valid=True)
-    pre = epilogue(acc, p, mut, exact)
+    pre = epilogue(acc, p, mut, exact, geom)
     if pre is None:
         return None
-    out = _store(pre, p, mut)
+    out = _store(pre, p, mut, geom)
     return None if out is None else dict(pre=pre, out=out)
 
 

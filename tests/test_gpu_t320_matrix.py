@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from tests import t320_ref as R
+from tests.gemm_spy import spy  # noqa: F401  (the fixture)
 from tests.test_gpu_f16_matrix import _eq, _ints, _store
 from tests.test_gpu_t320 import _sync_is_zero
 from tests.test_gpu_train_matrix import _gapped, _gaps_hold
@@ -32,43 +33,7 @@ T320, K_T320 = R.T320, R.KERNEL_T320
 
 
 # =========================================================================================== the plan of every launch
-class _Spy:
-    """stands in for the loaded library: seer_gemm_bf16 records seer_gemm_plan of the descriptor it is handed (and a copy of it), then
-    launches; everything else passes through"""
-
-    def __init__(self, lib):
-        self._real, self.plans, self.descs, self.tweak, self.keep = lib, [], [], None, []
-
-    def __getattr__(self, name):
-        return getattr(self._real, name)
-
-    def plan_of(self, d):
-        out = (C_.c_int32 * 5)()
-        assert self._real.seer_gemm_plan(C_.byref(d), out) == 0
-        return list(out)
-
-    def seer_gemm_bf16(self, dref, stream):
-        d = dref._obj
-        self.plans.append(self.plan_of(d))
-        self.descs.append(type(d).from_buffer_copy(d))
-        return self._real.seer_gemm_bf16(dref, stream)
-
-
-@pytest.fixture
-def spy(monkeypatch):
-    from seervideoldm_amd import ops
-    s = _Spy(ops._lib.load())
-    monkeypatch.setattr(ops._lib, "load", lambda: s)
-    launch = ops._launch_gemm
-
-    def tweaked(d, *a, **kw):
-        if s.tweak is not None:
-            s.tweak(d)                                                   # a field the wrappers do not expose (a phase launch with splits)
-        return launch(d, *a, **kw)
-    monkeypatch.setattr(ops, "_launch_gemm", tweaked)
-    return s
-
-
+# (the `spy` fixture: tests/gemm_spy.py, shared with tests/test_gpu_gemm_epi_matrix.py)
 def _ran_t320(spy, S, what):
     assert spy.plans[-1] == [0, K_T320, T320, S, 0], f"{what}: planned {spy.plans[-1]}, not the 256 x 320 kernel with {S} slice(s)"
 
