@@ -395,6 +395,34 @@ int seer_groupnorm_apply_fx(const void* x1, int32_t C1, const void* x2, int32_t 
  * for GroupNorm sources without accumulated producer sums (resnet.py:179,197, attention.py:133 normalise over all frames). */
 int seer_groupnorm_stats_fx(const void* x, int32_t C, int32_t batch, int64_t rows_per_batch, int64_t* fx, int32_t dtype,
                             void* stream);
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net", CVPR 2024; diffusers' apply_freeu / fourier_filter with threshold 1) on a
+ * decoder resnet's two inputs in front of their channel concat, ONE launch (csrc/freeu.hip).  Token-major activations of `images`
+ * images of H x W pixels, rows = images * H * W, 16-bit storage type `dtype`, fp32 arithmetic for either type (diffusers runs a
+ * half-precision FFT on fp16 power-of-two planes: a stated difference):
+ *   backbone  x [rows][Cx] -> x_out:  x_out[r][c] = rnd(x[r][c] * b) for c < Cx / 2, the bits of x[r][c] for the other channels;
+ *   skip      skip [rows][Cs] -> skip_out, per (image, channel) over that image's H x W plane:
+ *                 skip_out[h][w] = rnd(skip[h][w] + (s - 1) / (H W) * sum_{kh in K_H, kw in K_W} Re(X[kh][kw] e^{+2 pi i (kh h / H + kw w / W)}))
+ *                 X[kh][kw]      = sum_{h, w} skip[h][w] e^{-2 pi i (kh h / H + kw w / W)}
+ *             K_N = the distinct values of {0, -1 mod N} ({0} for N = 1, {0, 1} for N = 2): Re ifft2(mask * fft2(skip)) with the mask
+ *             s on the fft-shifted block [H/2 - 1 : H/2 + 1, W/2 - 1 : W/2 + 1] and 1 elsewhere.
+ * Either pair may be NULL (both pointers): the other half runs alone, with the bits it has in the joint launch.
+ *   params    fp32 [2] = (b, s), DEVICE memory, read by the kernel: a captured launch follows a change of the values.
+ *   twiddles  fp32 [2][2 H + 2 W]: row 0 = cos(2 pi h / H) (H values), sin(2 pi h / H), cos(2 pi w / W) (W values), sin(2 pi w / W) of
+ *             the caller's float64 table (exact 0 / +-1 at the multiples of a quarter turn) rounded to fp32, row 1 = what that
+ *             rounding left (float64 value - row 0, as fp32); the kernel evaluates no sin or cos.
+ * The skip half runs in two-float arithmetic (a value = hi + lo of two fp32 numbers, error-free sums and products): a correction kept
+ * in one fp32 number is too coarse for fp16 storage where skip and correction cancel.  The result is rounded to fp32 once and then to
+ * the storage type.
+ * A workgroup owns an image and 512 channels, a thread 8 channels, a wave every fourth row.  Order of summation of a coefficient, per
+ * channel: the pixels of a row left to right (compensated: the sum and the sum of its rounding errors), the wave's rows top to bottom,
+ * the four waves' partials in wave order (through LDS; no atomics).  An element's bits depend on its own (image, channel) plane, H, W,
+ * the table and the scalars only.
+ * x_out == x (in place, the same address) is allowed; the skip is read twice and skip_out must not overlap it.
+ * SEER_EINVAL, nothing launched: both pairs NULL, or half a pair; an output that overlaps an input of the other pair, the other
+ * output, or its own input other than x_out == x; images, H or W < 1; rows != images * H * W; Cx or Cs not a positive multiple of 8;
+ * an activation pointer off 16 bytes, params or twiddles NULL or off 4 bytes; more than 65535 channel slices. */
+int seer_freeu(const void* x, void* x_out, int32_t Cx, const void* skip, void* skip_out, int32_t Cs, int64_t rows, int32_t images,
+               int32_t H, int32_t W, const float* params, const float* twiddles, int32_t dtype, void* stream);
 /* The feed-forward of a transformer block at the 320-channel level and the transformer's proj_out, ONE launch (csrc/ff_fused.hip):
  *     y = x + [Wp | Wp W2] [h | g] + bcat,   g = GEGLU(LayerNorm(h; gamma, beta, eps) W1^T + b1)
  * i.e. norm3 -> ff.net.0 -> ff.net.2 + residual -> proj_out + residual (seer/models/attention.py:231-248, 308-327, 742-747,

@@ -143,6 +143,7 @@ SIGNATURES = {
     "seer_groupnorm_apply_fx": ([_vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _i32, _i64, _i32, _f64, _f32, _vp, _vp, _i32, _vp, _vp, _i32, _vp],
                                  C.c_int),
     "seer_groupnorm_stats_fx": ([_vp, _i32, _i32, _i64, _vp, _i32, _vp], C.c_int),
+    "seer_freeu": ([_vp, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _vp], C.c_int),
     "seer_ff_fused_c320": ([_vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i32, _i64, _vp, _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
                             _vp, _i32, _vp], C.c_int),
     "seer_rowchain_c320": ([C.POINTER(RowChainDesc), _vp], C.c_int),

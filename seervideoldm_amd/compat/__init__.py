@@ -26,6 +26,9 @@ is, treat the UNet's output as the velocity v (a model fine-tuned with `predicti
 `SEER_COMPAT_GUIDANCE_RESCALE=0.7` (read by `install()`, or `install(guidance_rescale=0.7)`) makes that sampler rescale its guided
 output to the conditional branch's std, blended by that factor (Lin et al. 2023; a number in [0, 1], how v-models are sampled);
 unset or 0, nothing is rescaled.
+`SEER_COMPAT_FREEU="0.9,0.2,1.2,1.4"` (read by `install()`, or `install(freeu=(0.9, 0.2, 1.2, 1.4))`: s1, s2, b1, b2 in diffusers'
+order) makes the aliased `SeerUNet` one that comes with FreeU enabled at those values (`SeerUNet.enable_freeu`; Si et al. 2024);
+unset or empty, the class is the product's own.  Inference scripts only: `SeerTrainer` refuses such a model.
 `SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
 `CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
 then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
@@ -71,6 +74,8 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
                 mod.DDIMSampler = _v_sampler(mod.DDIMSampler)
             if spec.name == "ldm.models.diffusion.ddim_video" and _rescale:
                 mod.DDIMSampler = _rescale_sampler(mod.DDIMSampler, _rescale)
+            if spec.name == "seer.models.unet_3d_condition" and _freeu is not None:
+                mod.SeerUNet = _freeu_unet(mod.SeerUNet, _freeu)
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -118,11 +123,36 @@ def _rescale_sampler(cls, phi: float):
     return _rescale_samplers[cls, phi]
 
 
+_freeu = None               # (s1, s2, b1, b2) while the aliased SeerUNet comes with FreeU enabled
+_freeu_unets = {}           # (SeerUNet class, values) -> its subclass whose instances have FreeU enabled at those values
+
+
+def _parse_freeu(text):
+    """"s1,s2,b1,b2" -> four finite floats; a ValueError that names the variable otherwise"""
+    try:
+        vals = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        vals = ()
+    if len(vals) != 4 or any(v != v or v in (float("inf"), float("-inf")) for v in vals):
+        raise ValueError(f"SEER_COMPAT_FREEU={text!r}: four finite numbers s1,s2,b1,b2, such as 0.9,0.2,1.2,1.4")
+    return vals
+
+
+def _freeu_unet(cls, vals):
+    """`cls` whose constructor ends with enable_freeu(*vals), as _v_sampler does for the prediction type"""
+    if (cls, vals) not in _freeu_unets:
+        def __init__(self, *args, **kwargs):
+            cls.__init__(self, *args, **kwargs)
+            self.enable_freeu(*vals)
+        _freeu_unets[cls, vals] = type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__, "__module__": cls.__module__})
+    return _freeu_unets[cls, vals]
+
+
 _clip_saved = None          # (transformers module, its own CLIPTextModel) while the native text encoder stands in
 
 
 def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None,
-            prediction: Optional[str] = None, guidance_rescale: Optional[float] = None) -> None:
+            prediction: Optional[str] = None, guidance_rescale: Optional[float] = None, freeu=None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
     `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler, "dpmpp" its DPMSolverSampler; anything else keeps
     DDIMSampler.
@@ -130,9 +160,11 @@ def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str
     to prediction_type="v_prediction"; "epsilon" or nothing keeps it as it is; anything else is train.py:376's ValueError.
     `guidance_rescale` (default: the environment's SEER_COMPAT_GUIDANCE_RESCALE, 0 when unset) in (0, 1] makes that class one whose
     constructor defaults to guidance_rescale of that value; 0 keeps it as it is; anything outside [0, 1] is a ValueError.
+    `freeu` (default: the environment's SEER_COMPAT_FREEU, "s1,s2,b1,b2") = four finite numbers makes the aliased SeerUNet a class whose
+    instances have FreeU enabled at those values; nothing keeps the class as it is; malformed text is a ValueError naming the variable.
     `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
     CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
-    global _sampler, _prediction, _rescale, _clip_saved
+    global _sampler, _prediction, _rescale, _clip_saved, _freeu
     _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
     _prediction = (os.environ.get("SEER_COMPAT_PREDICTION", "") if prediction is None else prediction).strip().lower()
     if _prediction not in ("", "epsilon", "v_prediction"):
@@ -140,6 +172,11 @@ def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str
     from seervideoldm_amd.ops import check_guidance_rescale
     _rescale = check_guidance_rescale((os.environ.get("SEER_COMPAT_GUIDANCE_RESCALE", "").strip() or 0.)
                                       if guidance_rescale is None else guidance_rescale)
+    if freeu is None:
+        text = os.environ.get("SEER_COMPAT_FREEU", "").strip()
+        _freeu = _parse_freeu(text) if text else None
+    else:
+        _freeu = _parse_freeu(",".join(repr(float(v)) for v in freeu))
     if (os.environ.get("SEER_COMPAT_CLIP", "") if clip is None else clip).strip().lower() == "native" and _clip_saved is None:
         import transformers
         from seervideoldm_amd import CLIPTextEncoder

@@ -516,7 +516,7 @@ class DDIMSampler(object):
         key = (kind, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv,
                *(() if temperature is None else (float(temperature),)),
                *(() if self.prediction_type == "epsilon" else (self.prediction_type,)),
-               *(("rescale", float(phi)) if cfg and phi > 0. else ()))
+               *(("rescale", float(phi)) if cfg and phi > 0. else ()), *getattr(eng, "freeu_key", ()))
         G = eng.graph_get(key)
         if G is None:
             G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L,

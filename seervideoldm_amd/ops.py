@@ -617,6 +617,63 @@ def groupnorm_stats_fx(x: torch.Tensor, batch: int, arena: Optional[FxArena] = N
     return ColSumsFx(buf, C_)
 
 
+def freeu_twiddles(H: int, W: int) -> torch.Tensor:
+    """the twiddle table of seer_freeu as float64 [2 H + 2 W] on the host: cos, sin of 2 pi h / H, then cos, sin of 2 pi w / W.  The
+    index is reduced first: a multiple of a quarter turn gives exactly 0 or +-1 (math.cos(math.pi / 2) is 6e-17, and an integer plane
+    would no longer filter to exact values)."""
+    import math
+
+    def axis(N):
+        c, s = [], []
+        for k in range(N):
+            if (4 * k) % N == 0:
+                q = 4 * k // N
+                c.append((1.0, 0.0, -1.0, 0.0)[q]); s.append((0.0, 1.0, 0.0, -1.0)[q])
+            else:
+                c.append(math.cos(2.0 * math.pi * k / N)); s.append(math.sin(2.0 * math.pi * k / N))
+        return c + s
+    return torch.tensor(axis(H) + axis(W), dtype=torch.float64)
+
+
+def freeu_table(H: int, W: int) -> torch.Tensor:
+    """the table as seer_freeu reads it: fp32 [2, 2 H + 2 W], row 0 the float64 twiddles rounded to fp32, row 1 what that rounding
+    left (the kernel's two-float arithmetic takes a twiddle as hi + lo)"""
+    t = freeu_twiddles(H, W)
+    hi = t.to(torch.float32)
+    return torch.stack([hi, (t - hi.double()).to(torch.float32)])
+
+
+_freeu_tables: dict = {}
+
+
+def freeu(x: Optional[torch.Tensor], skip: Optional[torch.Tensor], params: torch.Tensor, H: int, W: int):
+    """FreeU on a decoder resnet's inputs, one launch (seer_freeu): x [rows, Cx] with its first Cx // 2 channels times b, skip
+    [rows, Cs] with the lowest frequencies of every (image, channel) H x W plane times s; rows = images * H * W, params = fp32 (b, s)
+    on the device (the kernel reads it: a captured launch follows the values).  Either tensor may be None.  Returns (x', skip'), NEW
+    tensors without column sums: the GroupNorm behind them takes its statistics pass."""
+    ref = x if x is not None else skip
+    if ref is None:
+        raise ValueError("freeu: x or skip")
+    dt = _req16(ref, "x")
+    for t, name in ((x, "x"), (skip, "skip")):
+        if t is not None:
+            _req16(t, name, ref)
+            assert t.dim() == 2 and t.is_contiguous() and t.shape[0] == ref.shape[0], name
+    _req(params, torch.float32, "params")
+    assert params.numel() == 2 and params.is_contiguous()
+    rows = ref.shape[0]
+    assert H >= 1 and W >= 1 and rows % (H * W) == 0, (rows, H, W)
+    key = (H, W, ref.device)
+    tw = _freeu_tables.get(key)
+    if tw is None:
+        tw = _freeu_tables[key] = freeu_table(H, W).to(ref.device)
+    xo = None if x is None else torch.empty_like(x)
+    so = None if skip is None else torch.empty_like(skip)
+    check(_lib.load().seer_freeu(_p(x), _p(xo), 0 if x is None else x.shape[1], _p(skip), _p(so), 0 if skip is None else skip.shape[1],
+                                 rows, rows // (H * W), H, W, _p(params), _p(tw), dt, _stream()), "seer_freeu")
+    return xo, so
+
+
 def groupnorm_stats_from_fx(fx1: ColSumsFx, fx2: Optional[ColSumsFx], batch: int, groups: int, stats: torch.Tensor) -> torch.Tensor:
     """stats[b][g] = (sum, sumsq) from accumulated column sums (torch ops; the fall-back of a layout groupnorm_apply_fx refuses)."""
     v = fx1.totals() if fx2 is None else torch.cat([fx1.totals(), fx2.totals()], dim=1)

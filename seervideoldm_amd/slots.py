@@ -411,7 +411,8 @@ class SlotSampler:
         G = None
         if not self._capture_refused and capture_engine(unet, self.ops, self.device) is not None:
             key = (self._kind, self.slots, self.shape, self.f1, self.model_cond_frame, L, tuple(ctx.shape), eng.inv,
-                   *(() if self.prediction_type == "epsilon" else (self.prediction_type,)), *(("rescale",) if self.rescale else ()))
+                   *(() if self.prediction_type == "epsilon" else (self.prediction_type,)), *(("rescale",) if self.rescale else ()),
+                   *getattr(eng, "freeu_key", ()))
             G = eng.graph_get(key)
             if G is None or G["x"] is not self._x:   # (another SlotSampler of the same key owns that entry: this one captures its own)
                 G = self._capture(eng, key, model)

@@ -206,6 +206,9 @@ class SeerTrainer:
         self.lr, self.betas, self.weight_decay, self.eps, self.max_grad_norm = lr, betas, weight_decay, eps, max_grad_norm
         self.pg = process_group
         self.unet, self.fstext = unet, fstext
+        if getattr(unet, "_freeu", None) is not None:
+            # FreeU is an inference-time operation (and the trainer walks its own schedule, which knows nothing of it)
+            raise ValueError("SeerTrainer: the UNet has FreeU enabled (enable_freeu); call disable_freeu() before fine-tuning")
         self.eng = _Engine(unet, ops=ops, fold_ln=False)
         self.device = self.eng.device
         # Min-SNR-gamma loss weighting (`--snr_gamma` of the diffusers training scripts; Hang et al., ICCV 2023): sample b of a batch

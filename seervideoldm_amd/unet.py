@@ -100,6 +100,7 @@ class SeerUNet(nn.Module):
         # the storage type only -- not on the batch it came in, the CFG layout, the rank / frame-shard layout or the device's CU count.
         # True / False here or as an attribute before the first forward; None = the environment's SEER_LAYOUT_INVARIANT=1 (_Engine)
         self.layout_invariant = layout_invariant
+        self._freeu: Optional[Tuple[float, float, float, float]] = None     # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
 
     # ---- construction / weights -------------------------------------------------------------------------------
     @classmethod
@@ -152,6 +153,7 @@ class SeerUNet(nn.Module):
         dev = next(self.parameters()).device.type
         with torch.autocast(device_type=dev if dev in ("cuda", "cpu") else "cuda", enabled=False):     # fp32 weight algebra stays fp32
             self._engine = _Engine(self, ops=self._ops_backend, shard=self._shard, dtype=dtype)
+        self._engine.set_freeu(self._freeu)
         return self
 
     # ---- toggles of the reference surface ---------------------------------------------------------
@@ -172,6 +174,27 @@ class SeerUNet(nn.Module):
 
     def _set_gradient_checkpointing(self, module, value=False):
         pass
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """FreeU (Si et al., CVPR 2024), diffusers' name and argument order: in every resnet of up_blocks.0 (b1, s1) and up_blocks.1
+        (b2, s2) the first half of the backbone's channels is scaled by b and the lowest spatial frequencies of the skip connection
+        by s, in front of their concat (ops.freeu, one launch per resnet).  Inference only.  The four values live in a device buffer
+        of the engine: calling this again with other values rewrites it in place and a captured step follows without a recapture;
+        on <-> off selects another captured graph."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        for name, v in zip(("s1", "s2", "b1", "b2"), vals):
+            if v != v or v in (float("inf"), float("-inf")):
+                raise ValueError(f"enable_freeu: {name} = {v!r} is not finite")
+        self._freeu = vals
+        if self._engine is not None:
+            self._engine.set_freeu(vals)
+        return self
+
+    def disable_freeu(self):
+        self._freeu = None
+        if self._engine is not None:
+            self._engine.set_freeu(None)
+        return self
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -344,6 +367,36 @@ class _Engine:
         self._rec = None                # _SegmentRecorder while a segmented capture is running
         self._attn_list = None          # list that collects the text cross-attention scores of a return_attn forward
         self._attn_wanted = ()
+        self.freeu_on = False           # FreeU (SeerUNet.enable_freeu): set_freeu
+        self._freeu_buf = None          # fp32 (b1, s1, b2, s2) on the device, read by the seer_freeu launches
+
+    # ---- FreeU ----------------------------------------------------------------------------------------------------------
+    def set_freeu(self, vals) -> None:
+        """vals = (s1, s2, b1, b2) turns FreeU on, None off.  The device buffer is made once and REWRITTEN in place afterwards: the
+        captured steps read it by address."""
+        self.freeu_on = vals is not None
+        if vals is None:
+            return
+        s1, s2, b1, b2 = vals
+        host = torch.tensor([b1, s1, b2, s2], dtype=torch.float32)
+        if self._freeu_buf is None:
+            self._freeu_buf = host.to(self.device)
+        else:
+            self._freeu_buf.copy_(host)
+
+    @property
+    def freeu_key(self) -> Tuple:
+        """what FreeU adds to the key of a captured step: nothing while it is off (the keys are what they were), one word while it
+        is on -- the values are no part of it"""
+        return ("freeu",) if self.freeu_on else ()
+
+    def _freeu_params(self, p):
+        """the (b, s) pair of resnet `p` on the device, or None: FreeU is off, or `p` is outside up_blocks.0 / up_blocks.1"""
+        if not self.freeu_on:
+            return None
+        if p.startswith("up_blocks.0."):
+            return self._freeu_buf[0:2]
+        return self._freeu_buf[2:4] if p.startswith("up_blocks.1.") else None
 
     # ---- captured graphs: ONE cache, ONE eviction policy ------------------------------------------------------------
     # Every entry owns a private graph memory pool with a full set of step activations, so the cache is small and evicts the
@@ -563,6 +616,11 @@ class _Engine:
         B, Fr, H, W = geo
         rows_pb = Fr * H * W
         cb = self._cb(B, rows_pb)          # outputs that feed a GroupNorm leave their column sums behind
+        fu = self._freeu_params(p) if skip is not None else None
+        if fu is not None:
+            # FreeU, in front of everything the resnet does with its inputs: a new pair without column sums (norm1 takes its
+            # statistics pass); per (frame, channel), so batch, CFG and frame-shard layouts are untouched
+            x, skip = ops.freeu(x, skip, fu, H, W)
         h = self._gn(x, skip, B, rows_pb, p + ".norm1", self.eps, True)
         off, n = self.temb_slices[p]
         temb = self._temb[:, off:off + n]
@@ -895,7 +953,7 @@ class _Engine:
         """hipGraph replay of the shape-static step: ~1.3k launches -> one graph launch, or -- frame-sharded -- one graph
         launch per stretch between two collectives (GroupNorm statistics / K|V exchanges stay eager torch.distributed
         calls on the same stream)."""
-        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape), self.inv)
+        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape), self.inv, *self.freeu_key)
         g = self.graph_get(key)
         if g is None:
             # warm up eagerly (fills the K/V and rotary caches, creates process groups, lets allocations settle), then capture
