@@ -36,7 +36,8 @@ extern "C" {
 #define SEER_DT_F16 1
 
 /* library / device info ------------------------------------------------------------------- */
-int seer_abi_version(void);                 /* bumps when a struct below changes */
+#define SEER_ABI_VERSION 27                 /* bumps when a struct or an entry point below changes */
+int seer_abi_version(void);                 /* SEER_ABI_VERSION of the header the library was built from */
 const char* seer_strerror(int code);        /* host string */
 const char* seer_build_arch(void);          /* "gfx950" */
 
@@ -215,7 +216,7 @@ int32_t seer_gemm_colsum_rows(const seer_gemm_desc* desc /* host */);
 /* colsum_fx form of this exact launch for tensors of rows_per_batch rows per batch element: returns the rows one partial covers
  * (rows_per_batch must be a multiple; 0: the launch cannot accumulate column sums) and sets *reps = the replica count to
  * allocate and pass as colsum_fx_reps */
-int32_t seer_gemm_colsum_fx_layout(const seer_gemm_desc* desc /* host */, int32_t rows_per_batch, int32_t* reps);
+int32_t seer_gemm_colsum_fx_layout(const seer_gemm_desc* desc /* host */, int32_t rows_per_batch, int32_t* reps /* host */);
 /* 1 when this exact launch can accumulate the row statistics of its output (desc->rowstat), else 0 */
 int32_t seer_gemm_rowstat_ok(const seer_gemm_desc* desc /* host */);
 /* 1 when this exact launch (ln_rowstat / ln_wsum set) applies the folded LayerNorm, 0 when the caller has to run
@@ -240,7 +241,7 @@ int64_t seer_gemm_sync_bytes(const seer_gemm_desc* desc /* host */);
 #define SEER_GEMM_REDUCE_COLSUM 2         /* + per-tile column sums (desc.colsum) */
 #define SEER_GEMM_REDUCE_COLSUM_FX64 3    /* + accumulated column sums (desc.colsum_fx) on 64-row blocks */
 #define SEER_GEMM_REDUCE_COLSUM_FX32 4    /* ... on 32-row blocks */
-int seer_gemm_plan(const seer_gemm_desc* desc /* host */, int32_t out[5]);
+int seer_gemm_plan(const seer_gemm_desc* desc /* host */, int32_t out[5] /* host */);
 
 /* ---- attention -------------------------------------------------------------------------- */
 /* Replaces xformers.ops.memory_efficient_attention as called from CrossAttention

@@ -49,15 +49,8 @@ TILE_CODES = list(range(0, 4)) + list(range(5, 23)) + [77]          # every code
 
 
 def bind(path):
-    lib = C.CDLL(str(path))
-    D = C.POINTER(_lib.GemmDesc)
-    for name, res in (("seer_gemm_workspace_bytes", C.c_int64), ("seer_gemm_sync_bytes", C.c_int64),
-                      ("seer_gemm_colsum_rows", C.c_int32), ("seer_gemm_rowstat_ok", C.c_int32), ("seer_gemm_lnfold_ok", C.c_int32)):
-        getattr(lib, name).argtypes, getattr(lib, name).restype = [D], res
-    lib.seer_gemm_colsum_fx_layout.argtypes, lib.seer_gemm_colsum_fx_layout.restype = [D, C.c_int32, C.POINTER(C.c_int32)], C.c_int32
-    if hasattr(lib, "seer_gemm_plan"):
-        lib.seer_gemm_plan.argtypes, lib.seer_gemm_plan.restype = [D, C.POINTER(C.c_int32)], C.c_int
-    return lib
+    """a parent's library, bound by this tree's header for the entry points it exports (one that predates seer_gemm_plan has none)"""
+    return _lib.bind(C.CDLL(str(path)))
 
 
 def to_struct(d: dict) -> _lib.GemmDesc:

@@ -22,15 +22,12 @@ y = torch.empty_like(x)
 gamma, beta = 1 + 0.1 * r(Cc), 0.1 * r(Cc)
 w1, b1 = r(2 * inner, Cc, sc=Cc ** -0.5).to(bf16), 0.1 * r(2 * inner)
 wcat, bcat = r(Cc, Cc + inner, sc=(Cc + inner) ** -0.5).to(bf16), 0.1 * r(Cc)
-from seervideoldm_amd import ops  # noqa: E402
+from seervideoldm_amd import _lib, ops  # noqa: E402
 
 w1f, wcf = ops.ff_fused_pack(w1, wcat)
 flop = 2.0 * M * Cc * 2 * inner + 2.0 * M * (Cc + inner) * Cc
 NAMES = {1: "W1 stream", 2: "[Wp|WpW2] stream", 4: "MFMAs", 8: "GELU", 16: "fragment reads"}
 masks = [int(a) for a in sys.argv[1:]] or [0]
-vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-# a, lda, wof, bo (no prologue: NULL), h .. colsum_tiles, dtype (SEER_DT_BF16 = 0), stream
-FF_ARGTYPES = [vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, i64, vp, vp, C.c_float, vp, vp, vp, vp, vp, i64, i32, vp, i32, vp]
 out = ROOT / "gpurun_out" / "ffprobe"
 out.mkdir(parents=True, exist_ok=True)
 for mask in masks:
@@ -38,12 +35,10 @@ for mask in masks:
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", f"-I{ROOT / 'include'}",
                     f"-I{ROOT / 'seervideoldm_amd' / 'csrc'}", "-fno-gpu-rdc", f"-DFF_PROBE={mask}",
                     str(ROOT / "seervideoldm_amd" / "csrc" / "ff_fused.hip"), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
-    fn = lib.seer_ff_fused_c320
-    fn.argtypes = FF_ARGTYPES
+    fn = _lib.bind(C.CDLL(str(so)), ["seer_ff_fused_c320"]).seer_ff_fused_c320
     st = torch.cuda.current_stream().cuda_stream
 
-    def call():
+    def call():                  # a, lda, wof, bo NULL: no prologue; dtype 0 = SEER_DT_BF16
         rc = fn(None, 0, None, None, h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
                 b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, 0, st)
         assert rc == 0, rc
@@ -65,9 +60,8 @@ so = out / "ff_stamps.so"
 subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", f"-I{ROOT / 'include'}",
                 f"-I{ROOT / 'seervideoldm_amd' / 'csrc'}", "-fno-gpu-rdc", "-DFF_STAMPS",
                 str(ROOT / "seervideoldm_amd" / "csrc" / "ff_fused.hip"), "-o", str(so)], check=True)
-lib = C.CDLL(str(so))
+lib = _lib.bind(C.CDLL(str(so)), ["seer_ff_fused_c320"])
 fn = lib.seer_ff_fused_c320
-fn.argtypes = FF_ARGTYPES
 for _ in range(3):
     assert fn(None, 0, None, None, h.data_ptr(), Cc, x.data_ptr(), Cc, y.data_ptr(), Cc, M, gamma.data_ptr(), beta.data_ptr(), 1e-5, w1f.data_ptr(),
               b1.data_ptr(), wcf.data_ptr(), bcat.data_ptr(), None, 0, 0, None, 0, st) == 0

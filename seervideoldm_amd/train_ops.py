@@ -114,6 +114,12 @@ def transpose(x: torch.Tensor, pad_to: int = 64) -> torch.Tensor:
     return y
 
 
+def pack_transpose_items(items: "Sequence[dict]") -> bytes:
+    """the item table of seer_transpose_batched_bf16 as the kernel reads it: one seer_transpose_item (_lib.TransposeItem) per
+    dict of field values (x, y, rows, ldy, tile0, cols, ldx, tiles_r; `reserved` stays 0), in order"""
+    return bytes((_lib.TransposeItem * len(items))(*(_lib.TransposeItem(**it) for it in items)))
+
+
 class TransposePlan:
     """`run()` transposes every x_i [rows, cols] (bf16, row-strided views) into y_i [cols, round_up(rows, 64)] in ONE launch
     (seer_transpose_batched_bf16).  The outputs are views of one arena and live as long as the plan; the item table is built
@@ -139,11 +145,10 @@ class TransposePlan:
             assert y.data_ptr() % 16 == 0
             self.outputs.append(y)
             tiles_r = ldy // 64
-            # seer_transpose_item: x, y, rows, ldy, tile0 (int64 x 5), cols, ldx, tiles_r, reserved (int32 x 4) = 56 bytes
-            table.append((x.data_ptr(), y.data_ptr(), rows, ldy, tile0, cols | (x.stride(0) << 32), tiles_r))
+            table.append(dict(x=x.data_ptr(), y=y.data_ptr(), rows=rows, ldy=ldy, tile0=tile0, cols=cols, ldx=x.stride(0), tiles_r=tiles_r))
             tile0 += tiles_r * ((cols + 63) // 64)
         self.total_tiles, self.n = tile0, len(table)
-        self.table = torch.tensor(table, dtype=torch.int64).to(dev)   # [n, 7] int64 = the C struct (little endian)
+        self.table = torch.frombuffer(bytearray(pack_transpose_items(table)), dtype=torch.uint8).to(dev)
 
     def run(self) -> None:
         check(_lib.load().seer_transpose_batched_bf16(_p(self.table), self.n, self.total_tiles, _stream()),

@@ -53,11 +53,21 @@ def test_one_entry_point_per_kernel(lib_path):
     assert exported == names
 
 
-def test_desc_struct_layout_matches_header():
-    """field order of the ctypes structs == field order of the C structs (parsed from the header)."""
+STRUCTS = {"seer_gemm_desc": "GemmDesc", "seer_attn_desc": "AttnDesc", "seer_attn_bwd_desc": "AttnBwdDesc",
+           "seer_rowchain_desc": "RowChainDesc", "seer_tn_item": "TnItem", "seer_colfinal_item": "ColfinalItem",
+           "seer_transpose_item": "TransposeItem"}
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """all seven structs: field names and order == the header's (read here by a parser of the test's own), and sizeof, every
+    field's offset and size == what gcc makes of the header (a C program generated from the classes prints them)"""
+    import subprocess
     from seervideoldm_amd import _lib
     text = HEADER.read_text()
-    for cname, cls in (("seer_gemm_desc", _lib.GemmDesc), ("seer_attn_desc", _lib.AttnDesc), ("seer_rowchain_desc", _lib.RowChainDesc)):
+    assert _lib.CLASS_NAMES == STRUCTS and len(re.findall(r"typedef struct", text)) == len(STRUCTS)
+    lines, want = [], {}
+    for cname, pyname in STRUCTS.items():
+        cls = getattr(_lib, pyname)
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), text, flags=re.S).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
@@ -69,6 +79,75 @@ def test_desc_struct_layout_matches_header():
             for nm in names.split(","):
                 fields.append(nm.strip().lstrip("*").strip())
         assert fields == [f[0] for f in cls._fields_], cname
+        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        want[cname] = ctypes.sizeof(cls)
+        for f in fields:
+            lines.append(f'    printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));')
+            want[f"{cname}.{f}"] = (getattr(cls, f).offset, getattr(cls, f).size)
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "seer_hip.h"\nint main(void) {\n' + "\n".join(lines)
+                   + "\n    return 0;\n}\n")
+    r = subprocess.run(["gcc", "-std=c99", "-O1", f"-I{HEADER.parent}", str(src), "-o", str(tmp_path / "layout")],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(tmp_path / "layout")], capture_output=True, text=True, check=True).stdout
+    got = {}
+    for l in out.splitlines():
+        key, *nums = l.split()
+        got[key] = int(nums[0]) if len(nums) == 1 else (int(nums[0]), int(nums[1]))
+    assert got == want and got["seer_transpose_item"] == 56
+
+
+GOOD = """#define SEER_FLAG 4u
+typedef struct seer_d { const void* p; int32_t a, b; double c; } seer_d;
+const char* seer_name(int code);
+int32_t seer_f(const seer_d* d /* host */, const float* x, int32_t out[5] /* host */, int64_t n[2], uint64_t s, void* stream);
+"""
+
+
+def test_parser_types_of_a_well_formed_header():
+    from seervideoldm_amd._lib import parse_header
+    constants, structs, sigs = parse_header(GOOD)
+    D = structs["seer_d"]
+    assert constants == {"SEER_FLAG": 4} and list(structs) == ["seer_d"] and list(sigs) == ["seer_name", "seer_f"]
+    assert D._fields_ == [("p", ctypes.c_void_p), ("a", ctypes.c_int32), ("b", ctypes.c_int32), ("c", ctypes.c_double)]
+    assert sigs["seer_name"] == ([ctypes.c_int], ctypes.c_char_p)
+    assert sigs["seer_f"] == ([ctypes.POINTER(D), ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_uint64,
+                               ctypes.c_void_p], ctypes.c_int32)
+    assert parse_header(GOOD, {"seer_d": "Desc"})[1]["seer_d"].__name__ == "Desc"
+
+
+@pytest.mark.parametrize("bad, line, says", [
+    ("int seer_f(int32_t n, long m);", 3, "long m"),                                    # an unknown scalar type
+    ("typedef struct seer_e { int32_t a; size_t n; } seer_e;", 3, "size_t n"),          # a struct field of unknown type
+    ("static int seer_f(int32_t n);", 3, "static int seer_f"),                          # `seer_...(` that is no declaration
+    ("int seer_f(int32_t n) { return seer_g(n); }", 3, "seer_g"),
+    ("seer_d seer_f(int32_t n);", 3, "seer_d"),                                         # a struct by value is no scalar
+    ("#define SEER_SCALE 1.5f", 3, "SEER_SCALE"),
+], ids=["scalar", "field", "not-a-declaration", "body", "struct-by-value", "define"])
+def test_parser_refuses_what_it_does_not_understand(bad, line, says):
+    """a four-line header whose third line is not understood: SeerHipError with the line and its text, nothing skipped"""
+    from seervideoldm_amd._lib import SeerHipError, parse_header
+    lines = GOOD.splitlines()
+    text = "\n".join(lines[:2] + [bad] + lines[2:3]) + "\n"
+    parse_header("\n".join(lines[:2] + lines[2:3]) + "\n")                              # the same header without that line parses
+    with pytest.raises(SeerHipError) as e:
+        parse_header(text)
+    assert f"line {line}:" in str(e.value) and says in str(e.value), str(e.value)
+
+
+def test_transpose_items_pack_to_the_c_struct():
+    """train_ops.pack_transpose_items == struct.pack of seer_transpose_item's fields (5 x int64, 4 x int32); the second item has
+    cols and ldx close to 2^31: two int32 fields, not the two halves of one int64"""
+    import struct
+    from seervideoldm_amd import _lib
+    from seervideoldm_amd.train_ops import pack_transpose_items
+    a = dict(x=0x7F0000001000, y=0x7F0000200000, rows=3, ldy=64, tile0=0, cols=320, ldx=328, tiles_r=1)
+    b = dict(x=0x7F0123456780, y=0x7FFFFFFFFFF0, rows=65528, ldy=65536, tile0=5, cols=65528, ldx=2 ** 31 - 8, tiles_r=1024)
+    want = (struct.pack("<5q4i", 0x7F0000001000, 0x7F0000200000, 3, 64, 0, 320, 328, 1, 0)
+            + struct.pack("<5q4i", 0x7F0123456780, 0x7FFFFFFFFFF0, 65528, 65536, 5, 65528, 2 ** 31 - 8, 1024, 0))
+    assert ctypes.sizeof(_lib.TransposeItem) == 56 and len(want) == 112
+    assert pack_transpose_items([a, b]) == want and pack_transpose_items([b]) == want[56:]
 
 
 def test_argument_validation_without_gpu(lib_path):
