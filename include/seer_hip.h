@@ -424,6 +424,23 @@ int seer_groupnorm_stats_fx(const void* x, int32_t C, int32_t batch, int64_t row
  * an activation pointer off 16 bytes, params or twiddles NULL or off 4 bytes; more than 65535 channel slices. */
 int seer_freeu(const void* x, void* x_out, int32_t Cx, const void* skip, void* skip_out, int32_t Cs, int64_t rows, int32_t images,
                int32_t H, int32_t W, const float* params, const float* twiddles, int32_t dtype, void* stream);
+/* Step caching (DeepCache, Ma et al., CVPR 2024; TaylorSeer, Liu et al., 2025; csrc/step_cache.hip): the feature that enters the
+ * shallowest decoder layers of the UNet, kept over the last three full evaluations and forecast on the evaluations between them.
+ *   ring      three slots of n elements of the 16-bit storage type `dtype`, slot_stride elements apart; slot 0 is the newest.
+ * seer_cache_push:      slot2 <- slot1, slot1 <- slot0, slot0 <- x (n elements).  A thread reads its elements of all three sources
+ *                       before it writes; values move as bits (NaN payloads included: a slot that was never written may hold anything),
+ *                       so one kernel serves both storage types.  x is not written.
+ * seer_cache_forecast:  out[i] = rnd(fmaf(w2, f2[i], fmaf(w1, f1[i], w0 * f0[i]))), f_k = slot k; fp32 arithmetic in exactly this order,
+ *                       ONE round-to-nearest-even conversion to the storage type.
+ *   w         fp32 [3], DEVICE memory, read by the kernel: the launch is a node of a captured graph whose arguments are frozen.
+ *             A slot whose weight is exactly 0 is NOT READ and its term is left out (for slot 0 the sum starts from +0): it may hold
+ *             NaN.  So w = (1, 0, 0) returns the finite values of slot 0 bit for bit.
+ * Flat and memory bound: 16-byte accesses (8 elements per thread), the n % 8 elements of the tail by one thread, no LDS, no atomics.
+ * SEER_EINVAL, nothing launched: a NULL pointer; n < 1; slot_stride < n; slot_stride no multiple of 8 (a slot would leave 16-byte
+ * alignment); x, ring or out off 16 bytes, w off 4 bytes; x or out overlapping the ring's 2 * slot_stride + n elements; a dtype other
+ * than SEER_DT_BF16 / SEER_DT_F16. */
+int seer_cache_push(const void* x, void* ring, int64_t n, int64_t slot_stride, int32_t dtype, void* stream);
+int seer_cache_forecast(const void* ring, int64_t n, int64_t slot_stride, const float* w, void* out, int32_t dtype, void* stream);
 /* The feed-forward of a transformer block at the 320-channel level and the transformer's proj_out, ONE launch (csrc/ff_fused.hip):
  *     y = x + [Wp | Wp W2] [h | g] + bcat,   g = GEGLU(LayerNorm(h; gamma, beta, eps) W1^T + b1)
  * i.e. norm3 -> ff.net.0 -> ff.net.2 + residual -> proj_out + residual (seer/models/attention.py:231-248, 308-327, 742-747,

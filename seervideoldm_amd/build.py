@@ -21,7 +21,7 @@ LIB = LIBDIR / "libseer_hip.so"
 # the tile kernel of seer_gemm_bf16 compiles as units that share csrc/gemm_tiles.h (gemm_tiles_all.hip, every row in one unit, is
 # for the measurement builds of scripts/ and is not part of the library)
 GEMM_TILE_UNITS = [f"gemm_tiles_{u}.hip" for u in range(6)]
-SOURCES = ["gemm.hip", *GEMM_TILE_UNITS, "gemm_reduce.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "freeu.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "train.hip"]
+SOURCES = ["gemm.hip", *GEMM_TILE_UNITS, "gemm_reduce.hip", "gemm_ws.hip", "gemm_t320.hip", "ff_fused.hip", "rowchain.hip", "attention.hip", "attention40.hip", "attention_bwd.hip", "clip_text.hip", "gemm_tn.hip", "norm.hip", "freeu.hip", "step_cache.hip", "elementwise.hip", "sampler_step.hip", "rng.hip", "train.hip"]
 ARCH = "gfx950"
 # per-source extra flags.  attention: keep the MFMA accumulators in VGPRs (gfx950's unified file allows it) -- the online
 # softmax touches S and O every key tile, and the default AGPR form costs ~220 v_accvgpr moves per tile per wave.

@@ -29,6 +29,9 @@ unset or 0, nothing is rescaled.
 `SEER_COMPAT_FREEU="0.9,0.2,1.2,1.4"` (read by `install()`, or `install(freeu=(0.9, 0.2, 1.2, 1.4))`: s1, s2, b1, b2 in diffusers'
 order) makes the aliased `SeerUNet` one that comes with FreeU enabled at those values (`SeerUNet.enable_freeu`; Si et al. 2024);
 unset or empty, the class is the product's own.  Inference scripts only: `SeerTrainer` refuses such a model.
+`SEER_COMPAT_STEP_CACHE="3,1,1"` (read by `install()`, or `install(step_cache=(3, 1, 1))`: interval, branch, order) makes the aliased
+`SeerUNet` one that comes with step caching enabled (`SeerUNet.enable_step_cache`; DeepCache, Ma et al. 2024): the scripts' sampler
+then runs every interval-th model evaluation in full and the others from the cached feature.  Unset or empty, nothing is cached.
 `SEER_COMPAT_CLIP=native` (read by `install()`, or `install(clip="native")`) makes `transformers.CLIPTextModel` the product's
 `CLIPTextEncoder` (train.py:21,199; inference_img.py:85): `CLIPTextModel.from_pretrained(<local directory>, subfolder="text_encoder")`
 then loads the text tower onto the HIP kernels.  Unset, the scripts keep transformers' module.
@@ -76,6 +79,8 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
                 mod.DDIMSampler = _rescale_sampler(mod.DDIMSampler, _rescale)
             if spec.name == "seer.models.unet_3d_condition" and _freeu is not None:
                 mod.SeerUNet = _freeu_unet(mod.SeerUNet, _freeu)
+            if spec.name == "seer.models.unet_3d_condition" and _step_cache is not None:
+                mod.SeerUNet = _step_cache_unet(mod.SeerUNet, _step_cache)
             return mod
         # a parent package: a namespace over every directory of that name on sys.path (the reference checkout's own
         # `utils/`, `ldm/`, `seer/` when the script runs from there), so the reference's other modules keep resolving
@@ -148,11 +153,38 @@ def _freeu_unet(cls, vals):
     return _freeu_unets[cls, vals]
 
 
+_step_cache = None          # (interval, branch, order) while the aliased SeerUNet comes with step caching enabled
+_step_cache_unets = {}      # (SeerUNet class, values) -> its subclass whose instances have step caching enabled at those values
+
+
+def _parse_step_cache(text):
+    """"interval,branch,order" -> three integers; a ValueError that names the variable otherwise (the ranges are enable_step_cache's)"""
+    try:
+        vals = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        vals = ()
+    if len(vals) != 3 or vals[0] < 2 or vals[1] < 0 or vals[2] not in (0, 1, 2):
+        raise ValueError(f"SEER_COMPAT_STEP_CACHE={text!r}: three integers interval,branch,order with interval >= 2, branch >= 0 and "
+                         "order 0, 1 or 2, such as 3,1,1")
+    return vals
+
+
+def _step_cache_unet(cls, vals):
+    """`cls` whose constructor ends with enable_step_cache(*vals), as _freeu_unet does for FreeU"""
+    if (cls, vals) not in _step_cache_unets:
+        def __init__(self, *args, **kwargs):
+            cls.__init__(self, *args, **kwargs)
+            self.enable_step_cache(*vals)
+        _step_cache_unets[cls, vals] = type(cls.__name__, (cls,), {"__init__": __init__, "__doc__": cls.__doc__,
+                                                                   "__module__": cls.__module__})
+    return _step_cache_unets[cls, vals]
+
+
 _clip_saved = None          # (transformers module, its own CLIPTextModel) while the native text encoder stands in
 
 
 def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str] = None,
-            prediction: Optional[str] = None, guidance_rescale: Optional[float] = None, freeu=None) -> None:
+            prediction: Optional[str] = None, guidance_rescale: Optional[float] = None, freeu=None, step_cache=None) -> None:
     """`sampler` (default: the environment's SEER_COMPAT_SAMPLER) = "plms" makes the aliased
     `ldm.models.diffusion.ddim_video.DDIMSampler` the product's PLMSSampler, "dpmpp" its DPMSolverSampler; anything else keeps
     DDIMSampler.
@@ -162,9 +194,12 @@ def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str
     constructor defaults to guidance_rescale of that value; 0 keeps it as it is; anything outside [0, 1] is a ValueError.
     `freeu` (default: the environment's SEER_COMPAT_FREEU, "s1,s2,b1,b2") = four finite numbers makes the aliased SeerUNet a class whose
     instances have FreeU enabled at those values; nothing keeps the class as it is; malformed text is a ValueError naming the variable.
+    `step_cache` (default: the environment's SEER_COMPAT_STEP_CACHE, "interval,branch,order") = three integers makes the aliased SeerUNet
+    a class whose instances have step caching enabled at those values; nothing keeps the class as it is; malformed text is a ValueError
+    naming the variable.
     `clip` (default: the environment's SEER_COMPAT_CLIP) = "native" makes `transformers.CLIPTextModel` the product's
     CLIPTextEncoder until uninstall(); anything else leaves transformers alone"""
-    global _sampler, _prediction, _rescale, _clip_saved, _freeu
+    global _sampler, _prediction, _rescale, _clip_saved, _freeu, _step_cache
     _sampler = (os.environ.get("SEER_COMPAT_SAMPLER", "") if sampler is None else sampler).strip().lower()
     _prediction = (os.environ.get("SEER_COMPAT_PREDICTION", "") if prediction is None else prediction).strip().lower()
     if _prediction not in ("", "epsilon", "v_prediction"):
@@ -177,6 +212,11 @@ def install(vae: bool = False, sampler: Optional[str] = None, clip: Optional[str
         _freeu = _parse_freeu(text) if text else None
     else:
         _freeu = _parse_freeu(",".join(repr(float(v)) for v in freeu))
+    if step_cache is None:
+        text = os.environ.get("SEER_COMPAT_STEP_CACHE", "").strip()
+        _step_cache = _parse_step_cache(text) if text else None
+    else:
+        _step_cache = _parse_step_cache(",".join(str(v) for v in step_cache))
     if (os.environ.get("SEER_COMPAT_CLIP", "") if clip is None else clip).strip().lower() == "native" and _clip_saved is None:
         import transformers
         from seervideoldm_amd import CLIPTextEncoder

@@ -44,6 +44,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .step_cache import policy_of
 from .step_graph import capture_engine, capture_step, changed, refresh      # capture_step: slots.py and callers import it from here
 
 
@@ -149,7 +150,9 @@ class DDIMSampler(object):
     def _chain_start(self, unet, shape, x_T, x0_emb):
         """the latent a chain starts from -- x_T, or torch.randn(shape) -- in fp32 on the sampler's device, and x0_emb on that device.
         One clip sharded over several ranks (parallel.attach): every rank must denoise the SAME latent, so the start code and the
-        conditioning latents (a per-rank posterior sample) come from rank 0, like any per-step noise."""
+        conditioning latents (a per-rank posterior sample) come from rank 0, like any per-step noise.  A model with its step cache
+        enabled begins a chain of evaluations here: the first one runs in full, and nothing an earlier chain kept is read."""
+        _begin_cache_chain(unet)
         img = torch.randn(shape, device=self.device) if x_T is None else x_T.to(device=self.device, dtype=torch.float32)
         img = _from_rank0(unet, img)
         if x0_emb is not None:
@@ -334,7 +337,7 @@ class DDIMSampler(object):
                                            limit, phi=phi)
             if done is not None:
                 return done
-        eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale)
+        eps, cfg, cond_f = self._model_output(unet, x, c, t, x0_emb, cond_frames, uc, scale, cached=False)
         return self.ops.cfg_ddim_invert_step(self._rescaled(eps, scale, cond_f, phi), x, self.ddim_coef, int(index), cfg=cfg,
                                              scale=scale, cond_f=cond_f)
 
@@ -417,21 +420,26 @@ class DDIMSampler(object):
         return self.ops.cfg_ddim_step(eps, x, self.ddim_coef, index, cfg=cfg, scale=scale, cond_f=cond_f,
                                       noise=noise if sigma != 0. else None)
 
-    def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale):
+    def _model_output(self, unet, x, c, t, x0_emb, cond_frames, uc, scale, cached=True):
         """the model call of p_sample_ddim (ddim_video.py:187-207): x0_emb in front of x along frames, batched CFG when uc has c's
         frame count, two calls otherwise.  Returns (eps [2b or b, C, cond_f + F, h, w], cfg, cond_f): the CFG combine and the
-        slicing off of the conditioning frames are the update kernel's.  For a v-model "eps" is v: the caller passes it through _as_eps."""
+        slicing off of the conditioning frames are the update kernel's.  For a v-model "eps" is v: the caller passes it through _as_eps.
+        A SeerUNet with its step cache enabled is handed the phase of this evaluation (`cache_phase`, one next() of its policy) where
+        the step makes ONE model call; the two calls of unbatched CFG, and inversion (cached=False), run in full and leave the cache
+        alone.  Any other model is called as it always was."""
         cond_f = 0
         x_cat = x
         if x0_emb is not None:
             cond_f = x0_emb.shape[2]
             x_cat = torch.cat([x0_emb.to(x.dtype), x], dim=2)
         t = t.to(torch.long)
+        pol = policy_of(unet) if cached and (uc is None or scale == 1. or uc.shape[2] == c.shape[2]) else None
+        phase = {} if pol is None else {"cache_phase": pol.next()[0]}
         if uc is None or scale == 1.:
-            eps = unet(x_cat, t, c)
+            eps = unet(x_cat, t, c, **phase)
             cfg = False
         elif uc.shape[2] == c.shape[2]:
-            eps = unet(torch.cat([x_cat] * 2), torch.cat([t] * 2), self._cfg_context(c, uc), cond_frame=cond_frames)
+            eps = unet(torch.cat([x_cat] * 2), torch.cat([t] * 2), self._cfg_context(c, uc), cond_frame=cond_frames, **phase)
             cfg = True
         else:
             e_uc = unet(x_cat, t, uc, cond_frame=cond_frames)
@@ -478,7 +486,7 @@ class DDIMSampler(object):
         "invert"; G["expect"] follows it, so that a chain's later steps find the index they need already in device memory."""
         if draw and self.consume_rng_when_deterministic:
             torch.randn(x.shape, device=x.device)   # ddim_video.py:234 draws every step, also at sigma = 0: keep the RNG stream
-        G["graph"].replay()
+        (G["graph_cached"] if G.get("phase") else G["graph"]).replay()      # (_step_graph left this evaluation's phase there)
         G["expect"] = index + direction
         if self.static_step_outputs:
             return G["x"], G["pred"]
@@ -503,6 +511,7 @@ class DDIMSampler(object):
         if eng is None:
             return None
         cfg = uc is not None
+        pol = None if kind == "invert" else policy_of(unet)      # step caching: inversion runs every step in full
         context = self._cfg_context(c, uc) if cfg else c
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
@@ -516,11 +525,12 @@ class DDIMSampler(object):
         key = (kind, (b, Cc, Fp, h, w), f1, cfg, int(cond_frames), float(scale) if cfg else None, L, tuple(ctx.shape), eng.inv,
                *(() if temperature is None else (float(temperature),)),
                *(() if self.prediction_type == "epsilon" else (self.prediction_type,)),
-               *(("rescale", float(phi)) if cfg and phi > 0. else ()), *getattr(eng, "freeu_key", ()))
+               *(("rescale", float(phi)) if cfg and phi > 0. else ()), *getattr(eng, "freeu_key", ()),
+               *(() if pol is None else eng.step_cache_key))
         G = eng.graph_get(key)
         if G is None:
             G = self._capture_step(eng, key, x, x0_emb, reps, cfg, int(cond_frames), float(scale), temperature, ctx, L,
-                                   phi=float(phi) if cfg else 0.)
+                                   phi=float(phi) if cfg else 0., cached=pol is not None)
             if G is None:
                 return None
         n = self.ddim_coef.shape[0]
@@ -533,11 +543,20 @@ class DDIMSampler(object):
             G["expect"] = None
         if x is not G["x"] and x.data_ptr() != G["x"].data_ptr():
             G["x"].copy_(x)
+        # step caching, last of all (from here on the caller replays): the phase of this evaluation picks the graph, and the host's
+        # half of it -- the count of valid slots, a cached phase's weights into the device buffer -- is done as for a launched one
+        G["phase"] = None
+        if pol is not None:
+            G["phase"], weights = pol.next()
+            eng.cache_note(reps * b * (f1 + Fp) * h * w, G["phase"], weights)
         return G
 
-    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, temperature, ctx, L, phi=0.):
+    def _capture_step(self, eng, key, x, x0_emb, reps, cfg, cond_frames, scale, temperature, ctx, L, phi=0., cached=False):
         """the step of kind key[0] over fresh static buffers, captured and put under `key`; None when the capture is refused.  phi > 0:
-        the rescale node sits behind the model and in front of the v-conversion, its workspace one more static buffer"""
+        the rescale node sits behind the model and in front of the v-conversion, its workspace one more static buffer.  cached (step
+        caching): TWO graphs over the one set of buffers, the step around a full evaluation that keeps its cut feature and the step
+        around a cached one -- counter, solver state and latents are shared, the update kernels are the same.  Warm-up and capture
+        may come in the middle of a chain (PLMS captures at its second step): the ring is put back afterwards."""
         dev = x.device
         b, Cc, Fp, h, w = x.shape
         f1 = 0 if x0_emb is None else x0_emb.shape[2]
@@ -557,17 +576,22 @@ class DDIMSampler(object):
         if x0_emb is not None:
             G["x0"].copy_(x0_emb)
 
-        def body():
+        def body(phase=0 if cached else None):
             for launch in front:
                 launch(G)
             ops.ddim_step_begin(G["x0"], G["x"], G["ttab"], G["step"], reps, G["sample"], G["t"])
-            eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames)
+            eps = eng._forward(G["sample"], G["t"], ctx, L, cond_frames, cache_phase=phase)
             if phi > 0.:                                # in place, on the engine's output buffer, both rows of every clip
                 ops.cfg_rescale(eps, scale=scale, rescale=phi, cond_f=f1, ws=G["rescale_ws"])
             if self.prediction_type != "epsilon":       # in place as well: nothing is allocated for it
                 ops.v_to_eps_dev(eps, G["x"], G["coef"], G["step"], cond_f=f1, out=eps)
             update(G, eps, temperature, cfg=cfg, scale=scale, cond_f=f1)
-        if capture_step(eng, key, G, body) is None:
+        ring = eng.cache_set(G["sample"].numel() // Cc)["ring"] if cached else None
+        ring_was = None if ring is None else ring.clone()
+        done = capture_step(eng, key, G, body, **({"cached_body": lambda: body(1)} if cached else {}))
+        if ring is not None:
+            ring.copy_(ring_was)
+        if done is None:
             self._capture_refused = True
             return None
         return G
@@ -615,6 +639,15 @@ STEP_KINDS = {"step": (lambda x: {}, (), _ddim_update),
               "step-rng": (_seed_buffers, (), _rng_update),
               "step-mask": (_mask_buffers, (_blend,), _rng_update),
               "invert": (_limit_buffers, (), _invert_update)}
+
+
+def _begin_cache_chain(unet) -> None:
+    """a chain of model evaluations begins: the step cache's policy, and the engine's count of valid slots, start over"""
+    pol = policy_of(unet)
+    if pol is not None:
+        pol.begin()
+        if unet._engine is not None:
+            unet._engine.cache_begin()
 
 
 def _refuse_sharded(unet, what: str) -> None:

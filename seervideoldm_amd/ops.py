@@ -674,6 +674,33 @@ def freeu(x: Optional[torch.Tensor], skip: Optional[torch.Tensor], params: torch
     return xo, so
 
 
+def _cache_ring(ring: torch.Tensor, other: torch.Tensor, name: str) -> int:
+    """the checks cache_push / cache_forecast share: ring [3, slot_stride] of `other`'s 16-bit type, rows contiguous"""
+    dt = _req16(other, name)
+    _req16(ring, "ring", other)
+    assert ring.dim() == 2 and ring.shape[0] == 3 and ring.stride(1) == 1 and ring.stride(0) >= other.numel(), tuple(ring.shape)
+    assert other.is_contiguous(), name
+    return dt
+
+
+def cache_push(x: torch.Tensor, ring: torch.Tensor) -> None:
+    """step caching, one launch (seer_cache_push): slot 2 <- slot 1 <- slot 0 <- x over the first x.numel() elements of every slot of
+    ring [3, slot_stride] (slot 0 the newest).  Bits move; x is not written."""
+    dt = _cache_ring(ring, x, "x")
+    check(_lib.load().seer_cache_push(_p(x), _p(ring), x.numel(), ring.stride(0), dt, _stream()), "seer_cache_push")
+
+
+def cache_forecast(ring: torch.Tensor, w: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """step caching, one launch (seer_cache_forecast): out = rnd(fma(w2, slot 2, fma(w1, slot 1, w0 * slot 0))) over out.numel()
+    elements; w = fp32 [3] on the device (the kernel reads it: a captured launch follows the values).  A slot whose weight is exactly
+    0 is not read.  Returns out."""
+    dt = _cache_ring(ring, out, "out")
+    _req(w, torch.float32, "w")
+    assert w.numel() == 3 and w.is_contiguous()
+    check(_lib.load().seer_cache_forecast(_p(ring), out.numel(), ring.stride(0), _p(w), _p(out), dt, _stream()), "seer_cache_forecast")
+    return out
+
+
 def groupnorm_stats_from_fx(fx1: ColSumsFx, fx2: Optional[ColSumsFx], batch: int, groups: int, stats: torch.Tensor) -> torch.Tensor:
     """stats[b][g] = (sum, sumsq) from accumulated column sums (torch ops; the fall-back of a layout groupnorm_apply_fx refuses)."""
     v = fx1.totals() if fx2 is None else torch.cat([fx1.totals(), fx2.totals()], dim=1)

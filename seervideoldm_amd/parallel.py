@@ -291,6 +291,8 @@ def probe_capture(device, group=None) -> bool:
 def attach(model, world: int, rank: int, batch_groups: Optional[int] = None, capture_collectives: Optional[bool] = None) -> FrameShard:
     """make `model.forward` run sharded: every rank passes the FULL (sample, timestep, context) and gets the FULL output.
     capture_collectives=False keeps the eager exchanges between hipGraph segments (the conservative replay)."""
+    if getattr(model, "_step_cache", None) is not None:
+        raise ValueError("parallel.attach: the model's step cache is enabled (a sharded model keeps none); call disable_step_cache() first")
     shard = FrameShard(world, rank, batch_groups, capture_collectives)
     if world > 1 and dist.is_available() and dist.is_initialized():
         shard.control_group()                # every rank, here: new_group is itself collective

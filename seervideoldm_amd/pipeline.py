@@ -84,6 +84,8 @@ def generate_queue(sunet, fstext_model, vae, requests: Iterable[dict], *, slots:
     only when a slot is free -- and the VAE decode, 1/0.18215 and clamp01 when its clip finishes, as ddim_sample does them.  Yields
     (tag, clip [1, 3, num_frames - cond_frames, H, W] in [0, 1]) in finishing order.  Every request has the shape of the first."""
     from .slots import SlotSampler
+    from .step_cache import refuse
+    refuse(sunet, "generate_queue")
     f1, f2 = cond_frames, num_frames - cond_frames
     fstext_model.set_numframe(num_frames)
     sampler: List[SlotSampler] = []

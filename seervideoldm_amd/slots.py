@@ -68,6 +68,7 @@ from typing import Dict, Iterable, Iterator, List, Optional, Tuple
 import torch
 
 from . import ops as hip_ops
+from . import step_cache
 from .ddim import DDIMSampler, capture_step
 from .dpm import DPMSolverSampler
 from .step_graph import capture_engine, engine_on
@@ -98,6 +99,7 @@ class SlotSampler:
                  model_cond_frame: int = 0, plms: bool = False, stochastic: bool = False, editing: bool = False,
                  dpm: bool = False, prediction_type: str = "epsilon", rescale: bool = False):
         self.prediction_type = hip_ops.check_prediction_type(prediction_type)
+        step_cache.refuse(unet, "SlotSampler")
         C, Fp, h, w = (int(v) for v in shape)
         L, D = (int(v) for v in context_shape)
         f1 = int(cond_frames)
@@ -398,6 +400,7 @@ class SlotSampler:
     def _run_step(self) -> None:
         from .unet import SeerUNet
         unet = self.unet
+        step_cache.refuse(unet, "SlotSampler")       # (enabled since the sampler was built)
         if not isinstance(unet, SeerUNet):
             self._body(lambda: unet(self._sample, self._t, self._context, cond_frame=self.model_cond_frame).float().contiguous())
             return

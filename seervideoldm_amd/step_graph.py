@@ -47,20 +47,27 @@ def refresh(kept: dict, name: str, sources, dests) -> bool:
     return True
 
 
-def capture_step(eng, key, G, body):
+def capture_step(eng, key, G, body, cached_body=None):
     """`body` (the launches of one sampler step over the static buffers in G) as ONE hipGraph: a warm-up run, the capture, and the
     entry G -- with the graph under "graph" -- in the engine's graph cache under `key`.  Returns G, or None with a warning when the
-    capture is refused: the caller keeps the launch-by-launch path."""
+    capture is refused: the caller keeps the launch-by-launch path.  `cached_body` (step caching): the same step around a cached
+    model evaluation, over the SAME static buffers, as a second graph under "graph_cached" in the same entry and the first one's
+    memory pool (the two never run at once and hand nothing to each other but G); both are captured or neither is."""
     try:
-        body()                                       # warm-up: K|V / rotary caches, allocations
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            body()
+        graphs = []
+        for b in (body,) if cached_body is None else (body, cached_body):
+            b()                                      # warm-up: K|V / rotary caches, allocations
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local", **({"pool": graphs[0].pool()} if graphs else {})):
+                b()
+            graphs.append(g)
     except Exception as e:      # noqa: BLE001  capture refused: keep the launch-by-launch path
         import warnings
         warnings.warn(f"hipGraph capture of the sampler step failed ({type(e).__name__}: {e}); stepping launch by launch")
         return None
-    G["graph"] = g
+    G["graph"] = graphs[0]
+    if cached_body is not None:
+        G["graph_cached"] = graphs[1]
     eng.graph_put(key, G)
     return G

@@ -24,6 +24,7 @@ from . import _lib
 from . import ops as hip_ops
 from . import synth
 from .groupnorm import groupnorm, groupnorm_statistics
+from .step_cache import RING_SLOTS, StepCachePolicy
 from .weights import geglu_row_order, pack_conv1x1, pack_conv3x3, pack_conv3x3_up_phases
 
 bf16 = torch.bfloat16
@@ -101,6 +102,7 @@ class SeerUNet(nn.Module):
         # True / False here or as an attribute before the first forward; None = the environment's SEER_LAYOUT_INVARIANT=1 (_Engine)
         self.layout_invariant = layout_invariant
         self._freeu: Optional[Tuple[float, float, float, float]] = None     # (s1, s2, b1, b2) while FreeU is on (enable_freeu)
+        self._step_cache: Optional[StepCachePolicy] = None                  # the policy while step caching is on (enable_step_cache)
 
     # ---- construction / weights -------------------------------------------------------------------------------
     @classmethod
@@ -154,6 +156,7 @@ class SeerUNet(nn.Module):
         with torch.autocast(device_type=dev if dev in ("cuda", "cpu") else "cuda", enabled=False):     # fp32 weight algebra stays fp32
             self._engine = _Engine(self, ops=self._ops_backend, shard=self._shard, dtype=dtype)
         self._engine.set_freeu(self._freeu)
+        self._engine.set_step_cache(None if self._step_cache is None else self._step_cache.branch)
         return self
 
     # ---- toggles of the reference surface ---------------------------------------------------------
@@ -196,21 +199,74 @@ class SeerUNet(nn.Module):
             self._engine.set_freeu(None)
         return self
 
+    def enable_step_cache(self, interval: int = 3, branch: int = 1, order: int = 1):
+        """Step caching (DeepCache, Ma et al., CVPR 2024; forecasting as in TaylorSeer, Liu et al., 2025): of a sampler's model
+        evaluations every `interval`-th runs in full and keeps the feature that enters the last `branch` + 1 layers of the last up
+        block; the others forecast that feature from the last full evaluations (order 0: reuse, 1: linear, 2: quadratic
+        extrapolation) and run conv_in, the first `branch` layers of down_blocks.0 and those last layers only (step_cache.py, DESIGN.md
+        "Step caching").  Inference only, off by default.  interval and order may change between samples without a recapture; branch
+        and on <-> off select other captured graphs."""
+        L = self.config.layers_per_block
+        for name, v in (("interval", interval), ("branch", branch), ("order", order)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError(f"enable_step_cache: {name} = {v!r} is not an integer")
+        if interval < 2:
+            raise ValueError(f"enable_step_cache: interval = {interval}: 2 or more (every interval-th evaluation runs in full)")
+        if not 0 <= branch <= L:
+            raise ValueError(f"enable_step_cache: branch = {branch}: 0 .. layers_per_block = {L}")
+        if order not in (0, 1, 2):
+            raise ValueError(f"enable_step_cache: order = {order}: 0 (reuse), 1 (linear) or 2 (quadratic) over the ring's {RING_SLOTS} slots")
+        if self._shard is not None:
+            raise ValueError("enable_step_cache: a sharded model (parallel.attach) keeps no step cache; detach it first")
+        self._step_cache = StepCachePolicy(interval, branch, order)
+        if self._engine is not None:
+            self._engine.set_step_cache(int(branch))
+        return self
+
+    def disable_step_cache(self):
+        self._step_cache = None
+        if self._engine is not None:
+            self._engine.set_step_cache(None)
+        return self
+
     # ---- forward ---------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep: Union[torch.Tensor, float, int], context: torch.Tensor,
-                cond_frame: int = 0, return_attn: bool = False) -> torch.Tensor:
+                cond_frame: int = 0, return_attn: bool = False, cache_phase: Optional[int] = None) -> torch.Tensor:
+        """cache_phase (step caching, enable_step_cache): None = the evaluation as it always was, the cache untouched; 0 = the same
+        evaluation, which also keeps its cut feature; d >= 1 = a cached evaluation, d evaluations after the last full one."""
         if not sample.is_cuda and self._ops_backend is hip_ops:
             raise hip_ops._lib.SeerHipError("SeerUNet.forward needs ROCm tensors: the HIP kernels are the only compute path")
         dt = self._dtype_of_call()
         # the caller's autocast state has said its piece (the storage type): everything below -- the host-side weight algebra of
         # prepare() included -- runs outside it (a torch matmul under autocast would hand back 16-bit biases)
         with torch.autocast(device_type=sample.device.type if sample.device.type in ("cuda", "cpu") else "cuda", enabled=False):
-            return self._forward_impl(sample, timestep, context, cond_frame, return_attn, dt)
+            return self._forward_impl(sample, timestep, context, cond_frame, return_attn, dt, cache_phase)
 
-    def _forward_impl(self, sample, timestep, context, cond_frame, return_attn, dt):
+    def _cache_args(self, cache_phase, return_attn):
+        """forward's cache_phase -> the engine's (phase, weights) keywords; the weights of a cached phase follow the policy and the
+        engine's count of valid slots"""
+        if self._step_cache is not None and self._shard is not None:
+            raise ValueError("a sharded model (parallel.attach) keeps no step cache: call disable_step_cache(), or detach the model")
+        if cache_phase is None:
+            return {}
+        if self._step_cache is None:
+            raise ValueError("cache_phase: step caching is off (enable_step_cache)")
+        if return_attn:
+            raise ValueError("cache_phase with return_attn: the attention maps of the skipped blocks do not exist")
+        d = int(cache_phase)
+        if d < 0:
+            raise ValueError(f"cache_phase = {cache_phase}: None, 0 (full, keep the feature) or d >= 1 (cached)")
+        if d == 0:
+            return {"cache_phase": 0}
+        if self._engine.cache_valid < 1:
+            raise ValueError(f"cache_phase = {d}: no full evaluation (cache_phase=0) has filled the cache since it was reset")
+        return {"cache_phase": d, "cache_weights": self._step_cache.weights(d, self._engine.cache_valid)}
+
+    def _forward_impl(self, sample, timestep, context, cond_frame, return_attn, dt, cache_phase=None):
         if self._engine is None or self._engine.device != sample.device or self._engine.dt != dt:
             self.prepare(dt)
+        cache = self._cache_args(cache_phase, return_attn)
         if self.config.center_input_sample:
             sample = 2 * sample - 1.0
         t = timestep
@@ -227,7 +283,7 @@ class SeerUNet(nn.Module):
             out, attn = self._engine.run(sample.float().contiguous(), t, context, int(cond_frame), return_attn=True)
             return out.to(sample.dtype), [a.to(sample.dtype) for a in attn]
         if self._shard is None:
-            out = self._engine.run(sample.float().contiguous(), t, context, int(cond_frame), use_graph=self.use_graph)
+            out = self._engine.run(sample.float().contiguous(), t, context, int(cond_frame), use_graph=self.use_graph, **cache)
             return out.to(sample.dtype)
         # sharded step: every rank holds the full inputs, computes its (batch rows, frames) block, all ranks get the full eps
         sh = self._shard
@@ -369,6 +425,65 @@ class _Engine:
         self._attn_wanted = ()
         self.freeu_on = False           # FreeU (SeerUNet.enable_freeu): set_freeu
         self._freeu_buf = None          # fp32 (b1, s1, b2, s2) on the device, read by the seer_freeu launches
+        self.cache_branch = None        # step caching (SeerUNet.enable_step_cache): the branch while it is on, set_step_cache
+        self._cache_sets: Dict[Tuple[int, int], Dict[str, torch.Tensor]] = {}   # (rows, branch) -> ring, forecast and weight buffers
+        self._cache_cur = None          # the set the last phase went to
+        self.cache_valid = 0            # slots of that set's ring that hold a feature of the running chain
+
+    # ---- step caching ---------------------------------------------------------------------------------------------------
+    def set_step_cache(self, branch) -> None:
+        """branch = 0 .. layers_per_block turns step caching on, None off.  Another branch is another cut: the count of valid slots
+        starts over.  The buffer sets stay: captured graphs read them by address."""
+        if branch != self.cache_branch:
+            self.cache_valid = 0
+        self.cache_branch = branch
+
+    @property
+    def step_cache_key(self) -> Tuple:
+        """what step caching adds to the key of a captured sampler step: nothing while it is off, ("cache", branch) while it is on --
+        interval and order are host policy and no part of it"""
+        return () if self.cache_branch is None else ("cache", self.cache_branch)
+
+    def cache_set(self, rows: int) -> Dict[str, torch.Tensor]:
+        """the static buffers of the cut feature [rows, C] at the current branch, made on first use -- before any capture, like
+        fx_arena: `ring` [3, n] (slot 0 the newest), `fc` [rows, C] the forecast, `w` fp32 [3] its weights on the device.  C is
+        boc[0], the width of level 0 -- except at branch = layers_per_block, where the cut feature is the last upsampler's output and
+        has the width of level 1"""
+        key = (int(rows), self.cache_branch)
+        S = self._cache_sets.get(key)
+        if S is None:
+            assert not (self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()), \
+                "the step cache's buffers must exist before a graph capture"
+            C = self.boc[1 if self.cache_branch == self.lpb else 0]
+            n = (rows * C + 7) // 8 * 8          # a slot keeps 16-byte alignment
+            S = dict(ring=torch.zeros((RING_SLOTS, n), device=self.device, dtype=self.dt),
+                     fc=torch.zeros((rows, C), device=self.device, dtype=self.dt),
+                     w=torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32).to(self.device))
+            self._cache_sets[key] = S
+        return S
+
+    def cache_begin(self) -> None:
+        """a sampler begins a chain: nothing an earlier chain left in a ring is read"""
+        self.cache_valid = 0
+
+    def cache_note(self, rows: int, phase: int, weights=None) -> None:
+        """the host's half of one evaluation with a phase, launched or replayed: the count of valid slots (reset when the feature's
+        shape or the branch is not the last evaluation's), the refusal of a cold cached phase, and the weights of a cached one written
+        into the set's device buffer -- the only host write of such a step"""
+        if self.cache_branch is None:
+            raise ValueError("cache_phase: step caching is off (SeerUNet.enable_step_cache)")
+        S = self.cache_set(rows)
+        if self._cache_cur is not S:
+            self._cache_cur, self.cache_valid = S, 0
+        if phase == 0:
+            self.cache_valid = min(self.cache_valid + 1, RING_SLOTS)
+            return
+        if self.cache_valid < 1:
+            raise ValueError(f"cache_phase = {phase}: no full evaluation (cache_phase=0) of this shape and branch has filled the cache "
+                             "since it was reset")
+        if weights is None or len(weights) != RING_SLOTS:
+            raise ValueError(f"cache_phase = {phase}: a cached evaluation needs its {RING_SLOTS} forecast weights")
+        S["w"].copy_(torch.tensor([float(v) for v in weights], dtype=torch.float32))
 
     # ---- FreeU ----------------------------------------------------------------------------------------------------------
     def set_freeu(self, vals) -> None:
@@ -820,10 +935,16 @@ class _Engine:
                    (k.endswith("norm1.weight") or k.endswith("norm2.weight") or k.endswith(".norm.weight") or
                     k == "conv_norm_out.weight") and "transformer_blocks" not in k)
 
-    def _forward(self, sample, t, ctx_bf16, ctx_len, cond_frame, return_attn=False):
+    def _forward(self, sample, t, ctx_bf16, ctx_len, cond_frame, return_attn=False, cache_phase=None):
+        """cache_phase (step caching; the launches only -- the host's half is cache_note): None = the schedule as it always was;
+        0 = the same, plus one cache_push of the cut feature, the backbone input of up_blocks.{n-1}.resnets.{lpb - branch}; d >= 1 =
+        the cached walk: time embedding, conv_in, the first `branch` layers of down_blocks.0, one cache_forecast, the layers lpb -
+        branch .. lpb of the last up block, conv_norm_out, conv_out."""
         ops, w = self.ops, self.w
         B, Cin, Fr, H, W = sample.shape
         boc, lpb, n = self.boc, self.lpb, len(self.boc)
+        cache = None if cache_phase is None else self.cache_set(B * Fr * H * W)
+        cut = None if cache is None else lpb - self.cache_branch          # the layer of the last up block the cut feature enters
         self._attn_list = [] if return_attn else None
         # the last text block of each container: the reference's containers overwrite attn_map layer by layer
         self._attn_wanted = {f"down_blocks.{i}.attentions.{lpb - 1}" for i in range(n - 1)} | {"mid_block.attentions.0"} | \
@@ -859,6 +980,22 @@ class _Engine:
             ops.conv_in(sample, w["conv_in.weight"], w["conv_in.bias"], dtype=self.dt)
         skips = [x]
         geo = (B, Fr, H, W)
+        if cache_phase:
+            # a cached evaluation: the skips s_0 .. s_branch of level 0, then the last up block from the forecast cut feature on.  The
+            # forecast is a fresh view of the static buffer, without column sums: norm1 takes its statistics pass, as behind ops.freeu
+            for j in range(self.cache_branch):
+                x = self._resnet(f"down_blocks.0.resnets.{j}", x, None, geo, feeds_transformer=True)
+                x = self._text_transformer(f"down_blocks.0.attentions.{j}", x, geo)
+                x = self._temporal_transformer(f"down_blocks.0.temporal_attentions.{j}", x, geo, cond_frame)
+                skips.append(x)
+            x = ops.cache_forecast(cache["ring"], cache["w"], cache["fc"])[:]
+            p = f"up_blocks.{n - 1}"
+            for j in range(cut, lpb + 1):
+                x = self._resnet(f"{p}.resnets.{j}", x, skips.pop(), geo, feeds_transformer=True)
+                x = self._text_transformer(f"{p}.attentions.{j}", x, geo)
+                x = self._temporal_transformer(f"{p}.temporal_attentions.{j}", x, geo, cond_frame)
+            x = self._gn(x, None, B, Fr * H * W, "conv_norm_out", self.eps, True)
+            return ops.conv_out(x, w["conv_out.weight"], w["conv_out.bias"], B, Fr, H, W)
         for i in range(n):
             p = f"down_blocks.{i}"
             for j in range(lpb):
@@ -880,6 +1017,8 @@ class _Engine:
         for i in range(n):
             p = f"up_blocks.{i}"
             for j in range(lpb + 1):
+                if cache is not None and i == n - 1 and j == cut:
+                    ops.cache_push(x, cache["ring"])                # phase 0: the cut feature joins the ring; x itself is only read
                 x = self._resnet(f"{p}.resnets.{j}", x, skips.pop(), geo, feeds_transformer=i > 0)
                 if i > 0:
                     x = self._text_transformer(f"{p}.attentions.{j}", x, geo)
@@ -920,7 +1059,10 @@ class _Engine:
             self._kv_ctx_ref = context
         return self._ctx_bf16, context.shape[-2]
 
-    def run(self, sample, t, context, cond_frame, use_graph=False, return_attn=False):
+    def run(self, sample, t, context, cond_frame, use_graph=False, return_attn=False, cache_phase=None, cache_weights=None):
+        """cache_phase / cache_weights: step caching (_forward, cache_note); None leaves the cache alone"""
+        if cache_phase is not None and return_attn:
+            raise ValueError("cache_phase with return_attn: the attention maps of the skipped blocks do not exist")
         if context.dim() == 3:      # [B, L, Dc] -> same text for every frame
             context = context[:, None].expand(-1, sample.shape[2], -1, -1)
         assert context.shape[0] == sample.shape[0] and context.shape[1] == sample.shape[2], \
@@ -931,9 +1073,14 @@ class _Engine:
         ctx, L = self._context(context)
         if return_attn:
             return self._forward(sample, t, ctx, L, cond_frame, return_attn=True)
+        if cache_phase is not None:
+            if self.shard is not None:
+                raise ValueError("cache_phase: a sharded engine keeps no step cache")
+            B, _, Fr = sample.shape[:3]
+            self.cache_note(B * Fr * H * W, cache_phase, cache_weights)
         if not use_graph or getattr(self, "_graph_broken", False):
-            return self._forward(sample, t, ctx, L, cond_frame)
-        return self._run_graph(sample, t, ctx, L, cond_frame)
+            return self._forward(sample, t, ctx, L, cond_frame, cache_phase=cache_phase)
+        return self._run_graph(sample, t, ctx, L, cond_frame, cache_phase)
 
     def sync_point(self, fn):
         """run `fn` -- a cross-rank exchange (all-reduce / all-gather on static buffers) -- at this point of the schedule.
@@ -949,16 +1096,21 @@ class _Engine:
         rec.steps.append(fn)
         rec.begin_segment()
 
-    def _run_graph(self, sample, t, ctx, L, cond_frame):
+    def _run_graph(self, sample, t, ctx, L, cond_frame, cache_phase=None):
         """hipGraph replay of the shape-static step: ~1.3k launches -> one graph launch, or -- frame-sharded -- one graph
         launch per stretch between two collectives (GroupNorm statistics / K|V exchanges stay eager torch.distributed
-        calls on the same stream)."""
-        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape), self.inv, *self.freeu_key)
+        calls on the same stream).  With a cache_phase the graph is the storing walk or the cached one of the current branch: the
+        key takes that class and the branch, never the phase's number."""
+        key = (tuple(sample.shape), L, cond_frame, tuple(ctx.shape), self.inv, *self.freeu_key,
+               *(() if cache_phase is None else ("cached" if cache_phase else "store", self.cache_branch)))
         g = self.graph_get(key)
         if g is None:
             # warm up eagerly (fills the K/V and rotary caches, creates process groups, lets allocations settle), then capture
             s_in, t_in = sample.clone(), t.clone()
-            self._forward(s_in, t_in, ctx, L, cond_frame)
+            # (the warm-up of a storing walk pushes, and the replay below pushes again: the ring is put back in between)
+            ring = None if cache_phase is None else self.cache_set(sample.shape[0] * sample.shape[2] * sample.shape[3] * sample.shape[4])["ring"]
+            ring_was = None if ring is None else ring.clone()
+            self._forward(s_in, t_in, ctx, L, cond_frame, cache_phase=cache_phase)
             torch.cuda.synchronize()
             sharded = self.shard is not None and self.shard.world > 1
             err = None
@@ -967,7 +1119,7 @@ class _Engine:
                 self._rec = rec
                 try:
                     rec.begin_segment()
-                    out = self._forward(s_in, t_in, ctx, L, cond_frame)
+                    out = self._forward(s_in, t_in, ctx, L, cond_frame, cache_phase=cache_phase)
                     rec.end_segment()
                     err = None
                 except Exception as e:      # noqa: BLE001  capture refused (driver / RCCL state)
@@ -993,7 +1145,11 @@ class _Engine:
                 self._graph_broken = True
                 import warnings
                 warnings.warn(f"hipGraph capture of the denoising step failed ({type(err).__name__}: {err}); running eagerly")
-                return self._forward(sample, t, ctx, L, cond_frame)
+                if ring is not None:
+                    ring.copy_(ring_was)
+                return self._forward(sample, t, ctx, L, cond_frame, cache_phase=cache_phase)
+            if ring is not None:
+                ring.copy_(ring_was)
             g = (rec, s_in, t_in, out)
             self.graph_put(key, g)
         rec, s_in, t_in, out = g
