@@ -579,20 +579,12 @@ class SeerTrainer:
 
     # ================================================================================================ UNet schedule
     def _text_blocks(self) -> List[str]:
-        boc, lpb, n = self.eng.boc, self.eng.lpb, len(self.eng.boc)
-        names = []
-        for i in range(n - 1):
-            names += [f"down_blocks.{i}.attentions.{j}" for j in range(lpb)]
-        names.append("mid_block.attentions.0")
-        for i in range(1, n):
-            names += [f"up_blocks.{i}.attentions.{j}" for j in range(lpb + 1)]
-        return names
+        return [st.name for st in self.eng.seq if st.kind == "text"]
 
     def _unet_fwd(self, sample, t, ctx_bf16, ctx_len, cond_frame):
-        """the schedule of unet._Engine._forward, keeping what the backward needs.  Returns (pred fp32 [B,4,F,H,W], tape)."""
+        """the block sequence of the engine (unet.block_sequence), keeping what the backward needs.  Returns (pred fp32 [B,4,F,H,W], tape)."""
         ops, w, eng = self.ops, self.w, self.eng
         B, Cin, Fr, H, W = sample.shape
-        boc, lpb, n = eng.boc, eng.lpb, len(eng.boc)
         self._ctx, self._ctx_len = ctx_bf16, ctx_len
         if self._kv_cols is None:
             self._kv_cols, c = {}, 0
@@ -602,49 +594,40 @@ class SeerTrainer:
                 c += 2 * lvl_c
             self._kv_total = c
         self._dkv_all = torch.empty((ctx_bf16.shape[0], self._kv_total), device=sample.device, dtype=bf16)
-        emb = ops.timestep_embedding(t, boc[0], eng.cfg.flip_sin_to_cos, eng.cfg.freq_shift)
+        emb = ops.timestep_embedding(t, eng.boc[0], eng.cfg.flip_sin_to_cos, eng.cfg.freq_shift)
         emb = ops.linear_smallm(emb, w["time_embedding.linear_1.weight"], w["time_embedding.linear_1.bias"], silu_out=True)
         emb = ops.linear_smallm(emb, w["time_embedding.linear_2.weight"], w["time_embedding.linear_2.bias"])
         self._temb = ops.linear_smallm(emb, w["temb_all.w"], w["temb_all.b"], silu_in=True)
         tape: List[Tuple] = []
         self._fx = None
         if self.gn_fx:
-            self._fx = self._fx_arena = fx_arena(ops, sample, (eng.n_groupnorms() + 16) * B * 4 * max(boc) * 2,
+            self._fx = self._fx_arena = fx_arena(ops, sample, (eng.n_groupnorms() + 16) * B * 4 * max(eng.boc) * 2,
                                                  self._fx_arena, self._fx_retired)
         x = ops.conv_in(sample, w["conv_in.weight"], w["conv_in.bias"])
         skips = [x]
         geo = (B, Fr, H, W)
-        for i in range(n):
-            p = f"down_blocks.{i}"
-            for j in range(lpb):
-                x, s = self._resnet_fwd(f"{p}.resnets.{j}", x, None, geo); tape.append(("resnet", s))
-                if i < n - 1:
-                    x, s = self._text_fwd(f"{p}.attentions.{j}", x, geo); tape.append(("text", s))
-                    x, s = self._temporal_fwd(f"{p}.temporal_attentions.{j}", x, geo, cond_frame); tape.append(("temporal", s))
-                skips.append(x); tape.append(("push", None))
-            if i < n - 1:
-                x = ops.conv3x3(x, w[f"{p}.downsamplers.0.conv.weight"], B * Fr, geo[2], geo[3], stride=2,
-                                bias=w[f"{p}.downsamplers.0.conv.bias"], colsum_batch=self._cb(B))
-                tape.append(("down", (f"{p}.downsamplers.0.conv.weight", geo)))
-                geo = (B, Fr, (geo[2] - 1) // 2 + 1, (geo[3] - 1) // 2 + 1)
-                skips.append(x); tape.append(("push", None))
-        x, s = self._resnet_fwd("mid_block.resnets.0", x, None, geo); tape.append(("resnet", s))
-        x, s = self._text_fwd("mid_block.attentions.0", x, geo); tape.append(("text", s))
-        x, s = self._temporal_fwd("mid_block.temporal_attentions.0", x, geo, cond_frame); tape.append(("temporal", s))
-        x, s = self._resnet_fwd("mid_block.resnets.1", x, None, geo); tape.append(("resnet", s))
-        for i in range(n):
-            p = f"up_blocks.{i}"
-            for j in range(lpb + 1):
-                x, s = self._resnet_fwd(f"{p}.resnets.{j}", x, skips.pop(), geo); tape.append(("resnet_pop", s))
-                if i > 0:
-                    x, s = self._text_fwd(f"{p}.attentions.{j}", x, geo); tape.append(("text", s))
-                    x, s = self._temporal_fwd(f"{p}.temporal_attentions.{j}", x, geo, cond_frame); tape.append(("temporal", s))
-            if i < n - 1:
-                x = ops.conv3x3(x, w[f"{p}.upsamplers.0.conv.weight"], B * Fr, geo[2], geo[3], upsample=True,
-                                bias=w[f"{p}.upsamplers.0.conv.bias"], colsum_batch=self._cb(B))
-                tape.append(("up", (f"{p}.upsamplers.0.conv.weight", geo)))
-                geo = (B, Fr, geo[2] * 2, geo[3] * 2)
-        x, s = self._gn_fwd(x, None, B, Fr * geo[2] * geo[3], "conv_norm_out", eng.eps, True); tape.append(("gn_out", s))
+        for st in eng.seq:
+            kind, s = st.kind, None
+            if kind == "resnet":
+                x, s = self._resnet_fwd(st.name, x, skips.pop() if st.skip else None, geo)
+                kind = "resnet_pop" if st.skip else "resnet"
+            elif kind == "text":
+                x, s = self._text_fwd(st.name, x, geo)
+            elif kind == "temporal":
+                x, s = self._temporal_fwd(st.name, x, geo, cond_frame)
+            elif kind == "push":
+                skips.append(x)
+            elif kind == "down":
+                x = ops.conv3x3(x, w[st.name + ".weight"], B * Fr, geo[2], geo[3], stride=2, bias=w[st.name + ".bias"],
+                                colsum_batch=self._cb(B))
+                s, geo = (st.name + ".weight", geo), (B, Fr, (geo[2] - 1) // 2 + 1, (geo[3] - 1) // 2 + 1)
+            elif kind == "up":
+                x = ops.conv3x3(x, w[st.name + ".weight"], B * Fr, geo[2], geo[3], upsample=True, bias=w[st.name + ".bias"],
+                                colsum_batch=self._cb(B))
+                s, geo = (st.name + ".weight", geo), (B, Fr, geo[2] * 2, geo[3] * 2)
+            elif kind == "gn_out":
+                x, s = self._gn_fwd(x, None, B, Fr * geo[2] * geo[3], st.name, eng.eps, True)
+            tape.append((kind, s))
         pred = ops.conv_out(x, w["conv_out.weight"], w["conv_out.bias"], B, Fr, geo[2], geo[3])
         return pred, tape
 

@@ -15,7 +15,7 @@ import json
 import os
 from collections import OrderedDict
 from types import SimpleNamespace
-from typing import Dict, List, Optional, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -302,8 +302,8 @@ class SeerUNet(nn.Module):
 
 
 # =====================================================================================================================
-FX_MAX_ROWS = 100_000        # rows at the finest level up to which the LayerNorms are folded (see _Engine._forward)
-FX_MAX_ROWS_PB = int(os.environ.get("SEER_FX_MAX_ROWS_PB", "4096"))        # rows per batch element up to which a GroupNorm's statistics are accumulated in fixed point (_Engine._cb)
+FX_MAX_ROWS = 100_000        # rows at the finest level up to which the LayerNorms are folded (_LaunchPlan.ln_on)
+FX_MAX_ROWS_PB = int(os.environ.get("SEER_FX_MAX_ROWS_PB", "4096"))        # rows per batch element up to which a GroupNorm's statistics are accumulated in fixed point (_LaunchPlan.colsum_batch)
 
 
 def _switch(model, attr: str, env: Optional[str] = None, default: bool = True) -> bool:
@@ -362,6 +362,126 @@ def fx_arena(ops, sample, need: int, arena, retired: list):
     return arena
 
 
+class Step(NamedTuple):
+    kind: str               # resnet | text | temporal | push | down | up | gn_out; in a step-caching walk also cache_push | cache_forecast
+    name: str = ""          # the module's path (down / up: the conv's)
+    skip: bool = False      # resnet: takes the skip connection pushed last (unet_3d_blocks.py:596,712)
+    feeds: bool = False     # resnet: a transformer follows -- the output's only GroupNorm is that transformer's
+
+
+def block_sequence(boc, lpb):
+    """THE block sequence of the UNet (unet_3d_condition.py:283-376), written once: the steps behind conv_in, in order.  _Engine walks
+    it (whole, or the selection of a cached evaluation: _Engine._steps), SeerTrainer._unet_fwd walks it onto its tape; the text blocks,
+    the GroupNorm count and the attention maps wanted are filters over it."""
+    n = len(boc)
+
+    def layer(p, j, skip, attn):
+        yield Step("resnet", f"{p}.resnets.{j}", skip, attn)
+        if attn:
+            yield Step("text", f"{p}.attentions.{j}")
+            yield Step("temporal", f"{p}.temporal_attentions.{j}")
+    for i in range(n):
+        for j in range(lpb):
+            yield from layer(f"down_blocks.{i}", j, False, i < n - 1)
+            yield Step("push")
+        if i < n - 1:
+            yield Step("down", f"down_blocks.{i}.downsamplers.0.conv")
+            yield Step("push")
+    yield from layer("mid_block", 0, False, True)
+    yield Step("resnet", "mid_block.resnets.1")
+    for i in range(n):
+        for j in range(lpb + 1):
+            yield from layer(f"up_blocks.{i}", j, True, i > 0)
+        if i < n - 1:
+            yield Step("up", f"up_blocks.{i}.upsamplers.0.conv")
+    yield Step("gn_out", "conv_norm_out")
+
+
+class _LaunchPlan:
+    """the launch forms of ONE evaluation, decided once (at the top of _Engine._forward: nothing has been launched) and read by
+    the block functions.  The mode is read HERE and nowhere below: a layout-invariant engine decides by _one_element_all_frames, every
+    other by _rows_of_the_call.  The answers per (form, channel width, rows per batch element) are memoised: the producer of a tensor
+    and its consumer read ONE answer.  Whether _pack made a block's fused weights stays with the blocks."""
+
+    def __init__(self, eng, B, Fr, H, W, cond_frame):
+        ops, sh = eng.ops, eng.shard
+        self.ops, self.B, self.shard = ops, B, sh
+        self.exact = eng.inv                    # GroupNorm statistics: exact integer sums of the stored activations (no producer sums)
+        self._rule = self._one_element_all_frames if eng.inv else self._rows_of_the_call
+        self._widths = {"chain": ops.ROWCHAIN_C, "chain2": ops.ROWCHAIN_C} if eng.rowchain else {}
+        self._widths["ff_fused"] = getattr(ops, "FF_FUSED_C", -1)
+        self._sums = eng.gn_colsums and not eng.inv
+        self._memo: Dict[Tuple, bool] = {}
+        self.arena = None                       # the evaluation's ops.FxArena while the GroupNorm sums are accumulated (_forward)
+        # the folded LayerNorm trades a launch per norm for atomics in proportion to the rows: ahead up to ~100 k rows at the finest
+        # level (config 2: 24 576 rows -0.19 ms; 64x64 latent, 98 304 rows: even; bridge, 131 072 rows: +0.15 ms --
+        # profiles/r04_fx_ln_other_configs.log), off above
+        self.ln_on = eng.ln_fold and (self._all_frames(Fr * H * W) if eng.inv else B * Fr * H * W) <= FX_MAX_ROWS
+        self.fx_gn = bool((eng.gn_fx and eng.gn_colsums) or eng.inv)    # (per tensor: colsum_batch; frame shards all-reduce the integer sums: FrameShard.reduce_fx)
+        # the temporal feed-forward skips the conditioning frames (attention.py:241-246).  ff_whole: every local row takes it, so it
+        # runs in its folded / fused forms.  Layout-invariant engines decide on the CLIP's conditioning frames: a frame shard that
+        # holds none of them must run the form the unsharded clip runs on those frames
+        self.skip_frames = cond_frame if sh is None else sh.local_cond_frames(cond_frame)
+        self.ff_whole = self.skip_frames <= 0 and not (eng.inv and cond_frame > 0)
+        # every level's chain is asked now: a clip sharded too finely is refused before the first launch of the evaluation
+        for C in eng.boc:
+            self.runs("chain", C, Fr * H * W)
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+
+    def _rows_of_the_call(self, form, rows_pb):
+        """THE DEFAULT RULE: the rows of the call (B elements of this rank's frames) and the device's compute units.  Frame shards
+        exchange the GroupNorm statistics between the two steps and keep the separate launches in front of q|k|v (batch groups alone run
+        the single-process forms)."""
+        ops, rows = self.ops, self.B * rows_pb
+        if form == "chain":
+            return (self.shard is None or not self.shard.exact_stats) and rows_pb >= ops.ROWCHAIN_ROWS and ops.rowchain_pays(rows)
+        return ops.rowchain_pays(rows, products=2) if form == "chain2" else ops.ff_fused_pays(rows)
+
+    def _all_frames(self, rows_pb):
+        """rows per batch element over ALL frames of the clip (a frame shard holds local_frames of total_frames)"""
+        sh = self.shard
+        return rows_pb if sh is None or not sh.local_frames else rows_pb // sh.local_frames * sh.total_frames
+
+    def _one_element_all_frames(self, form, rows_pb):
+        """THE LAYOUT-INVARIANT RULE: ONE batch element over all its frames -- half of ops.FF_FUSED_MIN_ROWS, the rows from which a CFG
+        pair takes the row-owner launches by default -- and nothing else: not the batch, not the shard's share, not the device."""
+        ops, sh = self.ops, self.shard
+        ok = self._all_frames(rows_pb) >= ops.FF_FUSED_MIN_ROWS // 2
+        if form == "chain":         # (it reads exact sums, exchanged between frame shards first: _Engine._rc_in)
+            ok = ok and hasattr(ops, "groupnorm_stats_fx")
+            if ok and sh is not None and sh.local_frames:
+                # the launch needs ROWCHAIN_ROWS rows of a batch element on EVERY rank; falling back on one of them would give other
+                # bits than the unsharded clip.  Decided from the shard table every rank holds, before any launch: all refuse together
+                least = rows_pb // sh.local_frames * min(sh.frame_counts)
+                if least < ops.ROWCHAIN_ROWS:
+                    raise RuntimeError(f"layout_invariant: {least} rows per batch element on the smallest of {len(sh.frame_counts)} frame "
+                                       f"shards, the GroupNorm -> q|k|v launch needs {ops.ROWCHAIN_ROWS}: use fewer frame shards")
+        return ok
+
+    def runs(self, form, C, rows_pb):
+        """does `form` run over [B * rows_pb, C]?  "chain": GroupNorm -> proj_in -> norm1 -> q|k|v as one launch (ops.rowchain) -- read by
+        the consumer (_rc_in) and by the PRODUCER of its input, which then accumulates the column sums whatever the tensor's size
+        (colsum_batch(feeds=)): the chain reads them directly and the statistics launch in front of it goes too; "chain2": behind a
+        chain that ran, attn1.to_out + residual -> norm2 -> attn2.to_q as one launch; "ff_fused": the feed-forward + proj_out of a block
+        that has the weights as the fused launch (ops.ff_fused)"""
+        key = (form, C, rows_pb)
+        if key not in self._memo:
+            self._memo[key] = bool(C == self._widths.get(form) and self._rule(form, rows_pb))
+        return self._memo[key]
+
+    def colsum_batch(self, rows_pb, feeds=None):
+        """`colsum_batch` of a launch whose output (rows_pb rows per batch element) feeds a GroupNorm: (B, arena) = accumulate in
+        fixed point, B = per-tile sums, 0 = none.  feeds: the width of the transformer whose GroupNorm is the output's only one --
+        accumulated where that one runs as a chain.  The accumulated form wins where the tensor is small (its apply launch owns slices
+        of 64..128 channels: 160-byte pieces of a 640-byte row at the 32x32 level, ~20 % below the full-row kernel's bandwidth, and
+        eight replicas to add per block): from the 16x16 level down 7.5 / 9.6 / 5.7 / 3.8 us against 8.4 / 12.1 / 7.6 / 5.7 for
+        finalize + apply, at the 32x32 level 12.6 / 27.9 against 11.3 / 25.6 (profiles/r04_gn_fx_by_level.log)."""
+        if not self._sums:
+            return 0
+        fx = self.arena is not None and (rows_pb <= FX_MAX_ROWS_PB or (feeds is not None and self.runs("chain", feeds, rows_pb)))
+        return (self.B, self.arena) if fx else self.B
+
+
 class _Engine:
     """packed weights + the kernel schedule of one SeerUNet forward."""
 
@@ -377,6 +497,7 @@ class _Engine:
         self.lpb = self.cfg.layers_per_block
         self.heads = self.cfg.attention_head_dim
         self.G = self.cfg.norm_num_groups
+        self.seq: Tuple[Step, ...] = tuple(block_sequence(self.boc, self.lpb))
         self.eps = self.cfg.norm_eps
         # The switches, resolved here and nowhere else (_switch: the model's attribute if set, else the environment variable, else
         # on), each with what it needs.  A/B runs and the tests run the older forms through them.
@@ -401,16 +522,15 @@ class _Engine:
         # layout_invariant (OFF unless asked for): every choice below that looks at the rows of the call, at the device or at the shard
         #   layout is made per batch element on the clip's whole frame count instead -- the invariant GEMM plan and the pinned attention
         #   form (_InvariantOps), exact integer GroupNorm statistics from the stored activations (no producer sums: their float partials
-        #   follow the tiles), the 320-channel launches by _pays320.  Same bits for any batch, CFG layout or shard layout; slower.
+        #   follow the tiles), the 320-channel launches by _LaunchPlan._one_element_all_frames.  Same bits for any batch, CFG layout or shard layout; slower.
         #   (fold_ln=False: the trainer's engine ignores it, as it ignores ln_fold)
         self.inv = bool(fold_ln) and _switch(model, "layout_invariant", "SEER_LAYOUT_INVARIANT", default=False)
         if self.inv:
             self.ops = _InvariantOps(ops)
         self._fx_arena = None
         self._fx_retired: List[object] = []
-        self._fx = None
+        self._plan: Optional[_LaunchPlan] = None    # the launch forms of the running evaluation (_forward)
         self.ln_folded = 0
-        self._ln_on = False
         self.rowchains = 0
         self._ffpre_bias: Dict[str, str] = {}
         self.gn_from_colsums = 0
@@ -422,7 +542,8 @@ class _Engine:
         self._graphs: Dict[Tuple, object] = {}     # captured steps (whole-step graphs and sampler-step graphs), LRU: see graph_get / graph_put
         self._rec = None                # _SegmentRecorder while a segmented capture is running
         self._attn_list = None          # list that collects the text cross-attention scores of a return_attn forward
-        self._attn_wanted = ()
+        # ... of the last text block of each container: the reference's containers overwrite attn_map layer by layer
+        self._attn_wanted = set({st.name.rsplit(".", 1)[0]: st.name for st in self.seq if st.kind == "text"}.values())
         self.freeu_on = False           # FreeU (SeerUNet.enable_freeu): set_freeu
         self._freeu_buf = None          # fp32 (b1, s1, b2, s2) on the device, read by the seer_freeu launches
         self.cache_branch = None        # step caching (SeerUNet.enable_step_cache): the branch while it is on, set_step_cache
@@ -651,62 +772,20 @@ class _Engine:
         self._stats_i += 1
         y, from_colsums = groupnorm(self.ops, x1, x2, B, self.G, rows_pb, eps, self.w[name + ".weight"], self.w[name + ".bias"], silu,
                                     stats=self._stats_arena[self._stats_i - 1], use_colsums=self.gn_colsums, fused=self.gn_fused,
-                                    shard=self.shard, sync=self.sync_point, arena=self._fx, exact=self.inv)
+                                    shard=self.shard, sync=self.sync_point, arena=self._plan.arena, exact=self._plan.exact)
         self.gn_from_colsums += from_colsums
         return y
-
-    def _rows_all(self, rows_pb):
-        """rows per batch element over ALL frames of the clip (a frame shard holds local_frames of total_frames)"""
-        sh = self.shard
-        return rows_pb if sh is None or not sh.local_frames else rows_pb // sh.local_frames * sh.total_frames
-
-    def _pays320(self, rows_pb):
-        """layout-invariant engines: do the row-owner launches of the 320-channel level (ops.rowchain, ops.ff_fused) run?  Decided on
-        the rows of ONE batch element over all its frames -- half of ops.FF_FUSED_MIN_ROWS, the rows from which a CFG pair takes them
-        by default -- and on nothing else: not the batch, not the shard's share, not the device."""
-        return self._rows_all(rows_pb) >= self.ops.FF_FUSED_MIN_ROWS // 2
-
-    def _cb(self, B, rows_pb, for_chain=False):
-        """`colsum_batch` of a launch whose output (rows_pb rows per batch element) feeds a GroupNorm: (B, arena) = accumulate in
-        fixed point, B = per-tile sums.  The accumulated form wins where the tensor is small (its apply launch owns slices of
-        64..128 channels: 160-byte pieces of a 640-byte row at the 32x32 level, ~20 % below the full-row kernel's bandwidth, and
-        eight replicas to add per block): from the 16x16 level down 7.5 / 9.6 / 5.7 / 3.8 us against 8.4 / 12.1 / 7.6 / 5.7 for
-        finalize + apply, at the 32x32 level 12.6 / 27.9 against 11.3 / 25.6 (profiles/r04_gn_fx_by_level.log)."""
-        if not self.gn_colsums or self.inv:         # (inv: every GroupNorm sums its stored activations exactly, _gn)
-            return 0
-        return (B, self._fx) if (self._fx is not None and (rows_pb <= FX_MAX_ROWS_PB or for_chain)) else B
-
-    def _chain_ok(self, C, B, rows_pb):
-        """will a transformer's GroupNorm -> proj_in -> norm1 -> q|k|v over [B * rows_pb, C] run as one launch (ops.rowchain)?  Asked
-        by the consumer (_rc_in) and by the PRODUCER of its input, which then accumulates the column sums whatever the tensor's size
-        (_cb(for_chain=True)): the chain reads them directly and the statistics launch in front of it goes too (the apply launch
-        that made the accumulated form lose at the 32x32 level is not run at all there).  Frame shards exchange the statistics
-        between the two steps and keep the separate launches (batch groups alone run the single-process forms)."""
-        ops = self.ops
-        if self.inv:        # (the chain reads exact sums, exchanged between frame shards first: _rc_in)
-            ok = bool(self.rowchain and C == ops.ROWCHAIN_C and hasattr(ops, "groupnorm_stats_fx") and self._pays320(rows_pb))
-            sh = self.shard
-            if ok and sh is not None and sh.local_frames:
-                # the launch needs ROWCHAIN_ROWS rows of a batch element on EVERY rank; falling back on one of them would give other
-                # bits than the unsharded clip.  Decided from the shard table every rank holds, before any exchange: all refuse together
-                least = rows_pb // sh.local_frames * min(sh.frame_counts)
-                if least < ops.ROWCHAIN_ROWS:
-                    raise RuntimeError(f"layout_invariant: {least} rows per batch element on the smallest of {len(sh.frame_counts)} frame "
-                                       f"shards, the GroupNorm -> q|k|v launch needs {ops.ROWCHAIN_ROWS}: use fewer frame shards")
-            return ok
-        return bool(self.rowchain and (self.shard is None or not self.shard.exact_stats) and C == ops.ROWCHAIN_C and
-                    rows_pb >= ops.ROWCHAIN_ROWS and ops.rowchain_pays(B * rows_pb))
 
     def _rc_in(self, p, tb, x, B, rows_pb, rotary, qs):
         """GroupNorm -> proj_in -> norm1 -> q|k|v of transformer `p` as one launch: (h, qkv), or None when this block / shape keeps
         the separate launches"""
-        ops, w = self.ops, self.w
-        if not self._chain_ok(x.shape[1], B, rows_pb) or (p + ".rc.proj_in") not in w:
+        ops, w, plan = self.ops, self.w, self._plan
+        if not plan.runs("chain", x.shape[1], rows_pb) or (p + ".rc.proj_in") not in w:
             return None
-        if self.inv:
+        if plan.exact:
             # exact integer sums of x's stored values, added over the frame shards: the statistics of the unsharded clip, bit for bit
             if not isinstance(getattr(x, "colsums", None), ops.ColSumsFx):
-                x.colsums = ops.groupnorm_stats_fx(x, B, self._fx)
+                x.colsums = ops.groupnorm_stats_fx(x, B, plan.arena)
             st, count, from_colsums = x.colsums, rows_pb * (x.shape[1] // self.G), False
             if self.shard is not None:
                 count = self.shard.reduce_fx((st,), count, sync=self.sync_point)
@@ -717,7 +796,7 @@ class _Engine:
                          gn=(st, count, 1e-6, w[p + ".norm.weight"], w[p + ".norm.bias"], rows_pb, self.G),
                          ln=(w[tb + ".norm1.weight"], w[tb + ".norm1.bias"], 1e-5), w2f=w[tb + ".rc.qkv"], col_scale=(qs, 1), rotary=rotary)
         if r is None:
-            assert not self.inv, "layout_invariant: _chain_ok let a shape through that ops.rowchain refuses"
+            assert not plan.exact, "layout_invariant: the plan let a shape through that ops.rowchain refuses"
             return None
         self._stats_i += 1
         self.gn_from_colsums += from_colsums
@@ -726,11 +805,10 @@ class _Engine:
 
     def _resnet(self, p, x, skip, geo, feeds_transformer=False):
         """ResnetBlock3D (resnet.py:174-208); `skip` is the channel-concat partner of unet_3d_blocks.py:596,712.  feeds_transformer:
-        the output's only GroupNorm is the next transformer's (see _chain_ok)."""
-        ops, w = self.ops, self.w
+        the output's only GroupNorm is the next transformer's (see _LaunchPlan.runs)."""
+        ops, w, plan = self.ops, self.w, self._plan
         B, Fr, H, W = geo
         rows_pb = Fr * H * W
-        cb = self._cb(B, rows_pb)          # outputs that feed a GroupNorm leave their column sums behind
         fu = self._freeu_params(p) if skip is not None else None
         if fu is not None:
             # FreeU, in front of everything the resnet does with its inputs: a new pair without column sums (norm1 takes its
@@ -739,17 +817,18 @@ class _Engine:
         h = self._gn(x, skip, B, rows_pb, p + ".norm1", self.eps, True)
         off, n = self.temb_slices[p]
         temb = self._temb[:, off:off + n]
+        # (outputs that feed a GroupNorm leave their column sums behind)
         h = ops.conv3x3(h, w[p + ".conv1.weight"], B * Fr, H, W, bias=w[p + ".conv1.bias"], rowvec=temb,
-                        rows_per_batch=rows_pb, colsum_batch=cb)
+                        rows_per_batch=rows_pb, colsum_batch=plan.colsum_batch(rows_pb))
         h = self._gn(h, None, B, rows_pb, p + ".norm2", self.eps, True)
         if (p + ".conv_shortcut.weight") in w:
             sc = ops.gemm(x, w[p + ".conv_shortcut.weight"], a2=skip, bias=w[p + ".conv_shortcut.bias"])
         else:
             assert skip is None
             sc = x
-        if feeds_transformer and self._chain_ok(w[p + ".conv2.weight"].shape[0], B, rows_pb):
-            cb = self._cb(B, rows_pb, for_chain=True)
-        return ops.conv3x3(h, w[p + ".conv2.weight"], B * Fr, H, W, bias=w[p + ".conv2.bias"], residual=sc, colsum_batch=cb)
+        w2 = w[p + ".conv2.weight"]
+        return ops.conv3x3(h, w2, B * Fr, H, W, bias=w[p + ".conv2.bias"], residual=sc,
+                           colsum_batch=plan.colsum_batch(rows_pb, feeds=w2.shape[0] if feeds_transformer else None))
 
     def _ln_gemm(self, h, tb, norm, wkey, bias_key=None, **kw):
         """LayerNorm `tb + norm` followed by the projection `wkey`: one GEMM when the producer of h left its row statistics and the
@@ -767,29 +846,26 @@ class _Engine:
 
     def _rs(self):
         """extra arguments of a GEMM whose output rows feed a LayerNorm"""
-        return {"rowstat": self._fx_arena if self._fx_arena is not None else True} if self._ln_on else {}
+        return {"rowstat": self._fx_arena if self._fx_arena is not None else True} if self._plan.ln_on else {}
 
     def _ff(self, tb, h_rows):
         ops, w = self.ops, self.w
         g = self._ln_gemm(h_rows, tb, ".norm3", tb + ".ff.net.0.proj.weight", tb + ".ff.net.0.proj.bias", geglu=True)
         ops.gemm(g, w[tb + ".ff.net.2.weight"], bias=w[tb + ".ff.net.2.bias"], residual=h_rows, out=h_rows)
 
-    def _ff_fused_rows(self, p, h):
-        """will _ff_proj_out run transformer `p`'s feed-forward over the rows of h as the fused launch?"""
-        if self.inv:
-            return (p + ".ff_fused.w1f") in self.w and self._pays320(h.shape[0] // self._B)
-        return (p + ".ff_fused.w1f") in self.w and self.ops.ff_fused_pays(h.shape[0])
+    def _ff_forms(self, p, tb, C, rows_pb):
+        """(fused, pre) of transformer `p` over all its rows: will _ff_proj_out run its feed-forward as the fused launch, and will the
+        block's last to_out + residual ride in that launch (ops.ff_fused(pre=))?  The block's weights (_pack) and the plan"""
+        fused = (p + ".ff_fused.w1f") in self.w and self._plan.runs("ff_fused", C, rows_pb)
+        return fused, fused and (tb + ".ffpre.wo") in self.w
 
-    def _ff_pre(self, p, tb, h):
-        """will the block's last to_out + residual ride in the fused feed-forward launch (ops.ff_fused(pre=))?"""
-        return (tb + ".ffpre.wo") in self.w and self._ff_fused_rows(p, h)
-
-    def _ff_proj_out(self, p, tb, h, x, cb, a=None):
-        """the feed-forward of block `tb` and the transformer's proj_out + residual x: folded into one two-source GEMM when the
-        block's weights were (see _pack), else ff.net.2 + residual and proj_out + residual as two launches.  `a` (only with
-        _ff_pre): the attention output whose to_out projection + residual h the fused launch computes itself."""
+    def _ff_proj_out(self, p, tb, h, x, cb, fused, a=None):
+        """the feed-forward of block `tb` and the transformer's proj_out + residual x: the fused launch where _ff_forms said so, else
+        folded into one two-source GEMM when the block's weights were (see _pack), else ff.net.2 + residual and proj_out + residual
+        as two launches.  `a` (only with _ff_forms' pre): the attention output whose to_out projection + residual h the fused launch
+        computes itself."""
         ops, w = self.ops, self.w
-        if self._ff_fused_rows(p, h):
+        if fused:
             pre = None if a is None else (a, w[tb + ".ffpre.wo"], w[self._ffpre_bias[tb]])
             y = ops.ff_fused(h, x, w[tb + ".norm3.weight"], w[tb + ".norm3.bias"], w[p + ".ff_fused.w1f"],
                              w[tb + ".ff.net.0.proj.bias"], w[p + ".ff_fused.wcf"], w[p + ".ffproj.b"], colsum_batch=cb, pre=pre)
@@ -804,12 +880,13 @@ class _Engine:
 
     def _text_transformer(self, p, x, geo):
         """SpatialTransformer3D + BasicTextTransformerBlock3D (attention.py:129-145, 308-327)."""
-        ops, w = self.ops, self.w
+        ops, w, plan = self.ops, self.w, self._plan
         B, Fr, H, W = geo
         C = x.shape[1]
         heads, d = self.heads, C // self.heads
         HW = H * W
         tb = p + ".transformer_blocks.0"
+        fused, pre = self._ff_forms(p, tb, C, Fr * HW)
         # the q columns leave the projection as q * scale * log2(e) (one bf16 rounding): the attention kernels exponentiate
         # the raw dot products
         qs = ops.qk_prescale(d)
@@ -826,7 +903,7 @@ class _Engine:
                       Sq=HW, Sk=HW, q_prescaled=True)
         # text cross attention per frame (K/V depend on the context only: cached across DDIM steps)
         q = None
-        if rc is not None and (tb + ".rc.q") in w and (self._pays320(Fr * HW) if self.inv else ops.rowchain_pays(a.shape[0], products=2)):
+        if rc is not None and (tb + ".rc.q") in w and plan.runs("chain2", C, Fr * HW):
             # attn1.to_out + residual (over h) -> norm2 -> attn2.to_q, one launch
             r2 = ops.rowchain(a, w[tb + ".rc.to_out"], b1=w[tb + ".attn1.to_out.0.bias"], res=h, h_out=h,
                               ln=(w[tb + ".norm2.weight"], w[tb + ".norm2.bias"], 1e-5), w2f=w[tb + ".rc.q"], col_scale=(qs, 1))
@@ -845,13 +922,13 @@ class _Engine:
             self._attn_list.append(self._cross_scores(q, kv[:, :C], B, Fr, H, W, heads, d, L))
         ops.attention(q, kv[:, :C], kv[:, C:], a, batch=B * Fr, heads=heads, head_dim=d, Sq=HW, Sk=L, q_prescaled=True)
         # (the output's only GroupNorm is the temporal transformer's: accumulated sums when that one runs as a chain)
-        cb = self._cb(B, Fr * HW, for_chain=self._chain_ok(C, B, Fr * HW))
-        if self._ff_pre(p, tb, h):
-            return self._ff_proj_out(p, tb, h, x, cb, a=a)      # attn2.to_out + residual inside the fused feed-forward launch
+        cb = plan.colsum_batch(Fr * HW, feeds=C)
+        if pre:
+            return self._ff_proj_out(p, tb, h, x, cb, fused, a=a)      # attn2.to_out + residual inside the fused feed-forward launch
         # (the fused feed-forward normalises its rows itself: no row statistics asked of their producer)
         ops.gemm(a, w[tb + ".attn2.to_out.0.weight"], bias=w[tb + ".attn2.to_out.0.bias"], residual=h, out=h,
-                 **({} if self._ff_fused_rows(p, h) else self._rs()))
-        return self._ff_proj_out(p, tb, h, x, cb)
+                 **({} if fused else self._rs()))
+        return self._ff_proj_out(p, tb, h, x, cb, fused)
 
     def _cross_scores(self, q, k, B, Fr, H, W, heads, d, L):
         """`attention_scores` of the text cross attention (attention.py:556-584: scale * Q K^T before the softmax) as
@@ -879,10 +956,10 @@ class _Engine:
             self._rot_cache[key] = t
         return t
 
-    def _temporal_transformer(self, p, x, geo, cond_frame):
+    def _temporal_transformer(self, p, x, geo):
         """SpatialTransformer3D + BasicTransformerBlock3D(temporal) + WindowSTempAttention
         (attention.py:129-145, 231-248, 632-703)."""
-        ops, w = self.ops, self.w
+        ops, w, plan = self.ops, self.w, self._plan
         B, Fr, H, W = geo
         C = x.shape[1]
         heads, d = self.heads, C // self.heads
@@ -912,64 +989,59 @@ class _Engine:
             else:
                 ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], a, batch=B, heads=heads, head_dim=d,
                               Sq=Fr * HW, Sk=Fr * HW, causal=True, q_prescaled=True)
-        # FF skips the conditioning frames (attention.py:241-246); frames are the slow index inside a batch element
-        skip_f = cond_frame if self.shard is None else self.shard.local_cond_frames(cond_frame)
-        # whole: every local row takes the feed-forward, so it runs in its folded / fused forms.  Layout-invariant engines decide on the
-        # CLIP's conditioning frames: a frame shard that holds none of them must run the form the unsharded clip runs on those frames
-        whole = skip_f <= 0 and not (self.inv and cond_frame > 0)
-        if whole and self._ff_pre(p, tb, h):
-            return self._ff_proj_out(p, tb, h, x, self._cb(B, Fr * HW), a=a)    # attn1.to_out + residual inside the fused feed-forward launch
+        # FF skips the conditioning frames (attention.py:241-246; _LaunchPlan.ff_whole); frames are the slow index inside a batch element
+        skip_f, cb = plan.skip_frames, plan.colsum_batch(Fr * HW)
+        fused, pre = self._ff_forms(p, tb, C, Fr * HW) if plan.ff_whole else (False, False)
+        if pre:
+            return self._ff_proj_out(p, tb, h, x, cb, fused, a=a)    # attn1.to_out + residual inside the fused feed-forward launch
         ops.gemm(a, w[tb + ".attn1.to_out.0.weight"], bias=w[tb + ".attn1.to_out.0.bias"], residual=h, out=h,
-                 **({} if whole and self._ff_fused_rows(p, h) else self._rs()))
-        if whole:
-            return self._ff_proj_out(p, tb, h, x, self._cb(B, Fr * HW))
+                 **({} if fused else self._rs()))
+        if plan.ff_whole:
+            return self._ff_proj_out(p, tb, h, x, cb, fused)
         elif skip_f < Fr:
             for b in range(B):
                 self._ff(tb, h[b * Fr * HW + skip_f * HW:(b + 1) * Fr * HW])
-        return ops.gemm(h, w[p + ".proj_out.weight"], bias=w[p + ".proj_out.bias"], residual=x,
-                        colsum_batch=self._cb(B, Fr * HW))
+        return ops.gemm(h, w[p + ".proj_out.weight"], bias=w[p + ".proj_out.bias"], residual=x, colsum_batch=cb)
 
     # ---- the schedule ---------------------------------------------------------------------------------------------
     def n_groupnorms(self):
-        return sum(1 for k in self.w if k.endswith(".weight") and
-                   (k.endswith("norm1.weight") or k.endswith("norm2.weight") or k.endswith(".norm.weight") or
-                    k == "conv_norm_out.weight") and "transformer_blocks" not in k)
+        return sum({"resnet": 2, "text": 1, "temporal": 1, "gn_out": 1}.get(st.kind, 0) for st in self.seq)
+
+    def _steps(self, cache_phase) -> Tuple[Step, ...]:
+        """the steps of one evaluation (_forward): the sequence, or -- step caching -- the sequence around its cut, by position"""
+        seq = self.seq
+        if cache_phase is None:
+            return seq
+        cut = next(i for i, st in enumerate(seq) if st.name == f"up_blocks.{len(self.boc) - 1}.resnets.{self.lpb - self.cache_branch}")
+        if not cache_phase:
+            return seq[:cut] + (Step("cache_push"),) + seq[cut:]
+        pushes = [i for i, st in enumerate(seq) if st.kind == "push"]
+        head = seq[:pushes[self.cache_branch - 1] + 1] if self.cache_branch else ()
+        return head + (Step("cache_forecast"),) + seq[cut:]
 
     def _forward(self, sample, t, ctx_bf16, ctx_len, cond_frame, return_attn=False, cache_phase=None):
         """cache_phase (step caching; the launches only -- the host's half is cache_note): None = the schedule as it always was;
         0 = the same, plus one cache_push of the cut feature, the backbone input of up_blocks.{n-1}.resnets.{lpb - branch}; d >= 1 =
         the cached walk: time embedding, conv_in, the first `branch` layers of down_blocks.0, one cache_forecast, the layers lpb -
-        branch .. lpb of the last up block, conv_norm_out, conv_out."""
+        branch .. lpb of the last up block, conv_norm_out, conv_out (_steps)."""
         ops, w = self.ops, self.w
         B, Cin, Fr, H, W = sample.shape
-        boc, lpb, n = self.boc, self.lpb, len(self.boc)
+        plan = self._plan = _LaunchPlan(self, B, Fr, H, W, cond_frame)          # (raises where it refuses: nothing is launched above this line)
         cache = None if cache_phase is None else self.cache_set(B * Fr * H * W)
-        cut = None if cache is None else lpb - self.cache_branch          # the layer of the last up block the cut feature enters
         self._attn_list = [] if return_attn else None
-        # the last text block of each container: the reference's containers overwrite attn_map layer by layer
-        self._attn_wanted = {f"down_blocks.{i}.attentions.{lpb - 1}" for i in range(n - 1)} | {"mid_block.attentions.0"} | \
-                            {f"up_blocks.{i}.attentions.{lpb}" for i in range(1, n)}
         self._ctx, self._ctx_len = ctx_bf16, ctx_len
-        self._B = B
         self._stats_arena = torch.empty((self.n_groupnorms(), B, self.G, 2), device=sample.device, dtype=torch.float32)
         self._stats_i = 0
         self.gn_from_colsums = 0        # GroupNorms of this forward that took their statistics from column sums
         self.ln_folded = 0              # LayerNorms of this forward that ran inside the consuming GEMM
         self.rowchains = 0              # ops.rowchain launches of this forward
-        self._fx = None
-        # the folded LayerNorm trades a launch per norm for atomics in proportion to the rows: ahead up to ~100 k rows at the finest
-        # level (config 2: 24 576 rows -0.19 ms; 64x64 latent, 98 304 rows: even; bridge, 131 072 rows: +0.15 ms --
-        # profiles/r04_fx_ln_other_configs.log), off above
-        small = (self._rows_all(Fr * H * W) if self.inv else B * Fr * H * W) <= FX_MAX_ROWS
-        fx_gn = (self.gn_fx and self.gn_colsums) or self.inv      # (per tensor: _cb; frame shards all-reduce the integer sums: FrameShard.reduce_fx)
-        self._ln_on = self.ln_fold and small
-        if (fx_gn or self._ln_on) and hasattr(ops, "FxArena"):
+        if (plan.fx_gn or plan.ln_on) and hasattr(ops, "FxArena"):
             # fixed-point accumulators of the evaluation: a [reps, B, 2, C] slot per colsum producer, a [rows, 2] slot per producer
             # of LayerNorm rows
-            need = (self.n_groupnorms() + 16) * B * 4 * max(boc) * 2 + 5 * 16 * B * Fr * H * W * 2
+            need = (self.n_groupnorms() + 16) * B * 4 * max(self.boc) * 2 + 5 * 16 * B * Fr * H * W * 2
             self._fx_arena = fx_arena(ops, sample, need, self._fx_arena, self._fx_retired)
-            self._fx = self._fx_arena if fx_gn else None
-        emb = ops.timestep_embedding(t, boc[0], self.cfg.flip_sin_to_cos, self.cfg.freq_shift)
+            plan.arena = self._fx_arena if plan.fx_gn else None
+        emb = ops.timestep_embedding(t, self.boc[0], self.cfg.flip_sin_to_cos, self.cfg.freq_shift)
         emb = ops.linear_smallm(emb, w["time_embedding.linear_1.weight"], w["time_embedding.linear_1.bias"], silu_out=True)
         emb = ops.linear_smallm(emb, w["time_embedding.linear_2.weight"], w["time_embedding.linear_2.bias"])
         self._temb = ops.linear_smallm(emb, w["temb_all.w"], w["temb_all.b"], silu_in=True)
@@ -980,54 +1052,33 @@ class _Engine:
             ops.conv_in(sample, w["conv_in.weight"], w["conv_in.bias"], dtype=self.dt)
         skips = [x]
         geo = (B, Fr, H, W)
-        if cache_phase:
-            # a cached evaluation: the skips s_0 .. s_branch of level 0, then the last up block from the forecast cut feature on.  The
-            # forecast is a fresh view of the static buffer, without column sums: norm1 takes its statistics pass, as behind ops.freeu
-            for j in range(self.cache_branch):
-                x = self._resnet(f"down_blocks.0.resnets.{j}", x, None, geo, feeds_transformer=True)
-                x = self._text_transformer(f"down_blocks.0.attentions.{j}", x, geo)
-                x = self._temporal_transformer(f"down_blocks.0.temporal_attentions.{j}", x, geo, cond_frame)
+        for st in self._steps(cache_phase):
+            kind = st.kind
+            if kind == "resnet":
+                x = self._resnet(st.name, x, skips.pop() if st.skip else None, geo, feeds_transformer=st.feeds)
+            elif kind == "text":
+                x = self._text_transformer(st.name, x, geo)
+            elif kind == "temporal":
+                x = self._temporal_transformer(st.name, x, geo)
+            elif kind == "push":
                 skips.append(x)
-            x = ops.cache_forecast(cache["ring"], cache["w"], cache["fc"])[:]
-            p = f"up_blocks.{n - 1}"
-            for j in range(cut, lpb + 1):
-                x = self._resnet(f"{p}.resnets.{j}", x, skips.pop(), geo, feeds_transformer=True)
-                x = self._text_transformer(f"{p}.attentions.{j}", x, geo)
-                x = self._temporal_transformer(f"{p}.temporal_attentions.{j}", x, geo, cond_frame)
-            x = self._gn(x, None, B, Fr * H * W, "conv_norm_out", self.eps, True)
-            return ops.conv_out(x, w["conv_out.weight"], w["conv_out.bias"], B, Fr, H, W)
-        for i in range(n):
-            p = f"down_blocks.{i}"
-            for j in range(lpb):
-                x = self._resnet(f"{p}.resnets.{j}", x, None, geo, feeds_transformer=i < n - 1)
-                if i < n - 1:
-                    x = self._text_transformer(f"{p}.attentions.{j}", x, geo)
-                    x = self._temporal_transformer(f"{p}.temporal_attentions.{j}", x, geo, cond_frame)
-                skips.append(x)
-            if i < n - 1:
-                x = ops.conv3x3(x, w[f"{p}.downsamplers.0.conv.weight"], B * Fr, geo[2], geo[3], stride=2,
-                                bias=w[f"{p}.downsamplers.0.conv.bias"],
-                                colsum_batch=self._cb(B, Fr * ((geo[2] - 1) // 2 + 1) * ((geo[3] - 1) // 2 + 1)))
-                geo = (B, Fr, (geo[2] - 1) // 2 + 1, (geo[3] - 1) // 2 + 1)
-                skips.append(x)
-        x = self._resnet("mid_block.resnets.0", x, None, geo, feeds_transformer=True)
-        x = self._text_transformer("mid_block.attentions.0", x, geo)
-        x = self._temporal_transformer("mid_block.temporal_attentions.0", x, geo, cond_frame)
-        x = self._resnet("mid_block.resnets.1", x, None, geo)
-        for i in range(n):
-            p = f"up_blocks.{i}"
-            for j in range(lpb + 1):
-                if cache is not None and i == n - 1 and j == cut:
-                    ops.cache_push(x, cache["ring"])                # phase 0: the cut feature joins the ring; x itself is only read
-                x = self._resnet(f"{p}.resnets.{j}", x, skips.pop(), geo, feeds_transformer=i > 0)
-                if i > 0:
-                    x = self._text_transformer(f"{p}.attentions.{j}", x, geo)
-                    x = self._temporal_transformer(f"{p}.temporal_attentions.{j}", x, geo, cond_frame)
-            if i < n - 1:
-                x = ops.conv_up2x(x, w[f"{p}.upsamplers.0.conv.weight_up4"], B * Fr, geo[2], geo[3],
-                                  bias=w[f"{p}.upsamplers.0.conv.bias"], colsum_batch=self._cb(B, Fr * 4 * geo[2] * geo[3]))
+            elif kind == "down":
+                Ho, Wo = (geo[2] - 1) // 2 + 1, (geo[3] - 1) // 2 + 1
+                x = ops.conv3x3(x, w[st.name + ".weight"], B * Fr, geo[2], geo[3], stride=2, bias=w[st.name + ".bias"],
+                                colsum_batch=plan.colsum_batch(Fr * Ho * Wo))
+                geo = (B, Fr, Ho, Wo)
+            elif kind == "up":
+                x = ops.conv_up2x(x, w[st.name + ".weight_up4"], B * Fr, geo[2], geo[3], bias=w[st.name + ".bias"],
+                                  colsum_batch=plan.colsum_batch(Fr * 4 * geo[2] * geo[3]))
                 geo = (B, Fr, geo[2] * 2, geo[3] * 2)
-        x = self._gn(x, None, B, Fr * geo[2] * geo[3], "conv_norm_out", self.eps, True)
+            elif kind == "gn_out":
+                x = self._gn(x, None, B, Fr * geo[2] * geo[3], st.name, self.eps, True)
+            elif kind == "cache_push":
+                ops.cache_push(x, cache["ring"])                # phase 0: the cut feature joins the ring; x itself is only read
+            elif kind == "cache_forecast":
+                # the forecast cut feature: a fresh view of the static buffer, without column sums -- norm1 takes its statistics
+                # pass, as behind ops.freeu
+                x = ops.cache_forecast(cache["ring"], cache["w"], cache["fc"])[:]
         out = ops.conv_out(x, w["conv_out.weight"], w["conv_out.bias"], B, Fr, geo[2], geo[3])
         if return_attn:
             attn, self._attn_list = self._attn_list, None

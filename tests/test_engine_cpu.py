@@ -121,7 +121,7 @@ def test_engine_return_attn_matches_oracle(mini):
 
 @pytest.mark.parametrize("B,Fr,H,cond_frame", [(1, 2, 16, 0), (2, 3, 8, 1)])
 def test_engine_runs_the_row_chains(mini, B, Fr, H, cond_frame):
-    """host logic of the row-local chains (unet._Engine._rc_in, _chain_ok; ops.rowchain): at 320 channels GroupNorm -> proj_in -> norm1
+    """host logic of the row-local chains (unet._Engine._rc_in, _LaunchPlan.runs; ops.rowchain): at 320 channels GroupNorm -> proj_in -> norm1
     -> q|k|v (rotary on the temporal block's q and k, the q prescale) and attn1.to_out + residual -> norm2 -> attn2.to_q are one call
     each -- the statistics come from the producers' accumulated sums (the producer of a chain's input accumulates whatever its size),
     the residual stream is updated in place -- and the schedule lands on the oracle like the separate launches do"""

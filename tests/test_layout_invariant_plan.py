@@ -14,7 +14,7 @@ import torch
 
 from seervideoldm_amd import SeerUNet, _lib, synth
 from seervideoldm_amd import ops as real_ops
-from seervideoldm_amd.unet import _Engine
+from seervideoldm_amd.unet import _Engine, _LaunchPlan
 from tests import shape_ops_backend as sob
 from tests.recording_ops_backend import RecordingOps
 
@@ -268,9 +268,13 @@ def test_a_clip_sharded_too_finely_is_refused_from_the_shard_table():
     model = SeerUNet(**dict(synth.SD15_UNET_CFG), layout_invariant=True).to("meta")
     eng = _Engine(model, ops=RecordingOps(1))
     # 64 rows per frame; this rank holds 2 frames (128 rows), the last rank 1 (64 rows); 9 280 rows over the clip: the launch pays
-    eng.shard = SimpleNamespace(local_frames=2, total_frames=145, frame_counts=[2] * 72 + [1], exact_stats=True)
+    # The refusal comes while the evaluation's plan is made (unet._LaunchPlan: B = 1, the rank's 2 frames of 8 x 8), before any launch.
+    shard = dict(local_frames=2, exact_stats=True, local_cond_frames=lambda cond_frame: cond_frame)
+    eng.shard = SimpleNamespace(total_frames=145, frame_counts=[2] * 72 + [1], **shard)
     with pytest.raises(RuntimeError, match="fewer frame shards"):
-        eng._chain_ok(320, 1, 2 * 64)
-    eng.shard = SimpleNamespace(local_frames=2, total_frames=146, frame_counts=[2] * 73, exact_stats=True)
-    assert eng._chain_ok(320, 1, 2 * 64) is True
-    assert eng._chain_ok(640, 1, 2 * 64) is False
+        _LaunchPlan(eng, 1, 2, 8, 8, 0)
+    assert eng.ops.calls == []
+    eng.shard = SimpleNamespace(total_frames=146, frame_counts=[2] * 73, **shard)
+    plan = _LaunchPlan(eng, 1, 2, 8, 8, 0)
+    assert plan.runs("chain", 320, 2 * 64) is True
+    assert plan.runs("chain", 640, 2 * 64) is False
